@@ -158,7 +158,15 @@ def main():
                     help="NOT a measurement: after the ranks have been created (see ensure_world) every rank joins the process group, the ranks "
                          "all-gather their (rank, pid) and rank 0 prints them as one JSON line -- what tests/test_bench_launch_cpu.py runs over gloo "
                          "to pin that `--gpus N` alone produces N ranks; needs no HIP device")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed -- the rasterizer's outputs and the gradients a caller "
+                         "receives -- as DIR/<name>.npy (float32; integer outputs as float64).  An array above 4 MiB is written as a fixed sample of "
+                         "its rows (triangles, or pixels with their channels), drawn by a generator seeded with the array's name; N = 1 only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs is not None and args.gpus > 1:
+        ap.error("--dump-outputs is a single-GPU option")
     if args.hip_graph:
         args.sync_free = True
     args.exchange_compare = args.gpus > 1 and not args.no_exchange_compare
@@ -251,7 +259,7 @@ def main():
     sink = parallel.ShGradSink()
     vis_rows = parallel.VisibleRows(bucket_group if world > 1 else None, dev) if (world > 1 and args.sparse_exchange) else None
 
-    state = {"step": 0, "overlap": overlap, "pending": None}
+    state = {"step": 0, "overlap": overlap, "pending": None, "keep": False}
     optimizer = None
     if args.with_optimizer:
         if world > 1:
@@ -269,6 +277,12 @@ def main():
             state["shs_grad"] = shx[i % len(shx)].wait()  # dense dL_dshs summed over all ranks' views (one each)
         e1.record()
         wait_events.append((e0, e1))
+
+    def keep(out, center2D):
+        """--dump-outputs: references to what this step hands its caller (no copy, no kernel); written after the timed steps."""
+        state["last"] = dict(zip(("out_feature", "radii", "depth", "normal", "contrib_sum", "contrib_max"), out))
+        if not args.forward_only:
+            state["last"].update(dL_dvertex=vertex.grad, dL_dshs=shs.grad, dL_dopacity=opacity.grad, dL_dcenter2D=center2D.grad)
 
     def step():
         center2D = center2D_sink(P, dev)  # the caller's gradient sink (triangle_renderer.py:67), as diff_recon_hip.TriangleRenderer makes it: a fresh leaf per step, no fill kernel
@@ -302,12 +316,16 @@ def main():
             with torch.no_grad():
                 out = raster(vertex, center2D, opacity, shs=shs)
             state["image"] = out[0]
+            if state["keep"]:
+                keep(out, center2D)
             return
         else:
             out = raster(vertex, center2D, opacity, shs=shs)
             torch.autograd.backward([out[0], out[2], out[3]], [g_feat, g_depth, g_norm])
         if optimizer is not None:
             optimizer.step()
+        if state["keep"]:
+            keep(out, center2D)
         state["num_rendered"] = out[0].grad_fn.num_rendered
         state["image"] = out[0]
         vertex.grad = None
@@ -369,8 +387,10 @@ def main():
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
+        state["keep"] = args.dump_outputs is not None  # the captured step's tensors: every replay, the last timed one included, rewrites them
         with torch.cuda.graph(graph):
             step()
+        state["keep"] = False
         torch.cuda.synchronize()
         step = graph.replay
         if events:
@@ -391,10 +411,13 @@ def main():
         state["overlap"] = delayed
         wait_events.clear()
         stamps, marks = [], [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+        keep_at = args.steps - 1 if args.dump_outputs is not None and not args.hip_graph else -1
         barrier()
         t_start = time.perf_counter()
         marks[0].record()
         for k in range(args.steps):
+            if k == keep_at:
+                state["keep"] = True  # eager: the last timed step keeps what it computed
             step()
             marks[k + 1].record()               # ONE event per step on the launch stream: see `device_step_ms`
             stamps.append(time.perf_counter())  # host time at which the step was queued (no synchronisation added): see `host_step_ms`
@@ -403,6 +426,7 @@ def main():
             state["pending"] = None
         barrier()
         took = time.perf_counter() - t_start
+        state["keep"] = False
         exposed = sum(a.elapsed_time(b) for a, b in wait_events) / max(args.steps, 1) if wait_events else None
         return took, [t_start] + stamps, marks, exposed
 
@@ -425,6 +449,8 @@ def main():
         barrier()
         warm_rows = _C.profile_read()
     gc.enable()
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, state.pop("last"))
     t0 = stamps[0]
     stamps = stamps[1:]
     device_seq = [a.elapsed_time(b) for a, b in zip(marks[:-1], marks[1:])]
@@ -544,6 +570,27 @@ def main():
         print(json.dumps(result), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_ARRAY_BYTES = 4 << 20  # per array: the at most ten outputs of a step stay far below 64 MB
+IMAGE_OUTPUTS = ("out_feature", "depth", "normal")  # (C, H, W) or (H, W); every other output has one row per triangle
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: writes {name: tensor} as out_dir/<name>.npy.  Floating-point outputs stay float32, integer ones become float64
+    (exact).  An array above DUMP_ARRAY_BYTES keeps a fixed sample of its rows -- triangles, or pixels with all their channels (images
+    become (pixels, C)) -- in ascending order, drawn by a generator seeded with the name: the same arguments give the same rows."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float32 if np.issubdtype(a.dtype, np.floating) else np.float64)
+        if a.nbytes > DUMP_ARRAY_BYTES:
+            rows = a.reshape(-1, a.shape[-2] * a.shape[-1]).T if name in IMAGE_OUTPUTS else a
+            k = max(1, DUMP_ARRAY_BYTES * rows.shape[0] // rows.nbytes)
+            pick = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(rows.shape[0], k, replace=False))
+            a = np.ascontiguousarray(rows[pick])
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def ensure_world(args):

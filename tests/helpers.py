@@ -294,13 +294,19 @@ def _sweep_device_caches():
 
 
 def ref3d_builds(s, rich=True, back=False, use_feature=False, fuzz_seed=None):
-    """{build: outputs} of the reference's 3D extension built three ways on the scene `s`, or None when oracle/_ref is absent or the
-    reference died on this scene.  The reference runs in a server process of its own (tests/ref_worker.py): it aborts on some inputs
-    it was never exercised on (degenerate random configurations, and a few structured ones), which must not end the test session."""
+    """{build: outputs} of the reference's 3D extension built three ways on the scene `s`, or None when oracle/_ref is absent, the
+    reference cannot run the scene's mode (rich=False, below) or it died on this scene.  The reference runs in a server process of its
+    own (tests/ref_worker.py): it aborts on some inputs it was never exercised on (degenerate random configurations), which must not
+    end the test session."""
     import os
     import tempfile
     here = os.path.dirname(os.path.abspath(__file__))
     if not all(os.path.exists(os.path.join(os.path.dirname(here), "oracle", "_ref", b + ".so")) for b in R3D_BUILDS):
+        return None
+    if not rich:
+        # the reference's 3D backward reads the per-triangle normal gradients unconditionally (R3D backward.cu:176) but allocates them
+        # only with rich_info (rasterizer.cu:279-282): without it every backward reads unallocated device memory.  Its own Python module
+        # never gets there (its backward needs the depth / normal gradients of rich_info).  These scenes are compared with the oracle.
         return None
     with tempfile.TemporaryDirectory() as tmp:
         scene, out = os.path.join(tmp, "scene.npz"), os.path.join(tmp, "ref.npz")

@@ -31,6 +31,8 @@ def forward_backward(s, rich_info=True, back_culling=False, use_feature=False, v
     """One scene through the reference's rasterize_triangles / rasterize_triangles_backward (R2D/ext.cpp:6-8, R3D/ext.cpp).
     `build` names another build of the same sources (oracle/build_ref.py CODEGEN_FLAGS), e.g. "_ref3d_scalar_C"."""
     import torch
+    if variant == 3 and not rich_info:  # its backward would read unallocated memory (tests/helpers.py:ref3d_builds)
+        raise ValueError("the reference's 3D extension runs its backward only with rich_info")
     ref = load(build or ("_ref2d_C" if variant == 2 else "_ref3d_C"))
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
     empty = torch.empty(0, device=device)

@@ -4,7 +4,8 @@ TS2D_FLAG_3D (through diff_triangle_rasterization_3D -> ctypes -> C ABI) against
 All integer state must match the oracle bit for bit.  The floating-point outputs are held to ONE criterion (helpers.py,
 "THE criterion for the floating-point outputs of the 3D variant"): without any outlier budget or mask, the product must sit inside
 the spread of the reference's own three builds (oracle/_ref: hipcc defaults, -fno-slp-vectorize, -ffp-contract=off = the oracle).
-Only where those builds are unavailable (oracle/_ref absent, or the reference process died on a degenerate configuration) the
+Only where those builds are unavailable (oracle/_ref absent, rich_info=False -- which the reference's 3D backward cannot run -- or the
+reference process died on a degenerate configuration) the
 comparison falls back to the oracle alone, with every deviating triangle EXPLAINED in float64 (arg-min tie / edge-on view)."""
 import numpy as np
 import pytest

@@ -278,9 +278,9 @@ def _ref_request(line, timeout=600):
 def _sweep_device_caches():
     """Called after the reference-kernel server died.  It dies of GPU memory-access faults inside the reference's kernels, and on this platform
     a process that faults leaves the SURVIVING processes on the device with stale cache lines: the next large launch of this process can then
-    read memory as it was before its own memset / atomics (whole 128-byte lines of the backward's gradient records; tests/triage/fuzz_flow.py
-    reproduces it with a neighbour that runs none of the reference's code, tests/triage/gpu_faulter.py: 6 of 8 runs wrong, none without a
-    faulting neighbour, none with this sweep -- profiles/r04_neighbour_fault.txt).  Writing and re-reading 2 GiB pushes every line of the
+    read memory as it was before its own memset / atomics (whole 128-byte lines of the backward's gradient records; measured in round 4 with
+    a faulting neighbour that ran none of the reference's code: 6 of 8 runs wrong, none without a faulting neighbour, none with this sweep --
+    profiles/r04_neighbour_fault.txt).  Writing and re-reading 2 GiB pushes every line of the
     eight L2s and of the memory-side cache out while nothing of this process is live."""
     import torch
     if not torch.cuda.is_available():

@@ -1,7 +1,7 @@
 """Runs parity cases against the oracle in a SEPARATE process that loads the lab library (tools/bin/libts2d_lab.so: the product's
-objects + the measurement kernels of earlier rounds, selected by TS2D_BLEND / TS2D_BWD).  The product library has none of them.
+objects + the switches and readers of csrc/ts2d_lab.h).  The product library has none of them.
 
-    TS2D_LIBRARY_PATH=tools/bin/libts2d_lab.so TS2D_BWD=mfma python tests/lab_worker.py
+    TS2D_LIBRARY_PATH=tools/bin/libts2d_lab.so LAB_FORCE_TICKETS=1 python tests/lab_worker.py
 """
 import json
 import os

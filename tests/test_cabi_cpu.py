@@ -42,7 +42,7 @@ def test_library_exports_every_declared_symbol(lib):
 
 def test_product_library_reads_no_environment_and_has_one_blend_path(hip_lib_built):
     """libts2d.so carries one blend kernel family per variant (the lane-group kernels) and no run-time switch: the measurement
-    kernels of earlier rounds and their TS2D_BLEND / TS2D_BWD / TS2D_ABLATE variables exist only in tools/bin/libts2d_lab.so."""
+    kernels of earlier rounds and their TS2D_BLEND / TS2D_BWD / TS2D_ABLATE variables were removed and must not come back."""
     import subprocess
     blob = open(hip_lib_built, "rb").read()
     for name in (b"TS2D_BLEND", b"TS2D_BWD", b"TS2D_ABLATE"):

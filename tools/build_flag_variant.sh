@@ -27,20 +27,13 @@ pids="$pids $!"
 for p in $pids; do wait $p; done
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o $R/tools/bin/libts2d_$TAG.so $O/*.o
 echo $R/tools/bin/libts2d_$TAG.so
-# the matching lab library (state reader, test hooks, the measurement kernels of earlier rounds): the variant's objects, api.hip compiled with -DTS2D_LAB
+# the matching lab library (state reader, test hooks): the variant's objects, api.hip compiled with -DTS2D_LAB
 mkdir -p $O/lab
-pids=""
-for SRC in render render3d render_q8 lab_hooks api; do
-  X=""
-  case $SRC in
-    render*) X="-mllvm -amdgpu-atomic-optimizer-strategy=None -fno-slp-vectorize";;
-    api) X="-DTS2D_LAB";;
-  esac
-  D=$R/tools/lab; [ $SRC = api ] && D=$R/triangle-splatting_amd/csrc   # the lab kernels live in tools/lab/ since round 6
-  /opt/rocm/bin/hipcc $F $X -I$R/triangle-splatting_amd/csrc "$@" -c $D/$SRC.hip -o $O/lab/$SRC.o &
-  pids="$pids $!"
-done
-for p in $pids; do wait $p; done
+/opt/rocm/bin/hipcc $F -I$R/triangle-splatting_amd/csrc "$@" -c $R/tools/lab/lab_hooks.hip -o $O/lab/lab_hooks.o &
+P1=$!
+/opt/rocm/bin/hipcc $F -DTS2D_LAB "$@" -c $R/triangle-splatting_amd/csrc/api.hip -o $O/lab/api.o &
+P2=$!
+wait $P1; wait $P2
 OBJS=$(ls $O/*.o | grep -v "/api.o")
-/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o $R/tools/bin/libts2d_lab_$TAG.so $OBJS $O/lab/*.o
+/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o $R/tools/bin/libts2d_lab_$TAG.so $OBJS $O/lab/lab_hooks.o $O/lab/api.o
 echo $R/tools/bin/libts2d_lab_$TAG.so

@@ -3,12 +3,12 @@
     python triangle-splatting_amd/build.py [--force] [--verbose] [--lab]
 
 Output: triangle-splatting_amd/diff_triangle_rasterization_2D/libts2d.so (git-ignored, travels with gpurun).
---lab builds tools/bin/libts2d_lab.so instead: the same objects + the measurement kernels of earlier rounds (tools/lab/: render.hip, render3d.hip,
-render_q8.hip, lab_hooks.hip) and api.hip compiled with -DTS2D_LAB, which reads TS2D_BLEND / TS2D_BWD / TS2D_ABLATE.  The product library contains
-one blend path per variant and reads no environment; only tools/ and tests/ load the lab library (TS2D_LIBRARY_PATH, see _C.py).
+--lab builds tools/bin/libts2d_lab.so instead: the same objects + the test hooks of tools/lab/lab_hooks.hip and api.hip compiled with
+-DTS2D_LAB, which exports the switches and readers of csrc/ts2d_lab.h.  The product library contains one blend path per variant and reads no
+environment; only tools/ and tests/ load the lab library (TS2D_LIBRARY_PATH, see _C.py).
 hipcc cross-compiles without a GPU.  Per-file flags matter:
   * preprocess.hip is built with -ffp-contract=off (bit-comparable integer state, see the file header);
-  * render.hip uses the default fast contraction and hardware float atomics (-munsafe-fp-atomics).
+  * the blend kernels use the default fast contraction and hardware float atomics (-munsafe-fp-atomics).
 """
 from __future__ import annotations
 
@@ -29,7 +29,7 @@ ARCH = "gfx950"
 
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function",
           "-Wno-unused-result", "-DNDEBUG", "-fvisibility=hidden"]  # exports = what include/*.h declares (api.hip), nothing else
-COMMON += os.environ.get("TS2D_EXTRA_FLAGS", "").split()  # profiling builds: -DTS2D_ABLATION, -DTS2D_STATS (use --force)
+COMMON += os.environ.get("TS2D_EXTRA_FLAGS", "").split()  # profiling builds: -DTS2D_STATS (use --force)
 SOURCES = {
     "preprocess.hip": ["-ffp-contract=off"],
     "preprocess3d.hip": ["-ffp-contract=off"],
@@ -50,16 +50,12 @@ SOURCES = {
     "render3d_group.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None", "-fno-slp-vectorize"],
     "api.hip": [],
 }
-LAB_SOURCES = {  # measurement kernels: libts2d_lab.so only
-    "render.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None", "-fno-slp-vectorize"],
-    "render3d.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None", "-fno-slp-vectorize"],
-    "render_q8.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None", "-fno-slp-vectorize"],
+LAB_SOURCES = {  # libts2d_lab.so only
     "lab_hooks.hip": [],  # sort / scan test hooks + their rocPRIM comparators (csrc/ts2d_lab.h)
     "api.hip": ["-DTS2D_LAB"],
 }
 LAB_LIB = os.path.join(os.path.dirname(HERE), "tools", "bin", "libts2d_lab.so")
-LAB_SRC = os.path.join(os.path.dirname(HERE), "tools", "lab")  # render.hip, render3d.hip, render_q8.hip, lab_hooks.hip: measurement kernels of rounds 1-3 and the
-                                                                # test hooks -- out of the product's csrc/ since round 6; they include csrc's headers (-I)
+LAB_SRC = os.path.join(os.path.dirname(HERE), "tools", "lab")  # lab_hooks.hip: the test hooks, outside the product's csrc/; it includes csrc's headers (-I)
 HEADERS = ["ts2d_common.h", "ts2d_lab.h", "ts2d_math.h", "ts2d_wave.h", "ts2d_group.h", "ts2d_support.h", "ts2d_sh.h", "ts2d_stage.h", "ts2d_preprocess_launch.h", "ts2d_imgops.h", "ts2d_select.h", os.path.join("..", "..", "include", "ts2d.h"),
            os.path.join("..", "..", "include", "ts_loss.h"),
            os.path.join("..", "..", "include", "ts_knn.h"),
@@ -88,27 +84,42 @@ def _newest_header() -> float:
     return max(os.path.getmtime(os.path.join(CSRC, h)) for h in HEADERS)
 
 
+def _sources(lab: bool) -> dict:
+    if not lab:
+        return dict(SOURCES)
+    sources = {k: v for k, v in SOURCES.items() if k != "api.hip"}  # the product's objects are shared
+    sources.update({("lab/" + k): v for k, v in LAB_SOURCES.items()})
+    return sources
+
+
+def _object(key: str) -> str:
+    src, _, part = key.partition("@")  # "file.hip@tag": the same source compiled into file_tag.o with its own flags
+    return os.path.join(OBJ_DIR, src.replace(".hip", ("_" + part if part else "") + ".o"))
+
+
+def objects(lab: bool = False) -> list:
+    """The objects build(lab=lab) links (tools/build_stats_lib.sh relinks them with a few replaced)."""
+    return [_object(k) for k in _sources(lab)]
+
+
 def build(force: bool = False, verbose: bool = False, lab: bool = False) -> str:
     os.makedirs(OBJ_DIR, exist_ok=True)
     cc = hipcc()
     hdr_t = max(_newest_header(), os.path.getmtime(os.path.abspath(__file__)))
     jobs, objs = [], []
-    sources = dict(SOURCES)
     lib = LIB
     if lab:
         build(force, verbose)  # the product's objects are shared
-        sources = {k: v for k, v in SOURCES.items() if k != "api.hip"}
-        sources.update({("lab/" + k): v for k, v in LAB_SOURCES.items()})
         lib = LAB_LIB
         os.makedirs(os.path.join(OBJ_DIR, "lab"), exist_ok=True)
         os.makedirs(os.path.dirname(LAB_LIB), exist_ok=True)
-    for src, extra in sources.items():
-        src, _, part = src.partition("@")  # "file.hip@tag": the same source compiled into file_tag.o with its own flags
+    for key, extra in _sources(lab).items():
+        src = key.partition("@")[0]
         s = os.path.join(CSRC, os.path.basename(src))
         if not os.path.exists(s):  # a lab-only source
             s = os.path.join(LAB_SRC, os.path.basename(src))
             extra = list(extra) + ["-I" + CSRC]
-        o = os.path.join(OBJ_DIR, src.replace(".hip", ("_" + part if part else "") + ".o"))
+        o = _object(key)
         objs.append(o)
         cmd = [cc, *COMMON, *extra, "-c", s, "-o", o]
         # the object is only reused when it was produced by this very command line with this very compiler: a profiling build

@@ -43,9 +43,11 @@ struct Cull3
     bool ov[4];
 };
 
-// Conservative culling against the four 4x4 blocks of the quadrant.  With u2 = v2 - v1, u3 = v3 - v1 and r = hit point - v1,
-// Den r = n x (delta x v1) where p_ray = v1 / v1.z + delta (see the derivation in render3d.hip: affine in the pixel offset, no
-// pole at grazing incidence); a2 = r.(u3 x n) / n.n, a3 = r.(n x u2) / n.n, a1 = 1 - a2 - a3.
+// Conservative culling against the four 4x4 blocks of the quadrant.  With u2 = v2 - v1, u3 = v3 - v1, n = u2 x u3 and r = hit point - v1
+// (in the plane), r = a2 u2 + a3 u3, so a2 = r.(u3 x n) / n.n, a3 = r.(n x u2) / n.n, a1 = 1 - a2 - a3.  The hit point is (d0 / Den) p_ray
+// with Den = p_ray.n and d0 = v1.n, hence Den r = d0 p_ray - Den v1 = n x (p_ray x v1).  Writing p_ray = v1 / v1.z + delta (the ray through
+// v1 plus a small in-image offset) the first part drops out exactly and Den r = n x (delta x v1), delta = delta0 + (qx sx, qy sy, 0): affine
+// in the pixel offset q, no pole where the ray grazes the plane, and no more digits lost than in the reference's own p_vk = v_k - p_view.
 template <bool GAMMA1>
 __device__ __forceinline__ Cull3 cull3(V3 v1, V3 v2, V3 v3, V3 n, float op, float g2, V3 ray0, float sx, float sy)
 {
@@ -436,7 +438,7 @@ __global__ void __launch_bounds__(64 * WPB, TS3G_BWD_WAVES) render3d_bwd_group_k
     float T = inside ? final_T[pix] : 0.0f;
     const int last = inside ? (int)n_contrib[pix] : 0;
     float dpr = 0.0f, dpg = 0.0f, dpb = 0.0f, dnx = 0.0f, dny = 0.0f, dnz = 0.0f, dd = 0.0f, B = 0.0f;
-    if (inside) // backward.cu:283-295; one scalar back-to-front composite B = sum_c dL_dpix_c accum_c (see render.hip)
+    if (inside) // backward.cu:283-295; one scalar back-to-front composite B = sum_c dL_dpix_c accum_c (derived at the backward of render_group.hip)
     {
         dpr = dL_dout_feature[pix];
         B = dpr * a.background[0];

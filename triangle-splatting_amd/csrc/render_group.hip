@@ -439,8 +439,11 @@ __global__ void __launch_bounds__(256, TSG_FWD_WAVES) render_fwd_group_kernel(Re
 // pair's 16 values are formed per lane exactly in the reference's per-pixel form (no moment / epilogue algebra):
 //   dL/dv_j (screen space) = perp(t_j) / area2 with  t_1 = e_3 p_v2 - e_2 p_v3,  t_2 = e_1 p_v3 - e_3 p_v1,  t_3 = e_2 p_v1 - e_1 p_v2,
 //   e_k = dL/da_k - sum_m dL/da_m a_m     (backward.cu:464-479 regrouped: v2_v3 = p_v3 - p_v2 etc.; perp(x, y) = (y, -x)),
-// the division by area2 is applied once per entry when the sums are flushed.  The reference's seven back-to-front
-// composites per pixel collapse to one scalar B = sum_c dL_dpix_c * accum_c (same mathematics, see render.hip).
+// the division by area2 is applied once per entry when the sums are flushed.  The reference keeps seven back-to-front
+// composites per pixel (accum_feature[3], accum_normal, accum_depth: backward.cu:323-325) but uses them only through
+// dL_dcontrib = sum_c dL_dpix_c * (value_c - accum_c).  With X = sum_c dL_dpix_c * value_c and B = sum_c dL_dpix_c * accum_c
+// that is X - B, and the per-channel update accum_c <- alpha value_c + (1 - alpha) accum_c collapses to
+// B <- alpha X + (1 - alpha) B: one scalar of sequential state instead of seven (same mathematics, different rounding order).
 // Each group reduces its 16 values over its 16 lanes (DPP row transpose-reduce) and adds them into the entry's row of a
 // wave-private LDS table (one group after the other: two groups may be working on the same entry); once per batch the rows
 // leave as coalesced 64-byte atomic adds, one gradient record per 16 lanes.

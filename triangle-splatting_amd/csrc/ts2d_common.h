@@ -27,8 +27,8 @@
 // Quadrant masks (ts2d_support.h): the emission kernel marks in the four spare bits of an instance's value which 8x8 quadrants of its tile the
 // triangle's support can reach, and the blend kernels' quadrant waves gather and cull only those entries, in dense batches.  Round 4,
 // measured against plain lists alternating on one box (profiles/r04_qmask.txt): render_fwd 0.429 -> 0.398 ms, render_bwd 0.839 -> 0.791,
-// emission 0.029 -> 0.053, step 1.658 -> 1.604.  The plain-list front end was deleted from the product in round 5 (it lives on in the lab
-// kernels render.hip / render_q8.hip, which ignore the mask bits): triangle ids are < 2^28 everywhere (validate() in api.hip).
+// emission 0.029 -> 0.053, step 1.658 -> 1.604.  The plain-list front end was deleted in round 5; every blend kernel reads the mask bits, and
+// triangle ids are < 2^28 everywhere (validate() in api.hip).
 #define TS_ID_BITS 28
 #define TS_ID_MASK 0x0FFFFFFFu
 // Gradient record (16 floats = 64 B), accumulated by render_bwd, consumed by preprocess_bwd.
@@ -279,16 +279,7 @@ struct RenderArgs
     const float *background; // C floats, device
     const float *background_depth_dev; // optional: one float on the device that overrides background_depth (ts2d_geometry)
     bool rich_info;
-    int ablate; // profiling only (env TS2D_ABLATE, builds with -DTS2D_ABLATION): 0 = full kernel; see render.hip
-    int legacy_blend; // measurement only (env TS2D_BLEND=wave, read once): round-1 one-triangle-per-wave blend kernels
-    int bwd_mfma;  // experiment (env TS2D_BWD=mfma): render_bwd forms its per-entry sums with f32 MFMA instead of VALU reduction networks
 };
-void ts_launch_render_fwd(const RenderArgs &a, const GeometryStateView &g, const BinningStateView &b,
-                          const ImageStateView &im, float *out_feature, float *out_depth, float *out_normal,
-                          float *contrib_sum, float *contrib_max, hipStream_t s);
-void ts_launch_render_bwd(const RenderArgs &a, const GeometryStateView &g, const BinningStateView &b,
-                          const ImageStateView &im, const float *dL_dout_feature, const float *dL_dout_depth,
-                          const float *dL_dout_normal, float *grad_rec, hipStream_t s);
 // lane-group blend kernels (render_group.hip): four 4x4 pixel blocks per wave, one triangle per block and step
 void ts_launch_render_fwd_group(const RenderArgs &a, const GeometryStateView &g, const BinningStateView &b,
                                 const ImageStateView &im, float *out_feature, float *out_depth, float *out_normal,
@@ -296,11 +287,6 @@ void ts_launch_render_fwd_group(const RenderArgs &a, const GeometryStateView &g,
 void ts_launch_render_bwd_group(const RenderArgs &a, const GeometryStateView &g, const BinningStateView &b,
                                 const ImageStateView &im, const float *dL_dout_feature, const float *dL_dout_depth,
                                 const float *dL_dout_normal, float *grad_rec, hipStream_t s);
-// queue kernels (render_q8.hip; lab library only, selected with TS2D_BLEND=q8): eight 4x2 pixel blocks per wave, each walking its own queue of triangles
-void ts_launch_render_fwd_q8(const RenderArgs &a, const GeometryStateView &g, const BinningStateView &b, const ImageStateView &im,
-                             float *out_feature, float *out_depth, float *out_normal, float *contrib_sum, float *contrib_max, hipStream_t s);
-void ts_launch_render_bwd_q8(const RenderArgs &a, const GeometryStateView &g, const BinningStateView &b, const ImageStateView &im,
-                             const float *dL_dout_feature, const float *dL_dout_depth, const float *dL_dout_normal, float *grad_rec, hipStream_t s);
 void ts_launch_preprocess_bwd(const PreprocessArgs &a, const int32_t *radii, const GeometryStateView &g,
                               const float *grad_rec, float *dL_dvertex, float *dL_dcenter2D, float *dL_dshs,
                               float *dL_dfeature, float *dL_dopacity, hipStream_t s);
@@ -312,14 +298,8 @@ void ts_launch_preprocess3d_fwd(const PreprocessArgs &a, int32_t *radii, const G
 void ts_launch_preprocess3d_bwd(const PreprocessArgs &a, const int32_t *radii, const GeometryStateView &g,
                                 const float *grad_rec, float *dL_dvertex, float *dL_dcenter2D, float *dL_dshs,
                                 float *dL_dfeature, float *dL_dopacity, hipStream_t s);
-void ts_launch_render3d_fwd(const RenderArgs &a, float tan_fovx, float tan_fovy, const GeometryStateView &g,
-                            const BinningStateView &b, const ImageStateView &im, float *out_feature, float *out_depth,
-                            float *out_normal, float *contrib_sum, float *contrib_max, hipStream_t s);
-void ts_launch_render3d_bwd(const RenderArgs &a, float tan_fovx, float tan_fovy, const GeometryStateView &g,
-                            const BinningStateView &b, const ImageStateView &im, const float *dL_dout_feature,
-                            const float *dL_dout_depth, const float *dL_dout_normal, float *grad_rec, hipStream_t s);
 
-// lane-group kernels with the reference's per-pixel ray / plane arithmetic (render3d_group.hip); the default
+// lane-group kernels with the reference's per-pixel ray / plane arithmetic (render3d_group.hip)
 void ts_launch_render3d_fwd_group(const RenderArgs &a, float tan_fovx, float tan_fovy, const GeometryStateView &g,
                                   const BinningStateView &b, const ImageStateView &im, float *out_feature, float *out_depth,
                                   float *out_normal, float *contrib_sum, float *contrib_max, hipStream_t s);

@@ -73,44 +73,11 @@ __device__ __forceinline__ int carry_over(uint32_t &id, int &pos, bool keep, int
 }
 
 // ---- 16-lane (DPP row) transpose-reduce: N values per lane -> each lane keeps the row-wide reduction of ONE value ----
-// Level 1 pairs lanes l, l ^ 8 (row_ror:8), level 2 lanes inside a group of 8 (row_half_mirror), level 3 l, l ^ 2, then l, l ^ 1.
-struct RowSel
-{
-    bool b3, b2, b1;
-    __device__ __forceinline__ explicit RowSel(int lane) : b3(lane & 8), b2(lane & 4), b1(lane & 2) {}
-};
-template <typename Op>
-__device__ __forceinline__ float pair_ror8(float x, float y, bool b, Op op)
-{
-    const float own = b ? y : x, oth = b ? x : y;
-    return op(own, dpp<DPP_ROR8>(oth));
-}
-template <typename Op>
-__device__ __forceinline__ float pair_hmir(float x, float y, bool b, Op op)
-{
-    const float own = b ? y : x, oth = b ? x : y;
-    return op(own, dpp<DPP_HALF_MIRROR>(oth));
-}
-template <typename Op>
-__device__ __forceinline__ float pair_xor2(float x, float y, bool b, Op op)
-{
-    const float own = b ? y : x, oth = b ? x : y;
-    return op(own, dpp<DPP_XOR2>(oth));
-}
-// 8 values: the result of value (b3 + 2 b2 + 4 b1) lands in lanes l and l ^ 1
-template <typename Op>
-__device__ __forceinline__ float row_reduce8(const float (&c)[8], const RowSel &r, Op op)
-{
-    const float s0 = pair_ror8(c[0], c[1], r.b3, op), s1 = pair_ror8(c[2], c[3], r.b3, op);
-    const float s2 = pair_ror8(c[4], c[5], r.b3, op), s3 = pair_ror8(c[6], c[7], r.b3, op);
-    const float t0 = pair_hmir(s0, s1, r.b2, op), t1 = pair_hmir(s2, s3, r.b2, op);
-    const float v = pair_xor2(t0, t1, r.b1, op);
-    return op(v, dpp<DPP_XOR1>(v));
-}
-// Sum AND maximum of 8 values over the 16 lanes of each DPP row in one pass (the forward's contribution statistics): the transposed network of
-// row_reduce8 with the write masks of row_reduce16 -- levels 1 and 2 pair lanes of different DPP banks, so "which half keeps which value" is the
+// Sum AND maximum of 8 values over the 16 lanes of each DPP row in one pass (the forward's contribution statistics): an 8-value
+// transpose-reduce (level 1 pairs lanes l, l ^ 8 via row_ror:8, level 2 lanes inside a group of 8 via row_half_mirror, level 3 l, l ^ 2, then
+// l, l ^ 1) with the write masks of row_reduce16 -- levels 1 and 2 pair lanes of different DPP banks, so "which half keeps which value" is the
 // instruction's own bank mask (two v_add/v_max_f32_dpp per pair instead of two v_cndmask + one; every one of them half rate on gfx950): 32
-// instructions for both results against 44.  The two chains are interleaved so that no DPP operand is read within two wait states of its
+// instructions for both results against 44 with v_cndmask selects.  The two chains are interleaved so that no DPP operand is read within two wait states of its
 // write; level 1 writes fresh registers (the inputs stay intact for the caller).  Lanes l and l ^ 1 end up with step (b3 + 2 b2 + 4 b1).
 __device__ __forceinline__ void row_reduce8_sum_max(const float (&c)[8], unsigned long long mask_b1, float &sum, float &mx)
 {
@@ -143,12 +110,6 @@ __device__ __forceinline__ void row_reduce8_sum_max(const float (&c)[8], unsigne
 #undef TSG8_QP
     sum = s3;
     mx = m3;
-}
-__device__ __forceinline__ uint32_t row_select8(const uint32_t (&c)[8], const RowSel &r)
-{
-    const uint32_t s0 = r.b3 ? c[1] : c[0], s1 = r.b3 ? c[3] : c[2], s2 = r.b3 ? c[5] : c[4], s3 = r.b3 ? c[7] : c[6];
-    const uint32_t t0 = r.b2 ? s1 : s0, t1 = r.b2 ? s3 : s2;
-    return r.b1 ? t1 : t0;
 }
 
 // 16 values: the row-wide sum of the value fed at position (b3 + 2 b2 + 4 b1 + 8 b0) lands in the lane -- callers feed

@@ -6,7 +6,7 @@ src/diff_recon/renderer/triangle_renderer.py:5-6 when `rasterizer_type == "3D"`.
 differ only in where `.contiguous()` is applied (the 3D extension makes its inputs contiguous itself instead of
 raising, R3D/src/extension_interface.cu:82-92), so this package reuses the 2D package's classes and flips the native
 variant: same libts2d.so, entry points called with TS2D_FLAG_3D (include/ts2d.h), which selects preprocess3d.hip and
-render3d.hip (ray/plane intersection, 3D barycentrics, unnormalised normals).
+render3d_group.hip (ray/plane intersection, 3D barycentrics, unnormalised normals).
 """
 from __future__ import annotations
 

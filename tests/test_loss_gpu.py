@@ -196,6 +196,30 @@ def test_background_depth_equals_the_torch_expression(P):
     assert float(background_depth(vertex.requires_grad_(True), campos)) == float(got)
 
 
+@pytest.mark.parametrize("P", [85, 700001])
+@pytest.mark.parametrize("bad", ["nan", "inf", "nan_and_inf"])
+def test_background_depth_follows_the_torch_expression_through_non_finite_vertices(P, bad):
+    """VanillaTS_model.py:623 on a diverged model: torch's max over the distances is NaN as soon as one distance is NaN, and inf when one
+    coordinate is infinite.  The kernel's running maximum must not drop a NaN (fmaxf would, and the depth image would stay finite)."""
+    import torch
+    from diff_recon_hip import background_depth
+    g = torch.Generator().manual_seed(P)
+    vertex = (torch.randn(P, 3, 3, generator=g) * 7.0)
+    if bad in ("nan", "nan_and_inf"):
+        vertex[P // 3, 1, 2] = float("nan")  # one coordinate of one vertex, inside the range of some block other than the first
+    if bad in ("inf", "nan_and_inf"):
+        vertex[P - 1, 2, 0] = float("inf")  # the last vertex of the array
+    vertex = vertex.cuda()
+    campos = torch.tensor([0.3, -2.0, 11.0], device="cuda")
+    got = float(background_depth(vertex, campos))
+    want = float((campos.view(1, 1, 3) - vertex).norm(dim=-1).max())
+    assert (want != want) == (bad != "inf") and (want == float("inf")) == (bad == "inf")  # the torch expression itself: NaN wins over inf
+    if want != want:
+        assert got != got, got
+    else:
+        assert got == want, (got, want)
+
+
 def _dn_golden():
     import os
     return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "depth_normal.npz"))

@@ -154,18 +154,22 @@ __global__ void __launch_bounds__(256) gather_rows_kernel(int64_t total_words, i
     dst[(dst_row0 + j) * row_words + col] = src[(int64_t)idx[j] * row_words + col];
 }
 
+// |a - b| as torch's GPU norm over the last dimension of three forms it: (x^2 + z^2) + y^2, no contraction, correctly rounded square root
 __device__ __forceinline__ float side_len(const float *a, const float *b)
 {
+#pragma clang fp contract(off)
     const float x = a[0] - b[0], y = a[1] - b[1], z = a[2] - b[2];
-    return sqrtf(x * x + y * y + z * z);
+    return sqrtf((x * x + z * z) + y * y);
 }
-// get_scaling (VanillaTS_model.py:72-76): mean side length, sides in the order (v3 - v2, v1 - v3, v2 - v1)
+// get_scaling (VanillaTS_model.py:72-76): mean side length, sides in the order (v3 - v2, v1 - v3, v2 - v1).  Side lengths and mean are formed
+// the way torch's GPU norm and mean over three elements form them -- the mean as (l1 + l3) + l2, times float(1/3) -- so that a triangle whose
+// mean side lies on a threshold, or whose sides tie, is decided as in the reference (tests/test_model_ops_gpu.py)
 __device__ __forceinline__ float mean_side(const float *v, float &l1, float &l2, float &l3)
 {
     l1 = side_len(v + 6, v + 3);
     l2 = side_len(v + 0, v + 6);
     l3 = side_len(v + 3, v + 0);
-    return (l1 + l2 + l3) / 3.0f;
+    return ((l1 + l3) + l2) * (1.0f / 3.0f);
 }
 
 // _densification (:365-383) + the classification of _grow_points (:260-263): code 0 = untouched, 1 = clone, 2 = split;
@@ -257,14 +261,18 @@ __global__ void __launch_bounds__(256) opacity_reset_kernel(int P, float reset_v
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= P) return;
-    const float x = fminf(sigmoidf(opacity[i]), reset_value);
-    opacity[i] = logf(x / (1.0f - x)); // inverse_sigmoid, model_utils.py
+    const float o = sigmoidf(opacity[i]);
+    const float x = o > reset_value ? reset_value : o; // torch.min: a NaN opacity stays NaN (fminf would drop it)
+    opacity[i] = logf(x / (1.0f - x));                 // inverse_sigmoid, model_utils.py
     if (exp_avg) { exp_avg[i] = 0.0f; exp_avg_sq[i] = 0.0f; }
 }
 // bg_depth of VanillaTSModel.forward (:623): max over all vertices of |camera_center - vertex|.  torch spends three kernels on it (subtract, norm, max:
 // 61 us per view at 1 M triangles, profiles/r06_train_step_kernels.txt); this is one read of the vertices.  Distances are >= 0, so the unsigned bit
-// pattern orders like the value and one atomicMax per block lands the result (`out` zeroed by max_distance_zero_kernel in front).
+// pattern orders like the value and one atomicMax per block lands the result (`out` zeroed by max_distance_zero_kernel in front).  Like torch's max, a NaN
+// distance wins (nan_max below, where fmaxf would drop it): any NaN's unsigned pattern (0x7FC00000, 0xFFC00000, ...) is above +inf's 0x7F800000.
 __global__ void max_distance_zero_kernel(uint32_t *__restrict__ out) { out[0] = 0u; }
+
+__device__ __forceinline__ float nan_max(float m, float d) { return (d > m || d != d) ? d : m; } // m NaN stays NaN: d > NaN is false
 
 __global__ void __launch_bounds__(256) max_distance_kernel(int n, const float *__restrict__ vertex, const float *__restrict__ campos,
                                                            uint32_t *__restrict__ out)
@@ -275,13 +283,13 @@ __global__ void __launch_bounds__(256) max_distance_kernel(int n, const float *_
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256)
     {
         const float dx = cx - vertex[3 * (size_t)i], dy = cy - vertex[3 * (size_t)i + 1], dz = cz - vertex[3 * (size_t)i + 2];
-        m = fmaxf(m, __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+        m = nan_max(m, __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
     }
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    for (int o = 32; o > 0; o >>= 1) m = nan_max(m, __shfl_xor(m, o));
     if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0)
-        atomicMax(out, __float_as_uint(sqrtf(fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3])))));
+        atomicMax(out, __float_as_uint(sqrtf(nan_max(nan_max(wmax[0], wmax[1]), nan_max(wmax[2], wmax[3])))));
 }
 } // namespace
 

@@ -54,8 +54,9 @@ _lib.tsm_max_vertex_distance.argtypes = [ctypes.c_int32] + [ctypes.c_void_p] * 4
 
 def background_depth(vertex: torch.Tensor, camera_center: torch.Tensor) -> torch.Tensor:
     """VanillaTS_model.py:623, `(camera_center - vertex).norm(dim=-1).max()`: a 0-dim device tensor, by one read of the vertices
-    (include/ts_model.h: tsm_max_vertex_distance) instead of torch's three kernels.  It is a raster SETTING (the rasterizer package reads it
-    as a number), so it carries no gradient here as it carries none into the reference's rasterizer."""
+    (include/ts_model.h: tsm_max_vertex_distance) instead of torch's three kernels; like torch's max it is NaN as soon as one vertex is NaN,
+    inf for an infinite one.  It is a raster SETTING (the rasterizer package reads it as a number), so it carries no gradient here as it
+    carries none into the reference's rasterizer."""
     v = vertex.detach()
     if not v.is_cuda:
         raise RuntimeError("background_depth: the vertices live on the GPU (there is no CPU path)")

@@ -1,5 +1,7 @@
 """Profiling aid: times render_fwd / render_bwd of the headline scene (HIP events of libts2d's profile hook), rich and plain,
-and prints the lane-group statistics when the library was built with -DTS2D_STATS."""
+and prints the lane-group statistics when the library was built with -DTS2D_STATS:
+    python triangle-splatting_amd/build.py --variant stats --lab --unit render_group_fwd=-DTS2D_STATS --unit render_group_bwd=-DTS2D_STATS
+    TS2D_LIBRARY_PATH=tools/bin/libts2d_stats.so python tests/triage/blend_probe.py   (libts2d_lab_stats.so: the lab library with the counters)"""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "triangle-splatting_amd"), os.path.join(ROOT, "tests")]

@@ -1,11 +1,17 @@
 """Builds libts2d.so (the C-ABI HIP library of include/ts2d.h) for gfx950 with hipcc, in-tree.
 
     python triangle-splatting_amd/build.py [--force] [--verbose] [--lab]
+    python triangle-splatting_amd/build.py --variant TAG [--lab] [--all "FLAGS"] [--unit NAME="FLAGS" ...]
 
 Output: triangle-splatting_amd/diff_triangle_rasterization_2D/libts2d.so (git-ignored, travels with gpurun).
---lab builds tools/bin/libts2d_lab.so instead: the same objects + the test hooks of tools/lab/lab_hooks.hip and api.hip compiled with
+--lab builds tools/bin/libts2d_lab.so as well: the same objects + the test hooks of tools/lab/lab_hooks.hip and api.hip compiled with
 -DTS2D_LAB, which exports the switches and readers of csrc/ts2d_lab.h.  The product library contains one blend path per variant and reads no
 environment; only tools/ and tests/ load the lab library (TS2D_LIBRARY_PATH, see _C.py).
+--variant TAG builds an A/B or instrumentation variant instead: each unit named by --unit (an object name of objects(): render_group_fwd,
+lab/api, ...) is compiled with the product's own command line plus FLAGS into build/variants/TAG/; --all appends FLAGS to every unit (the lab
+units too with --lab).  Every other unit links the product's object.  Output: tools/bin/libts2d_TAG.so, with --lab also
+tools/bin/libts2d_lab_TAG.so (TS2D_LIBRARY_PATH / TS2D_LAB_LIBRARY_PATH); the product's libraries are not written.  E.g. the lane-group
+statistics build: --variant stats --lab --unit render_group_fwd=-DTS2D_STATS --unit render_group_bwd=-DTS2D_STATS.
 hipcc cross-compiles without a GPU.  Per-file flags matter:
   * preprocess.hip is built with -ffp-contract=off (bit-comparable integer state, see the file header);
   * the blend kernels use the default fast contraction and hardware float atomics (-munsafe-fp-atomics).
@@ -15,6 +21,8 @@ from __future__ import annotations
 import argparse
 import hashlib
 import os
+import re
+import shlex
 import shutil
 import subprocess
 import sys
@@ -24,12 +32,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "diff_triangle_rasterization_2D")
 OBJ_DIR = os.path.join(HERE, "build")
+VARIANT_DIR = os.path.join(OBJ_DIR, "variants")
 LIB = os.path.join(OUT_DIR, "libts2d.so")
 ARCH = "gfx950"
 
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function",
           "-Wno-unused-result", "-DNDEBUG", "-fvisibility=hidden"]  # exports = what include/*.h declares (api.hip), nothing else
-COMMON += os.environ.get("TS2D_EXTRA_FLAGS", "").split()  # profiling builds: -DTS2D_STATS (use --force)
 SOURCES = {
     "preprocess.hip": ["-ffp-contract=off"],
     "preprocess3d.hip": ["-ffp-contract=off"],
@@ -54,7 +62,8 @@ LAB_SOURCES = {  # libts2d_lab.so only
     "lab_hooks.hip": [],  # sort / scan test hooks + their rocPRIM comparators (csrc/ts2d_lab.h)
     "api.hip": ["-DTS2D_LAB"],
 }
-LAB_LIB = os.path.join(os.path.dirname(HERE), "tools", "bin", "libts2d_lab.so")
+BIN_DIR = os.path.join(os.path.dirname(HERE), "tools", "bin")
+LAB_LIB = os.path.join(BIN_DIR, "libts2d_lab.so")
 LAB_SRC = os.path.join(os.path.dirname(HERE), "tools", "lab")  # lab_hooks.hip: the test hooks, outside the product's csrc/; it includes csrc's headers (-I)
 HEADERS = ["ts2d_common.h", "ts2d_lab.h", "ts2d_math.h", "ts2d_wave.h", "ts2d_group.h", "ts2d_support.h", "ts2d_sh.h", "ts2d_stage.h", "ts2d_preprocess_launch.h", "ts2d_imgops.h", "ts2d_select.h", os.path.join("..", "..", "include", "ts2d.h"),
            os.path.join("..", "..", "include", "ts_loss.h"),
@@ -92,38 +101,67 @@ def _sources(lab: bool) -> dict:
     return sources
 
 
-def _object(key: str) -> str:
+def _unit(key: str) -> str:
     src, _, part = key.partition("@")  # "file.hip@tag": the same source compiled into file_tag.o with its own flags
-    return os.path.join(OBJ_DIR, src.replace(".hip", ("_" + part if part else "") + ".o"))
+    return src[: -len(".hip")] + ("_" + part if part else "")
 
 
-def objects(lab: bool = False) -> list:
-    """The objects build(lab=lab) links (tools/build_stats_lib.sh relinks them with a few replaced)."""
-    return [_object(k) for k in _sources(lab)]
+def units(lab: bool = False) -> list:
+    """The translation units build(lab=lab) links, in link order: their objects' paths under build/ without .o."""
+    return [_unit(k) for k in _sources(lab)]
 
 
-def build(force: bool = False, verbose: bool = False, lab: bool = False) -> str:
-    os.makedirs(OBJ_DIR, exist_ok=True)
+def _object(unit: str, variant: str | None = None) -> str:
+    return os.path.join(OBJ_DIR if variant is None else os.path.join(VARIANT_DIR, variant), unit + ".o")
+
+
+def objects(lab: bool = False, variant: str | None = None, extra: dict | None = None) -> list:
+    """The objects build(lab=lab, variant=variant, extra=extra) links: a unit with extra flags from the variant's directory, the others the product's."""
+    extra = extra or {}
+    return [_object(u, variant if extra.get(u) else None) for u in units(lab)]
+
+
+def library(lab: bool = False, variant: str | None = None) -> str:
+    if variant is None:
+        return LAB_LIB if lab else LIB
+    return os.path.join(BIN_DIR, f"libts2d_lab_{variant}.so" if lab else f"libts2d_{variant}.so")
+
+
+def command(unit: str, extra=(), variant: str | None = None, cc: str = "hipcc") -> list:
+    """The compile command of one unit: COMMON + its SOURCES / LAB_SOURCES entry, then `extra`; with extra flags the object goes to the variant's directory."""
+    table = {_unit(k): (k, v) for lab in (False, True) for k, v in _sources(lab).items()}
+    if unit not in table:
+        raise ValueError(f"unknown unit {unit!r}; the units are {', '.join(table)}")
+    key, flags = table[unit]
+    src = os.path.join(CSRC, os.path.basename(key.partition("@")[0]))
+    if not os.path.exists(src):  # a lab-only source
+        src = os.path.join(LAB_SRC, os.path.basename(src))
+        flags = list(flags) + ["-I" + CSRC]
+    return [cc, *COMMON, *flags, *extra, "-c", src, "-o", _object(unit, variant if extra else None)]
+
+
+def build(force: bool = False, verbose: bool = False, lab: bool = False, variant: str | None = None, extra: dict | None = None) -> str:
+    """Compiles the stale objects and links libts2d.so (lab: and libts2d_lab.so, returned).  variant = TAG: tools/bin/libts2d_TAG.so (lab: and
+    libts2d_lab_TAG.so, returned) instead, the units named in extra = {unit: [flags]} compiled with those flags appended."""
+    extra = {u: list(f) for u, f in (extra or {}).items() if f}
+    if variant is None and extra:
+        raise ValueError("extra flags need a variant tag")
+    if variant is not None and not re.fullmatch(r"[A-Za-z0-9_.+-]+", variant):
+        raise ValueError(f"bad variant tag {variant!r}")
+    libs = [False, True] if lab else [False]
+    known = dict.fromkeys(u for l in libs for u in units(l))
+    unknown = [u for u in extra if u not in known]
+    if unknown:
+        raise ValueError(f"unknown unit(s) {', '.join(unknown)}; the units are {', '.join(known)}" + ("" if lab else " (lab units need --lab)"))
     cc = hipcc()
     hdr_t = max(_newest_header(), os.path.getmtime(os.path.abspath(__file__)))
-    jobs, objs = [], []
-    lib = LIB
-    if lab:
-        build(force, verbose)  # the product's objects are shared
-        lib = LAB_LIB
-        os.makedirs(os.path.join(OBJ_DIR, "lab"), exist_ok=True)
-        os.makedirs(os.path.dirname(LAB_LIB), exist_ok=True)
-    for key, extra in _sources(lab).items():
-        src = key.partition("@")[0]
-        s = os.path.join(CSRC, os.path.basename(src))
-        if not os.path.exists(s):  # a lab-only source
-            s = os.path.join(LAB_SRC, os.path.basename(src))
-            extra = list(extra) + ["-I" + CSRC]
-        o = _object(key)
-        objs.append(o)
-        cmd = [cc, *COMMON, *extra, "-c", s, "-o", o]
-        # the object is only reused when it was produced by this very command line with this very compiler: a profiling build
-        # (TS2D_EXTRA_FLAGS=-DTS2D_STATS ...) or a toolchain update must not leave its objects behind for the next plain build
+    jobs = []
+    for u in known:
+        cmd = command(u, extra.get(u, ()), variant, cc)
+        s, o = cmd[-3], cmd[-1]
+        os.makedirs(os.path.dirname(o), exist_ok=True)
+        # the object is only reused when it was produced by this very command line with this very compiler: a toolchain update must not leave
+        # its objects behind for the next build
         stamp, key = o + ".cmd", _toolchain_id(cc) + "\n" + " ".join(cmd)
         fresh = os.path.exists(o) and os.path.exists(stamp) and open(stamp).read() == key
         if force or not fresh or os.path.getmtime(o) < max(os.path.getmtime(s), hdr_t):
@@ -148,8 +186,12 @@ def build(force: bool = False, verbose: bool = False, lab: bool = False) -> str:
 
     with ThreadPoolExecutor(max_workers=4) as ex:
         list(ex.map(compile_one, jobs))
-    if jobs or force or not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(o) for o in objs):
-        run([cc, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", lib, *objs])
+    compiled = {cmd[-1] for cmd, _, _ in jobs}
+    for l in libs:
+        lib, objs = library(l, variant), objects(l, variant, extra)
+        if force or not os.path.exists(lib) or compiled.intersection(objs) or os.path.getmtime(lib) < max(os.path.getmtime(o) for o in objs):
+            os.makedirs(os.path.dirname(lib), exist_ok=True)
+            run([cc, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", lib, *objs])
     return lib
 
 
@@ -158,5 +200,21 @@ if __name__ == "__main__":
     ap.add_argument("--force", action="store_true")
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("--lab", action="store_true")
-    a = ap.parse_args()
-    print(build(a.force, a.verbose, a.lab))
+    ap.add_argument("--variant", metavar="TAG")
+    ap.add_argument("--all", metavar="FLAGS", default="", help="extra flags for every unit")
+    ap.add_argument("--unit", metavar="NAME=FLAGS", action="append", default=[], help="extra flags for one unit")
+    # "--all -DX": glued to its option, or argparse would take a value that starts with "-" for an option of its own
+    argv, it = [], iter(sys.argv[1:])
+    for arg in it:
+        argv.append(arg + "=" + next(it, "") if arg in ("--all", "--unit") else arg)
+    a = ap.parse_args(argv)
+    extra = {u: shlex.split(a.all) for l in ([False, True] if a.lab else [False]) for u in units(l)} if a.all else {}
+    for spec in a.unit:
+        name, eq, flags = spec.partition("=")
+        if not eq:
+            ap.error(f"--unit {spec}: expected NAME=FLAGS")
+        extra[name] = extra.get(name, []) + shlex.split(flags)
+    try:
+        print(build(a.force, a.verbose, a.lab, a.variant, extra))
+    except ValueError as e:
+        ap.error(str(e))

@@ -103,16 +103,12 @@ __device__ __forceinline__ bool resolve_count(const unsigned long long *n_dev, i
 // Which chunk a workgroup of a radix pass works on.  Workgroups go to the 8 XCDs round-robin (block b -> XCD b % 8); XCD x takes the chunks
 // [x n / 8, (x + 1) n / 8): consecutive chunks write adjacent pieces of every digit's run (32 - 64 elements = one or two cache lines each),
 // and with ONE XCD behind both halves of a shared line the two partial writes meet in one L2 instead of two (round 4: tile sort 73 -> 69 us,
-// depth sort 48 -> 45 us against chunk = blockIdx, -DTS_RS_XCD_ROUND_ROBIN).  The partition follows the LIVE chunk count, so a launch that
+// depth sort 48 -> 45 us against chunk = blockIdx, measured and dropped: profiles/r04_notes.md).  The partition follows the LIVE chunk count, so a launch that
 // covers a larger capacity (speculative / sync-free forward) stays balanced over the XCDs.
 __device__ __forceinline__ int rs_chunk_of_block(int nchunks)
 {
-#ifdef TS_RS_XCD_ROUND_ROBIN
-    return (int)blockIdx.x < nchunks ? (int)blockIdx.x : -1;
-#else
     const int q = nchunks >> 3, r = nchunks & 7, x = blockIdx.x & 7, i = blockIdx.x >> 3;
     return i < q + (x < r ? 1 : 0) ? x * q + min(x, r) + i : -1;
-#endif
 }
 
 // Digit counts of every chunk, and -- by the blocks that arrive last -- their prefixes: the last block of a slab (64 chunks)
@@ -741,13 +737,10 @@ constexpr uint32_t SMALL = 32;
 
 // Round 5, measured on three scenes with the five combinations alternating on one box (profiles/r05_emission_variants.txt; tools/r05_call4.sh):
 // a register budget for 6 waves per SIMD (80 registers, 3 spilled; the compiler's own choice is 94 = 5 waves) is worth 0-3 %, and requesting
-// the rectangle / record gather EARLY, under the block sums and the scan, costs 10 % (1 M triangles: 0.054 -> 0.064 ms; 5 M: 0.245 -> 0.277):
-// the gather's 96-128 bytes per lane sit in registers across the scan and the loads queue in front of the block sums the scan waits for.
+// the rectangle / record gather EARLY, under the block sums and the scan, cost 10 % and was dropped (1 M triangles: 0.054 -> 0.064 ms; 5 M:
+// 0.245 -> 0.277): the gather's 96-128 bytes per lane sit in registers across the scan and the loads queue in front of the block sums.
 #ifndef TS_EMIT_WAVES // register budget for N waves per SIMD (0: the compiler's choice)
 #define TS_EMIT_WAVES 6
-#endif
-#ifndef TS_EMIT_PREFETCH
-#define TS_EMIT_PREFETCH 0
 #endif
 #if TS_EMIT_WAVES > 0
 __global__ void __launch_bounds__(256, TS_EMIT_WAVES) scan_emit_kernel(
@@ -777,20 +770,6 @@ int P, int grid_x, int ntiles, GeometryStateView g, BinningStateView b, uint2 *r
     const bool valid = i < P;
     uint32_t tiles = valid ? g.tiles_sorted[i] : 0u;
     const uint32_t id_ahead = valid ? sorted_ids(g)[i] : 0u; // wanted after the scan: requested now, one round trip less behind it
-    // (-DTS_EMIT_PREFETCH=1: what hangs on it -- the tile rectangle and the head of the render record -- requested as soon as the id is there; a
-    // measured negative, see above)
-    uint2 rect = {0u, 0u};
-    float4 rec0 = make_float4(0, 0, 0, 0), rec1 = rec0, rec2 = rec0;
-#if TS_EMIT_PREFETCH
-    if (tiles > 0)
-    {
-        rect = g.rect[id_ahead];
-        const float4 *rp = g.rec + 4 * (size_t)id_ahead;
-        rec0 = rp[0];
-        rec1 = rp[1];
-        if (qmask.variant == 3) rec2 = rp[2];
-    }
-#endif
     // Everything in front of this block, requested together and reduced once: the earlier quarters of this scan block (scan blocks are 1024
     // triangles = four of these 256-lane blocks), the raw sums of the scan blocks of its group of 64, the group sums in front of that.
     const int sblock = blockIdx.x >> 2, quarter = blockIdx.x & 3;
@@ -828,7 +807,8 @@ int P, int grid_x, int ntiles, GeometryStateView g, BinningStateView b, uint2 *r
     if (valid) g.offsets[i] = incl;
     const uint32_t id = tiles > 0 ? id_ahead : 0u;
     const uint32_t off = incl - tiles; // exclusive prefix
-#if !TS_EMIT_PREFETCH
+    uint2 rect = {0u, 0u};
+    float4 rec0 = make_float4(0, 0, 0, 0), rec1 = rec0, rec2 = rec0;
     if (tiles > 0)
     {
         rect = g.rect[id];
@@ -837,7 +817,6 @@ int P, int grid_x, int ntiles, GeometryStateView g, BinningStateView b, uint2 *r
         rec1 = rp[1];
         if (qmask.variant == 3) rec2 = rp[2];
     }
-#endif
     const uint32_t minx = rect.x & 0xffffu, miny = rect.x >> 16, maxx = rect.y & 0xffffu, maxy = rect.y >> 16;
     uint32_t *tile_out = b.k[0], *val_out = b.v[0];
     // the four spare bits of an instance's value say which 8x8 quadrants of its tile the triangle's support can reach (ts2d_support.h; both
@@ -1185,7 +1164,7 @@ __global__ void __launch_bounds__(64 * DS_WAVES) depth_order_small_kernel(int P,
 // Measured against the LSD passes alternating on one box (profiles/r06_depth_split.txt): 93 k triangles 57 -> 43 us (step 0.335 -> 0.321 ms), 300 k
 // 59 -> 47 (0.613 -> 0.605), 1 M 75 -> 65 us of kernels and NO difference in the step (the largest bucket holds 7 500 pairs = 8 steps x 2 passes of
 // a ranking that is issue-bound with 16 waves on the compute unit: K3 takes 35 us there) -- hence the switch-over below.
-#ifndef TS_DEPTH_SPLIT_MAX_VALUE // (variant builds: tools/build_obj_variant.sh ... binning "-DTS_DEPTH_SPLIT_MAX_VALUE=1600000")
+#ifndef TS_DEPTH_SPLIT_MAX_VALUE // (variant builds: build.py --variant TAG --unit binning=-DTS_DEPTH_SPLIT_MAX_VALUE=1600000)
 #define TS_DEPTH_SPLIT_MAX_VALUE 500000
 #endif
 constexpr int TS_DEPTH_SPLIT_MAX = TS_DEPTH_SPLIT_MAX_VALUE; // the product's switch-over: measured level with the LSD passes at 1 M triangles, ahead below

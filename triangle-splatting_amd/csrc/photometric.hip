@@ -55,63 +55,22 @@ __device__ __forceinline__ float wave_sum(float v)
 // column from 14 row-contiguous ds_read_b32 per array (consecutive lanes = consecutive columns).  A first version stored the row results
 // transposed to read them back as b128 columns: the counters (profiles/r06_loss_pmc.txt) showed 63 % of its LDS cycles were bank conflicts and no
 // gain over round 1.  Summation order per output is unchanged (taps 0..10 in sequence): same bits as round 1's kernels.
-#ifndef TS_SSIM_WG_PER_XCD
-#define TS_SSIM_WG_PER_XCD (1 << 24) /* workgroups per XCD: one per tile.  160 (= 32 compute units x 5 resident workgroups: persistent, the next tile's
-                                        loads in flight under the current tile's passes) was measured: SLOWER, 0.104 vs 0.089 ms forward -- the prefetch
-                                        registers cost a wave per SIMD and the kernel is not waiting for memory (profiles/r06_loss_pmc.txt) */
-#endif
 constexpr int LW = 48;            // LDS tile width: TW + 2 x 8 (the 5-pixel halo rounded to float4s)
 constexpr int LWP = 52;           // its row stride in floats
 constexpr int HS = TW + 4;        // row stride of the row-pass results (floats): 16-byte aligned rows, consecutive rows 4 banks apart
 
-// Tiles -> workgroups, XCD-aware and persistent.  Workgroups go to the 8 XCDs round-robin and every XCD has its own L2: XCD k takes the k-th eighth
-// of the tiles in (plane, y, x) order -- a band of tile rows, so that the tiles that share halo columns and halo rows meet in ONE L2 -- and the
-// workgroups of an XCD walk through that eighth together (workgroup j of the XCD takes tiles j, j + n, j + 2 n, ...).  A workgroup issues the global
-// loads of its NEXT tile into registers before it computes the current one: the two barriers and the dependent LDS phases of a tile otherwise
-// leave every wave waiting for memory at the top of each tile (3.9 waves per SIMD, VALU 31 % busy, profiles/r06_loss_pmc.txt).
-struct TileWalk
+// Tiles -> workgroups, XCD-aware, one tile per workgroup.  Workgroups go to the 8 XCDs round-robin and every XCD has its own L2: XCD k takes the
+// k-th eighth of the tiles in (plane, y, x) order -- a band of tile rows, so that the tiles that share halo columns and halo rows meet in ONE L2.
+// Persistent workgroups that load the next tile under the current one were measured slower and dropped (0.104 vs 0.089 ms forward: the prefetch
+// registers cost a wave per SIMD; profiles/r06_loss_pmc.txt).  False for the padding of the grid (a multiple of 8 workgroups).
+__device__ __forceinline__ bool tile_of_workgroup(int gx, int gy, int planes, int &tx, int &ty, int &tz)
 {
-    int nb, per, xcd, j, stride, gx, gy;
-    __device__ __forceinline__ TileWalk(int gx_, int gy_, int planes) : gx(gx_), gy(gy_)
-    {
-        nb = gx * gy * planes; per = (nb + 7) >> 3; xcd = (int)(blockIdx.x & 7); j = (int)(blockIdx.x >> 3); stride = (int)(gridDim.x >> 3);
-    }
-    __device__ __forceinline__ bool valid(int jj) const { return jj < per && xcd * per + jj < nb; }
-    __device__ __forceinline__ void decode(int jj, int &tx, int &ty, int &tz) const
-    {
-        const int t = xcd * per + jj;
-        tx = t % gx; ty = (t / gx) % gy; tz = t / (gx * gy);
-    }
-};
-constexpr bool PERSISTENT = TS_SSIM_WG_PER_XCD < (1 << 24); // compile time: the one-tile-per-workgroup form carries no prefetch registers and no loop
-constexpr int NPRE = (IH * 12 + 255) / 256; // float4 pieces of a halo tile per thread and array (IH rows x 12 float4)
-
-template <int NARR>
-__device__ __forceinline__ void prefetch_issue(float4 (&pre)[NARR][NPRE], const float *const (&src)[NARR], int x0, int y0, int H, int W, int tid)
-{
-#pragma unroll
-    for (int q = 0; q < NPRE; q++)
-    {
-        const int i = tid + 256 * q;
-        const int r = i / 12, qq = i - r * 12;
-        const int gy = y0 + r - R, gx = x0 - 8 + 4 * qq;
-        const bool in = i < IH * 12 && gy >= 0 && gy < H && gx >= 0 && gx < W; // W % 4 == 0 and gx % 4 == 0: four columns inside or outside together
-#pragma unroll
-        for (int a = 0; a < NARR; a++) pre[a][q] = in ? *(const float4 *)(src[a] + (size_t)gy * W + gx) : make_float4(0.0f, 0.0f, 0.0f, 0.0f); // zero padding, trainer_utils.py:42-43
-    }
-}
-template <int NARR>
-__device__ __forceinline__ void prefetch_commit(float (*dst)[IH][LWP], const float4 (&pre)[NARR][NPRE], int tid)
-{
-#pragma unroll
-    for (int q = 0; q < NPRE; q++)
-    {
-        const int i = tid + 256 * q;
-        const int r = i / 12, qq = i - r * 12;
-        if (i < IH * 12)
-#pragma unroll
-            for (int a = 0; a < NARR; a++) *(float4 *)&dst[a][r][4 * qq] = pre[a][q];
-    }
+    const int nb = gx * gy * planes, per = (nb + 7) >> 3, xcd = (int)(blockIdx.x & 7), j = (int)(blockIdx.x >> 3);
+    const bool valid = j < per && xcd * per + j < nb;
+    if (!valid) return false;
+    const int t = xcd * per + j;
+    tx = t % gx; ty = (t / gx) % gy; tz = t / (gx * gy);
+    return true;
 }
 
 template <int NARR, bool VEC>
@@ -172,40 +131,15 @@ __global__ void __launch_bounds__(256) ssim_l1_fwd_kernel(const float *__restric
     __shared__ __attribute__((aligned(16))) float hb[5][IH][HS];
     __shared__ float red[2][4];
     const int tid = threadIdx.x;
-    TileWalk walk(gx, gy, planes);
-    bool have = walk.valid(walk.j);
-    int tx = 0, ty = 0, tz = 0;
-    float4 pre[(PERSISTENT && VEC) ? 2 : 1][NPRE];
-    if (!have) return; // the grid is padded to a multiple of 8
-    walk.decode(walk.j, tx, ty, tz);
-    if (PERSISTENT && VEC)
-    {
-        const float *const src0[2] = {img + (size_t)tz * H * W, gt + (size_t)tz * H * W};
-        prefetch_issue<2>((float4(&)[2][NPRE])pre, src0, tx * TW, ty * TH, H, W, tid);
-    }
-    do
-    {
+    int tx, ty, tz;
+    if (!tile_of_workgroup(gx, gy, planes, tx, ty, tz)) return;
     const int x0 = tx * TW, y0 = ty * TH;
     const size_t plane = (size_t)tz * H * W;
-    const int ctx = tx, cty = ty, ctz = tz;
-    if (PERSISTENT && VEC) prefetch_commit<2>(sIG, (const float4(&)[2][NPRE])pre, tid);
-    else
     {
         const float *const src[2] = {img + plane, gt + plane};
         load_halo_tile<2, VEC>(sIG, src, x0, y0, H, W, tid);
     }
     __syncthreads();
-    if (PERSISTENT)
-    {
-        walk.j += walk.stride;
-        have = walk.valid(walk.j);
-        if (have)
-        {
-            walk.decode(walk.j, tx, ty, tz);
-            const float *const srcn[2] = {img + (size_t)tz * H * W, gt + (size_t)tz * H * W};
-            if (VEC) prefetch_issue<2>((float4(&)[2][NPRE])pre, srcn, tx * TW, ty * TH, H, W, tid); // in flight while this tile is computed
-        }
-    }
     if (tid < IH * (TW / 4)) // rows: four adjacent outputs per thread
     {
         const int r = tid >> 3, c0 = 4 * (tid & 7);
@@ -275,11 +209,9 @@ __global__ void __launch_bounds__(256) ssim_l1_fwd_kernel(const float *__restric
     __syncthreads();
     if (tid == 0)
     {
-        const int b = (ctz * gy + cty) * gx + ctx;
+        const int b = (tz * gy + ty) * gx + tx;
         partial[b] = make_float2(red[0][0] + red[0][1] + red[0][2] + red[0][3], red[1][0] + red[1][1] + red[1][2] + red[1][3]);
     }
-    // (the barrier above also separates this tile's last reads of sIG / hb from the next tile's commit)
-    } while (PERSISTENT && have);
 }
 
 // 1024 threads: at 1080p there are 12 240 partial pairs, and 256 threads walking 48 of them each + an 8-level LDS tree of doubles took 15 us
@@ -313,41 +245,15 @@ __global__ void __launch_bounds__(256) ssim_l1_bwd_kernel(const float *__restric
     __shared__ __attribute__((aligned(16))) float sM[3][IH][LWP];
     __shared__ __attribute__((aligned(16))) float hb[3][IH][HS];
     const int tid = threadIdx.x;
-    TileWalk walk(gx, gy, planes);
-    bool have = walk.valid(walk.j);
-    int tx = 0, ty = 0, tz = 0;
-    float4 pre[(PERSISTENT && VEC) ? 3 : 1][NPRE];
-    if (!have) return;
-    walk.decode(walk.j, tx, ty, tz);
-    if (PERSISTENT && VEC)
-    {
-        const size_t pl = (size_t)tz * H * W;
-        const float *const src0[3] = {d_mu + pl, d_s1 + pl, d_s12 + pl};
-        prefetch_issue<3>((float4(&)[3][NPRE])pre, src0, tx * TW, ty * TH, H, W, tid);
-    }
-    do
-    {
+    int tx, ty, tz;
+    if (!tile_of_workgroup(gx, gy, planes, tx, ty, tz)) return;
     const int x0 = tx * TW, y0 = ty * TH;
     const size_t plane = (size_t)tz * H * W;
-    if (PERSISTENT && VEC) prefetch_commit<3>(sM, (const float4(&)[3][NPRE])pre, tid);
-    else
     {
         const float *const src[3] = {d_mu + plane, d_s1 + plane, d_s12 + plane};
         load_halo_tile<3, VEC>(sM, src, x0, y0, H, W, tid);
     }
     __syncthreads();
-    if (PERSISTENT)
-    {
-        walk.j += walk.stride;
-        have = walk.valid(walk.j);
-        if (have)
-        {
-            walk.decode(walk.j, tx, ty, tz);
-            const size_t pl = (size_t)tz * H * W;
-            const float *const srcn[3] = {d_mu + pl, d_s1 + pl, d_s12 + pl};
-            if (VEC) prefetch_issue<3>((float4(&)[3][NPRE])pre, srcn, tx * TW, ty * TH, H, W, tid);
-        }
-    }
     if (tid < IH * (TW / 4))
     {
         const int r = tid >> 3, c0 = 4 * (tid & 7);
@@ -389,8 +295,6 @@ __global__ void __launch_bounds__(256) ssim_l1_bwd_kernel(const float *__restric
             }
         }
     }
-    if (PERSISTENT) __syncthreads(); // this tile's last reads of hb / sM before the next tile's commit
-    } while (PERSISTENT && have);
 }
 
 struct Carve
@@ -440,8 +344,7 @@ hipError_t ts_loss_forward(const float *image, const float *gt, int C, int H, in
     if (!gauss_matches_constants()) return hipErrorAssert;
     const Carve c = carve(workspace, C, H, W);
     const int gx = (W + TW - 1) / TW, gy = (H + TH - 1) / TH;
-    const int per = (gx * gy * C + 7) / 8;
-    const dim3 grid((unsigned)(8 * (per < TS_SSIM_WG_PER_XCD ? per : TS_SSIM_WG_PER_XCD))); // persistent workgroups, XCD-aware (TileWalk)
+    const dim3 grid((unsigned)(8 * ((gx * gy * C + 7) / 8))); // one workgroup per tile, padded to a multiple of 8 (tile_of_workgroup)
     const bool vec = (W % 4 == 0) && (((size_t)image | (size_t)gt) & 15) == 0; // planes then start on 16-byte boundaries too (H * W * 4 bytes each)
 #define TS_SSIM_FWD(G, V) hipLaunchKernelGGL((ssim_l1_fwd_kernel<G, V>), grid, dim3(256), 0, s, image, gt, H, W, c.d_mu, c.d_s1, c.d_s12, c.partial, gx, gy, C)
     if (need_grad) { if (vec) TS_SSIM_FWD(true, true); else TS_SSIM_FWD(true, false); }
@@ -456,8 +359,7 @@ hipError_t ts_loss_backward(const float *image, const float *gt, int C, int H, i
 {
     const Carve c = carve(const_cast<void *>(workspace), C, H, W);
     const int gx = (W + TW - 1) / TW, gy = (H + TH - 1) / TH;
-    const int per = (gx * gy * C + 7) / 8;
-    const dim3 grid((unsigned)(8 * (per < TS_SSIM_WG_PER_XCD ? per : TS_SSIM_WG_PER_XCD)));
+    const dim3 grid((unsigned)(8 * ((gx * gy * C + 7) / 8)));
     const double inv_n = 1.0 / ((double)C * H * W);
     // d(1 - mean(map)) = -1/N per map element; d mean|I - G| = sign / N
     const bool vec = (W % 4 == 0) && (((size_t)c.d_mu | (size_t)c.d_s1 | (size_t)c.d_s12) & 15) == 0;

@@ -23,7 +23,7 @@
 #include "ts2d_group.h"
 #include "ts2d_support.h"
 
-#ifndef TS3G_BWD_WAVES // resident waves per SIMD the backward's register budget is declared for (occupancy experiments: tools/build_variant.sh)
+#ifndef TS3G_BWD_WAVES // resident waves per SIMD the backward's register budget is declared for (occupancy experiments: build.py --variant TAG --unit render3d_group=-DTS3G_BWD_WAVES=n)
 #define TS3G_BWD_WAVES 6 // round 5: 80 registers with 3-4 spilled dwords outside the step loop; 1.128 vs 1.141 ms at the headline, 0.142 vs 0.148 at 93 k (profiles/r05_emission_variants.txt)
 #endif
 namespace
@@ -94,9 +94,6 @@ __device__ __forceinline__ Cull3 cull3(V3 v1, V3 v2, V3 v3, V3 n, float op, floa
             const float h3 = s * (f3c + f3x * bx + f3y * by) + fmaxf(0.0f, 3.0f * s * f3x) + fmaxf(0.0f, 3.0f * s * f3y);
             ov = ov && h1 >= -slack && h2 >= -slack && h3 >= -slack;
         }
-#ifdef TS3G_NO_CULL
-        ov = true;
-#endif
         c.ov[g] = ov;
     }
     return c;

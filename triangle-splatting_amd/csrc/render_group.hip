@@ -33,7 +33,7 @@
 #include "ts2d_group.h"
 #include "ts2d_support.h"
 
-#ifndef TSG_FWD_WAVES // resident waves per SIMD the register budget is declared for (occupancy experiments: tools/build_variant.sh ... -DTSG_BWD_WAVES=8)
+#ifndef TSG_FWD_WAVES // resident waves per SIMD the register budget is declared for (occupancy experiments: build.py --variant TAG --unit render_group_bwd=-DTSG_BWD_WAVES=8)
 #define TSG_FWD_WAVES 7
 #endif
 #ifndef TSG_BWD_WAVES
@@ -50,15 +50,6 @@
 #endif
 #ifndef TSG_PART // which kernels this translation unit holds: 1 = forward, 2 = backward, 3 = both.  build.py compiles the file twice, so that each
 #define TSG_PART 3 // kernel gets its own scheduler strategy (round 6: max-ilp is +1.3 % for the forward and -1 % for the backward, profiles/r05_notes.md)
-#endif
-#ifndef TSG_CARRY // 1: a batch with more than NR surviving entries hands the ones beyond the table to the NEXT batch instead of taking a second pass
-#define TSG_CARRY 0 // ("carried-over table", DESIGN 14 / VERDICT r5 item 3 (i): group_sim -26 % passes.  Built and measured in round 6, parity-green:
-#endif              // render_fwd 0.382 -> 0.403 ms, render_bwd 0.792 -> 0.806 -- the carried entries take slots of the next batch, i.e. MORE batches, each
-                    // with its full cull and list build, where a second pass had neither; profiles/r06_blend_ab.txt)
-#ifndef TSG_PROBE
-#define TSG_PROBE 0 // profiling builds: 1 = no contribution atomics, 2 = no contribution statistics at all, 3 = no serialised accumulate,
-                    // 4 = backward without its step loop (what the per-batch work alone costs), 6 = backward without the row flush,
-                    // 7 = backward whose row flush is a plain store instead of an atomic add -- results wrong
 #endif
 namespace
 {
@@ -202,10 +193,6 @@ __global__ void __launch_bounds__(256, TSG_FWD_WAVES) render_fwd_group_kernel(Re
     constexpr int TCAP = TSG_TCAP; // 960: 960 x 12 bytes + the tables = 23.1 KB per workgroup: seven workgroups per CU (1024 entries would leave six)
     __shared__ unsigned long long tsum[RICH ? TCAP : 1]; // 16.48 fixed point
     __shared__ int tmax[RICH ? TCAP : 1];
-#ifdef TSG_PAD_LDS // occupancy experiment: extra LDS bytes per workgroup
-    __shared__ int pad_lds[TSG_PAD_LDS / 4];
-    if (a.W < 0) pad_lds[threadIdx.x] = 1, atomicAdd(&tmax[0], pad_lds[255 - threadIdx.x]);
-#endif
 
     const int tile = tile_of_block(blockIdx.x, a.grid_x, a.grid_y);
     if (tile < 0) return; // the grid is padded (ts2d_wave.h)
@@ -242,13 +229,12 @@ __global__ void __launch_bounds__(256, TSG_FWD_WAVES) render_fwd_group_kernel(Re
 #endif
     // dense batches: only the entries whose quadrant bit is set are gathered and culled (ts2d_group.h, stream_refill); `pos` = list position
     uint32_t id = 0;
-    int pos = 0, cursor = 0, carried = 0; // carried: entries of the previous batch that did not fit its table (lanes [0, carried) of id / pos)
+    int pos = 0, cursor = 0;
     for (;;)
     {
         const unsigned long long alive = ballot(!done);
         if (alive == 0) break;
-        int nq = TSG_CARRY ? carried : 0;
-        carried = 0;
+        int nq = 0;
         stream_refill<false, TSG_FWD_CAP>(id, pos, nq, point_list + range.x, cursor, len, TS_ID_BITS + wave, lane);
         if (nq == 0) break;
         const bool valid = lane < nq;
@@ -279,7 +265,7 @@ __global__ void __launch_bounds__(256, TSG_FWD_WAVES) render_fwd_group_kernel(Re
         const int r = rank & (NR - 1);
         bool mine = anybit && rank < NR;
         if (mine) publish_row(cst + r * ROW, s, id, ent, r1, r2, r3);
-        for ([[maybe_unused]] int h = 0;;)
+        for (int h = 0;;)
         {
             const unsigned long long mm = nact <= NR ? any : ballot(mine);
             list[lane] = dummy | (dummy << 16); // four lists x NR entries: the dummy row
@@ -356,7 +342,6 @@ __global__ void __launch_bounds__(256, TSG_FWD_WAVES) render_fwd_group_kernel(Re
                         done = done || sat;
                     }
                 }
-#if TSG_PROBE != 2
                 if (RICH)
                 {
                     // contrib_sum / contrib_max (forward.cu:323-324; the reference issues two global atomics per (pixel, triangle)):
@@ -372,18 +357,12 @@ __global__ void __launch_bounds__(256, TSG_FWD_WAVES) render_fwd_group_kernel(Re
                     if ((lane & 1) == 0 && sm > 0.0f) k = __float_as_int(*(const float *)(lds0 + mylist[t0 + stat_step] + 18 * 4));
                     if ((lane & 1) == 0 && sm > 0.0f) tile_stats_add<TCAP>(tsum, tmax, k, sm, mx, point_list + range.x, contrib_sum, contrib_max);
                 }
-#endif
             }
-#if TSG_CARRY
-            // more survivors than table rows: the ones beyond the table open the NEXT batch (one more gather + cull of a few lanes that the batch
-            // runs anyway) instead of a second pass of their own with its list build and its short lockstep loop -- group_sim: -26 % passes
-            if (nact > NR) carried = carry_over(id, pos, anybit && rank >= NR, lane);
-            break;
-#else
+            // more survivors than table rows: a second pass (handing them to the next batch instead was measured and dropped, a loss:
+            // profiles/r06_blend_ab.txt)
             if (++h * NR >= nact) break;
             mine = anybit && rank >= NR;
             if (mine) republish_row<RICH>(cst + r * ROW, point_list, rec, range.x + pos, ent, OX, OY);
-#endif
         }
     }
 
@@ -427,7 +406,7 @@ __global__ void __launch_bounds__(256, TSG_FWD_WAVES) render_fwd_group_kernel(Re
             if (k < nflush)
             {
                 const unsigned long long fx48 = tsum[k];
-                if (TSG_PROBE != 5 && fx48 != 0ull) tile_stats_flush(fx48, tmax[k], TSG_PROBE == 9 ? ((range.x + (uint32_t)k) & 0x3FFFFu) : ids[j], contrib_sum, contrib_max);
+                if (fx48 != 0ull) tile_stats_flush(fx48, tmax[k], ids[j], contrib_sum, contrib_max);
             }
         }
     }
@@ -462,10 +441,6 @@ __global__ void __launch_bounds__(64 * WPB, TSG_BWD_WAVES) render_bwd_group_kern
 {
     __shared__ __attribute__((aligned(16))) float rows_all[WPB][(NR + 1) * BROW]; // constants + gradient sums; row -1 absorbs the adds of idle groups
     __shared__ __attribute__((aligned(16))) uint32_t list_all[WPB][4 * NR / 2];   // per group: NR entries (u16 byte offsets of rows)
-#ifdef TSG_PAD_LDS
-    __shared__ int pad_lds_b[TSG_PAD_LDS / 4];
-    if (a.W < 0) pad_lds_b[threadIdx.x] = 1, list_all[0][0] = (signed char)pad_lds_b[255 - threadIdx.x];
-#endif
 
     int tile, quad, wave; // quad = which 8x8 quadrant of the tile, wave = index into this workgroup's LDS arrays
     if (WPB == 4)
@@ -543,11 +518,10 @@ __global__ void __launch_bounds__(64 * WPB, TSG_BWD_WAVES) render_bwd_group_kern
 
     // dense batches, walked back to front: lane 0 holds the entry farthest back (ts2d_group.h, stream_refill<true>); `pos` = list position
     uint32_t id = 0;
-    int pos = 0, cursor = maxlast, carried = 0;
+    int pos = 0, cursor = maxlast;
     for (;;)
     {
-        int nq = TSG_CARRY ? carried : 0;
-        carried = 0;
+        int nq = 0;
         stream_refill<true, TSG_BWD_CAP>(id, pos, nq, point_list + range.x, cursor, maxlast, TS_ID_BITS + quad, lane);
         if (nq == 0) break;
         const bool valid = lane < nq;
@@ -571,7 +545,7 @@ __global__ void __launch_bounds__(64 * WPB, TSG_BWD_WAVES) render_bwd_group_kern
         const int r = rank & (NR - 1);
         bool mine = anybit && rank < NR;
         if (mine) publish_row(rows + r * BROW, s, id, ent, r1, r2, r3);
-        for ([[maybe_unused]] int h = (nact - 1) / NR;;)
+        for (int h = (nact - 1) / NR;;)
         {
             const unsigned long long mm = nact <= NR ? any : ballot(mine);
             if (mine)
@@ -590,7 +564,6 @@ __global__ void __launch_bounds__(64 * WPB, TSG_BWD_WAVES) render_bwd_group_kern
                 steps = max(steps, n);
             }
             const u16a *mylist = (const u16a *)list + grp * NR;
-            if (TSG_PROBE == 4) steps = 0;
 
             // steps at which two groups work on the SAME entry (their sums must then be added to its row one after the other)
             unsigned long long conflict;
@@ -608,7 +581,7 @@ __global__ void __launch_bounds__(64 * WPB, TSG_BWD_WAVES) render_bwd_group_kern
                     ra_next = mylist[min(t0 + 1, NR - 1)]; // fetched one step ahead: one LDS round trip less on the step's critical path
                     const float *row = (const float *)(lds0 + ra);
                     float *acc = (float *)(lds0 + ra + accoff);
-                    const bool shared_row = TSG_PROBE == 3 ? false : (bool)((conflict >> t0) & 1); // wave-uniform
+                    const bool shared_row = (conflict >> t0) & 1; // wave-uniform
                     const float q0acc = *acc;                              // fetched early; only used when no other group adds to this row now
                     const float4 q0 = *(const float4 *)(row), q1 = *(const float4 *)(row + 4);
                     const Bary b = barycentrics(q0, q1, fx, fy);
@@ -698,24 +671,13 @@ __global__ void __launch_bounds__(64 * WPB, TSG_BWD_WAVES) render_bwd_group_kern
                         const uint32_t eid = __float_as_uint(rows[e * BROW + 17]);
                         float val = rows[e * BROW + ROW + sub];
                         if (rcol < 6) val *= rows[e * BROW + 6];
-#if TSG_PROBE == 6
-                        if (a.W < 0) grad_rec[eid] = val; // never taken: keeps `val` alive
-#elif TSG_PROBE == 7
-                        if (RICH || rcol < 10) grad_rec[TS_GRAD_FLOATS * (size_t)eid + rcol] = val;
-#else
                         if (RICH || rcol < 10) unsafeAtomicAdd(grad_rec + TS_GRAD_FLOATS * (size_t)eid + rcol, val);
-#endif
                     }
                 }
             }
-#if TSG_CARRY
-            if (nact > NR) carried = carry_over(id, pos, anybit && rank >= NR, lane); // see the forward
-            break;
-#else
             if (--h < 0) break;
             mine = anybit && rank >= NR;
             if (mine) republish_row<RICH>(rows + r * BROW, point_list, rec, range.x + pos, ent, OX, OY);
-#endif
         }
     }
 }

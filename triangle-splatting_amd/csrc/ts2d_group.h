@@ -60,18 +60,6 @@ __device__ __forceinline__ void stream_refill(uint32_t &id, int &pos, int &n, co
     }
 }
 
-// The entries of a batch flagged `keep` move to lanes [0, n) of (id, pos), in lane order (= processing order); returns n.  One ballot, one
-// permutation of the 64 lanes -- the same move as stream_refill's.  The next stream_refill appends behind them.
-__device__ __forceinline__ int carry_over(uint32_t &id, int &pos, bool keep, int lane)
-{
-    const unsigned long long mk = ballot(keep);
-    const int cnt = __popcll(mk), rk = lane_rank(mk);
-    const int dest = keep ? rk : cnt + (lane - rk); // kept lanes to the front, the others behind them: a permutation
-    id = (uint32_t)__builtin_amdgcn_ds_permute(dest << 2, (int)id);
-    pos = __builtin_amdgcn_ds_permute(dest << 2, pos);
-    return cnt;
-}
-
 // ---- 16-lane (DPP row) transpose-reduce: N values per lane -> each lane keeps the row-wide reduction of ONE value ----
 // Sum AND maximum of 8 values over the 16 lanes of each DPP row in one pass (the forward's contribution statistics): an 8-value
 // transpose-reduce (level 1 pairs lanes l, l ^ 8 via row_ror:8, level 2 lanes inside a group of 8 via row_half_mirror, level 3 l, l ^ 2, then
@@ -225,13 +213,6 @@ __device__ __forceinline__ void tile_stats_add(unsigned long long *tsum, int *tm
 }
 __device__ __forceinline__ void tile_stats_flush(unsigned long long fx48, int mxbits, uint32_t tid, float *contrib_sum, float *contrib_max)
 {
-#if defined(TSG_PROBE) && TSG_PROBE == 8 // profiling build (results wrong): plain scattered stores in place of the two atomics -- what the ATOMIC costs
-    contrib_sum[tid] = (float)((double)fx48 * 0x1p-48);
-    contrib_max[tid] = __int_as_float(mxbits);
-#elif defined(TSG_PROBE) && TSG_PROBE == 9 // profiling build (results wrong): ONE coalesced 8-byte store per instance at its list position
-    ((float2 *)contrib_sum)[tid] = make_float2((float)((double)fx48 * 0x1p-48), __int_as_float(mxbits));
-#else
     global_stats_add(tid, (float)((double)fx48 * 0x1p-48), __int_as_float(mxbits), contrib_sum, contrib_max);
-#endif
 }
 } // namespace

@@ -12,9 +12,6 @@
 #include "ts2d_math.h"
 #include "ts2d_sh.h"
 
-#ifndef TS_PRE_OUT_REGS
-#define TS_PRE_OUT_REGS 0
-#endif
 namespace ts
 {
 // What a launch of the per-triangle forward computes (api.hip: forward_bin_impl).  The ordering chain -- depth sort, scan, emission, tile sort --
@@ -118,12 +115,12 @@ __global__ void __launch_bounds__(64) preprocess_bwd_staged_kernel(PreprocessArg
                                                                     float *__restrict__ dL_dopacity)
 {
     __shared__ float s_v[64 * 9];
-    constexpr bool OUT_REGS = SH_REGS && TS_PRE_OUT_REGS; // gradient rows leave from registers (strided dwordx4 stores) or through LDS (coalesced)
-    __shared__ float s_sh[(SHROW > 0 && (!SH_REGS || (WRITE_SH && !OUT_REGS))) ? 64 * (SHROW + 1) : 1];
+    __shared__ float s_sh[(SHROW > 0 && (!SH_REGS || WRITE_SH)) ? 64 * (SHROW + 1) : 1];
     const int lane = threadIdx.x, row0 = blockIdx.x * 64, idx = row0 + lane;
-    // SH_REGS (rows of whole 16-byte pieces): the coefficient row comes straight into registers and the gradient row leaves from
-    // registers, SHROW / 4 dwordx4 each -- see preprocess_fwd_staged_kernel
-    float shr[(SHROW > 0 && SH_REGS && SH_IN) ? SHROW : 4], osr[(SHROW > 0 && OUT_REGS && WRITE_SH) ? SHROW : 4];
+    // SH_REGS (rows of whole 16-byte pieces): the coefficient row comes straight into registers, SHROW / 4 dwordx4 -- see
+    // preprocess_fwd_staged_kernel.  The gradient row leaves through LDS (coalesced); strided stores from registers were measured, gained
+    // nothing and were dropped (profiles/r06_preprocess_bwd_reads.txt).
+    float shr[(SHROW > 0 && SH_REGS && SH_IN) ? SHROW : 4];
     if (SHROW > 0 && SH_REGS && SH_IN && idx < a.P)
     {
         const float4 *rowp = (const float4 *)(a.shs + (size_t)idx * SHROW);
@@ -137,29 +134,12 @@ __global__ void __launch_bounds__(64) preprocess_bwd_staged_kernel(PreprocessArg
     {
         const float *vp = s_v + lane * 9;
         const float *shp = (SHROW > 0 && SH_IN) ? (SH_REGS ? shr : s_sh + lane * (SHROW + 1)) : (a.use_shs ? a.shs + (size_t)idx * a.M * 3 : nullptr);
-        if (SHROW > 0 && OUT_REGS && WRITE_SH)
-        {
-            // the gradient row is expanded here, from the clamp-masked colour gradient the per-triangle function hands back: the
-            // row then never has its address taken inside that function and stays in registers.  The vertex row is consumed
-            // first (dL_dvertex overwrites it in place).
-            const f3 center = divf(add(add(f3{vp[0], vp[1], vp[2]}, f3{vp[3], vp[4], vp[5]}), f3{vp[6], vp[7], vp[8]}), 3.0f);
-            const f3 masked = Body::bwd(a, radii, g, grad_rec, idx, vp, shp, s_v + lane * 9, (float *)nullptr, dL_dcenter2D, dL_dfeature, dL_dopacity);
-#pragma unroll
-            for (int k = 0; k < SHROW; k++) osr[k] = 0.0f;
-            if (radii[idx] > 0) sh_grad_store(a.D, a.M, center, f3{a.campos[0], a.campos[1], a.campos[2]}, masked, osr);
-            float4 *rowo = (float4 *)(dL_dshs + (size_t)idx * SHROW);
-#pragma unroll
-            for (int c = 0; c < SHROW / 4; c++) rowo[c] = *(const float4 *)(osr + 4 * c);
-        }
-        else
-        {
-            float *row = (SHROW > 0 && !OUT_REGS) ? s_sh + lane * (SHROW + 1) : nullptr;
-            Body::bwd(a, radii, g, grad_rec, idx, vp, shp, s_v + lane * 9, WRITE_SH ? row : nullptr, dL_dcenter2D, dL_dfeature, dL_dopacity);
-        }
+        float *row = SHROW > 0 ? s_sh + lane * (SHROW + 1) : nullptr;
+        Body::bwd(a, radii, g, grad_rec, idx, vp, shp, s_v + lane * 9, WRITE_SH ? row : nullptr, dL_dcenter2D, dL_dfeature, dL_dopacity);
     }
     __syncthreads();
     stage_rows_out<9, 9>(s_v, dL_dvertex, row0, a.P, lane);
-    if (SHROW > 0 && WRITE_SH && !OUT_REGS) stage_rows_out<SHROW, SHROW + 1>(s_sh, dL_dshs, row0, a.P, lane);
+    if (SHROW > 0 && WRITE_SH) stage_rows_out<SHROW, SHROW + 1>(s_sh, dL_dshs, row0, a.P, lane);
 }
 
 // Staging policy: vertex rows whenever the pointers are 16-byte aligned; SH rows in when at least half of each row is

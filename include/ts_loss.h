@@ -8,7 +8,9 @@
  * and their autograd backward (ten eager torch kernels forward, more backward) with two HIP kernels each way.
  * Exported by the same libts2d.so as include/ts2d.h.  All pointers are device pointers; images are planar float32
  * (C, H, W) -- a leading batch dimension folds into C, exactly as the reference's depthwise conv + global mean does.
- * Every call enqueues on `stream` and returns TS2D_OK (0) or an error code of ts2d.h with ts2d_last_error() set. */
+ * Every call enqueues on `stream` and returns TS2D_OK (0) or an error code of ts2d.h with ts2d_last_error() set.
+ * Further sections: the depth / normal loss, the auxiliary image losses, the down-sampler, and the trainer's regularisers with the per-view
+ * colour affine (tsl_reg_*, tsl_color_affine_*; the regularisation half of VanillaTS_trainer.py:86-116). */
 #ifndef TS_LOSS_H
 #define TS_LOSS_H
 
@@ -101,6 +103,45 @@ int tsl_downsample_forward_planes(int32_t num_planes, const float *const *in_pla
                                   int32_t out_width, float *const *out_planes, void *stream);
 int tsl_downsample_backward_planes(int32_t num_planes, const float *const *grad_out_planes, int32_t in_height, int32_t in_width, int32_t out_height,
                                    int32_t out_width, float *const *grad_in_planes, void *stream);
+
+/* ---- the trainer's regularisers and the per-view colour affine (csrc/regularizers.hip) ------------------------------------------------------
+ * The regularisation half of VanillaTSTrainer._get_loss (src/diff_recon/trainers/VanillaTS_trainer.py:86-116) on P triangles:
+ *     scaling_reg = sum_i s_i / P                 s_i = mean side length of triangle i (get_scaling, VanillaTS_model.py:72-76)
+ *     opacity_reg = sum_i (0.25 - (o_i - 0.5)^2) / P  (QUAD)  or  sum_i (1 - o_i) / P  (LINEAR)      (:89-97; o = post-sigmoid opacity)
+ *     vertex_reg  = sum_k |p_k - p_nearest[k]|^2 / 3P   over the 3P vertices (nearest_dist2(...).mean(), trainer_utils.py:339-346)
+ * vertex (P, 3, 3) and opacity (P, 1) float32; nearest (3P,) uint32 = nearestNeighbor(vertex.view(-1, 3), 3) (include/ts_knn.h).  A term whose
+ * weight is 0 (the opacity term also in mode NONE) is neither computed nor read: opacity may be NULL then, and nearest / prepared when
+ * w_vertex == 0.  Sums are deterministic two-stage sums in double over a fixed grid; a NaN input makes the loss NaN as torch's mean does. */
+#define TSL_REG_OPACITY_NONE 0
+#define TSL_REG_OPACITY_QUAD 1
+#define TSL_REG_OPACITY_LINEAR 2
+/* Bytes of device scratch of tsl_reg_forward and tsl_color_affine_backward (per-block partial sums; independent of the sizes). */
+size_t tsl_reg_workspace_bytes(void);
+/* The inverse of the nearest relation, for the vertex term's backward: for each vertex j the vertices k with nearest[k] = j, in ascending order
+ * (stable radix sort on (nearest[k], k) + run offsets; in-degree unbounded).  Build it once per refresh of `nearest`; `prepared` must then
+ * stay untouched while backward calls read it.  nearest values outside [0, 3P) join no list (their own term is NaN). */
+size_t tsl_reg_prepared_bytes(int32_t P);
+int tsl_reg_prepare(int32_t P, const uint32_t *nearest, void *prepared, size_t prepared_bytes, void *stream);
+/* out[0] = w_scaling scaling_reg + w_opacity opacity_reg + w_vertex vertex_reg, out[1..3] = scaling_reg, opacity_reg, vertex_reg (0 for a term
+ * that is off): four floats in device memory, no host read (graph-capturable). */
+int tsl_reg_forward(int32_t P, const float *vertex, const float *opacity, const uint32_t *nearest, float w_scaling, float w_opacity,
+                    int32_t opacity_mode, float w_vertex, void *workspace, size_t workspace_bytes, float *out, void *stream);
+/* Backward of out[0]: dL_dvertex (P, 3, 3) and dL_dopacity (P, 1) fully written, one gather-form pass, no atomics (run-to-run identical).
+ * `grad_out`: device scalar or NULL for 1.  `prepared`: tsl_reg_prepare's buffer for this `nearest` (read only when w_vertex != 0). */
+int tsl_reg_backward(int32_t P, const float *vertex, const float *opacity, const uint32_t *nearest, const void *prepared, size_t prepared_bytes,
+                     float w_scaling, float w_opacity, int32_t opacity_mode, float w_vertex, const float *grad_out, float *dL_dvertex,
+                     float *dL_dopacity, void *stream);
+/* Per-view colour affine of VanillaTSModel.forward (VanillaTS_model.py:678-684) on a planar (3, H, W) image:
+ *     out_c = clamp(sum_k image_k W[k][c] + b_c, 0, 1)        (image.permute(1, 2, 0) @ W[uid] + b[uid]; NaN stays NaN)
+ * weight: the view's 3 x 3 row-major block of the (V, 3, 3) parameter, bias: its 3 floats (device pointers).  Backward: the pre-clamp value is
+ * recomputed; the gradient passes where 0 <= pre <= 1 (torch's clamp backward, bounds included).  dL_dimage (3, H, W) fully written;
+ * dL_dweight (9 floats) and dL_dbias (3 floats) written from deterministic two-stage sums over the pixels (the caller hands in the view's rows
+ * of zeroed (V, 3, 3) / (V, 3) gradients).  `grad_out`: the (3, H, W) gradient of the output. */
+int tsl_color_affine_forward(const float *image, int32_t height, int32_t width, const float *weight, const float *bias, float *out, void *stream);
+int tsl_color_affine_backward(const float *image, int32_t height, int32_t width, const float *weight, const float *bias, const float *grad_out,
+                              void *workspace, size_t workspace_bytes, float *dL_dimage, float *dL_dweight, float *dL_dbias, void *stream);
+/* affine_reg = L1(image, image_original) masked by gt_mask (VanillaTS_trainer.py:98-105) needs no entry point of its own: it is
+ * tsl_masked_l1_forward / _backward with the mask plane (all ones without a mask), dL/d image_original = -dL/d image. */
 
 #ifdef __cplusplus
 }

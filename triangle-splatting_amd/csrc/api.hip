@@ -984,6 +984,83 @@ int tsl_scharr_smoothness_backward(const float *image, const float *mask, int32_
     return TS2D_OK;
 }
 
+// ---- the trainer's regularisers + per-view colour affine (regularizers.hip) ------------------------------------------------------
+size_t tsl_reg_workspace_bytes(void) { return ts_reg_workspace_bytes(); }
+size_t tsl_reg_prepared_bytes(int32_t P) { return ts_reg_prepared_bytes(P); }
+static int reg_args_ok(int32_t P, int32_t mode)
+{
+    if (P < 0 || P > (1 << TS_ID_BITS)) return fail(TS2D_ERR_INVALID, "P must be in 0..2^28");
+    if (mode != TSL_REG_OPACITY_NONE && mode != TSL_REG_OPACITY_QUAD && mode != TSL_REG_OPACITY_LINEAR)
+        return fail(TS2D_ERR_INVALID, "opacity_mode must be TSL_REG_OPACITY_NONE, _QUAD or _LINEAR");
+    return TS2D_OK;
+}
+int tsl_reg_prepare(int32_t P, const uint32_t *nearest, void *prepared, size_t prepared_bytes, void *stream)
+{
+    if (int rc = reg_args_ok(P, TSL_REG_OPACITY_NONE)) return rc;
+    if (P == 0) return TS2D_OK;
+    if (!nearest) return fail(TS2D_ERR_INVALID, "null pointer");
+    if (!prepared || prepared_bytes < ts_reg_prepared_bytes(P)) return fail(TS2D_ERR_CAPACITY, "prepared buffer too small");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps("reg_prepare", s);
+    TS_HIP(ts_reg_prepare(P, nearest, prepared, s));
+    return TS2D_OK;
+}
+int tsl_reg_forward(int32_t P, const float *vertex, const float *opacity, const uint32_t *nearest, float w_scaling, float w_opacity,
+                    int32_t opacity_mode, float w_vertex, void *workspace, size_t workspace_bytes, float *out, void *stream)
+{
+    if (int rc = reg_args_ok(P, opacity_mode)) return rc;
+    if (!out || (P > 0 && (w_scaling != 0.0f || w_vertex != 0.0f) && !vertex)) return fail(TS2D_ERR_INVALID, "null pointer");
+    if (P > 0 && w_opacity != 0.0f && opacity_mode != TSL_REG_OPACITY_NONE && !opacity) return fail(TS2D_ERR_INVALID, "null opacity");
+    if (P > 0 && w_vertex != 0.0f && !nearest) return fail(TS2D_ERR_INVALID, "w_vertex != 0 needs the nearest indices");
+    if (!workspace || workspace_bytes < ts_reg_workspace_bytes()) return fail(TS2D_ERR_CAPACITY, "workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps("reg_fwd", s);
+    TS_HIP(ts_reg_forward(P, vertex, opacity, nearest, w_scaling, w_opacity, opacity_mode, w_vertex, workspace, out, s));
+    return TS2D_OK;
+}
+int tsl_reg_backward(int32_t P, const float *vertex, const float *opacity, const uint32_t *nearest, const void *prepared, size_t prepared_bytes,
+                     float w_scaling, float w_opacity, int32_t opacity_mode, float w_vertex, const float *grad_out, float *dL_dvertex,
+                     float *dL_dopacity, void *stream)
+{
+    if (int rc = reg_args_ok(P, opacity_mode)) return rc;
+    if (P == 0) return TS2D_OK;
+    if (!vertex || !dL_dvertex || !dL_dopacity) return fail(TS2D_ERR_INVALID, "null pointer");
+    if (w_opacity != 0.0f && opacity_mode != TSL_REG_OPACITY_NONE && !opacity) return fail(TS2D_ERR_INVALID, "null opacity");
+    if (w_vertex != 0.0f && !nearest) return fail(TS2D_ERR_INVALID, "w_vertex != 0 needs the nearest indices");
+    if (w_vertex != 0.0f && (!prepared || prepared_bytes < ts_reg_prepared_bytes(P)))
+        return fail(TS2D_ERR_CAPACITY, "w_vertex != 0 needs the buffer tsl_reg_prepare filled for these P");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps("reg_bwd", s);
+    TS_HIP(ts_reg_backward(P, vertex, opacity, nearest, prepared, w_scaling, w_opacity, opacity_mode, w_vertex, grad_out, dL_dvertex, dL_dopacity, s));
+    return TS2D_OK;
+}
+static int affine_args_ok(int32_t H, int32_t W)
+{
+    if (H <= 0 || W <= 0) return fail(TS2D_ERR_INVALID, "height and width must be positive");
+    if ((int64_t)H * W > ((int64_t)1 << 28)) return fail(TS2D_ERR_INVALID, "image too large");
+    return TS2D_OK;
+}
+int tsl_color_affine_forward(const float *image, int32_t H, int32_t W, const float *weight, const float *bias, float *out, void *stream)
+{
+    if (int rc = affine_args_ok(H, W)) return rc;
+    if (!image || !weight || !bias || !out) return fail(TS2D_ERR_INVALID, "null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps("color_affine_fwd", s);
+    TS_HIP(ts_color_affine_forward(image, H, W, weight, bias, out, s));
+    return TS2D_OK;
+}
+int tsl_color_affine_backward(const float *image, int32_t H, int32_t W, const float *weight, const float *bias, const float *grad_out, void *workspace,
+                              size_t workspace_bytes, float *dL_dimage, float *dL_dweight, float *dL_dbias, void *stream)
+{
+    if (int rc = affine_args_ok(H, W)) return rc;
+    if (!image || !weight || !bias || !grad_out || !dL_dimage || !dL_dweight || !dL_dbias) return fail(TS2D_ERR_INVALID, "null pointer");
+    if (!workspace || workspace_bytes < ts_reg_workspace_bytes()) return fail(TS2D_ERR_CAPACITY, "workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps("color_affine_bwd", s);
+    TS_HIP(ts_color_affine_backward(image, H, W, weight, bias, grad_out, workspace, dL_dimage, dL_dweight, dL_dbias, s));
+    return TS2D_OK;
+}
+
 // ---- include/ts_knn.h -------------------------------------------------------------------------------------------------
 size_t tsk_workspace_bytes(int32_t P) { return ts_knn_workspace_bytes(P); }
 

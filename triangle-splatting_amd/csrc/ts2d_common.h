@@ -339,6 +339,18 @@ hipError_t ts_depth_normal_forward(const float *depth, const float *normal, int 
 hipError_t ts_depth_normal_backward(const float *depth, const float *normal, int H, int W, float tan_fovx, float tan_fovy, double scale,
                                     const void *workspace, const float *grad_out, float *dL_ddepth, float *dL_dnormal, hipStream_t s);
 
+// ---- the trainer's regularisers + per-view colour affine (regularizers.hip, include/ts_loss.h) ------------------------------------
+size_t ts_reg_workspace_bytes();
+size_t ts_reg_prepared_bytes(int P);
+hipError_t ts_reg_prepare(int P, const uint32_t *nearest, void *prepared, hipStream_t s);
+hipError_t ts_reg_forward(int P, const float *vertex, const float *opacity, const uint32_t *nearest, float w_s, float w_o, int omode, float w_v,
+                          void *workspace, float *out, hipStream_t s);
+hipError_t ts_reg_backward(int P, const float *vertex, const float *opacity, const uint32_t *nearest, const void *prepared, float w_s, float w_o,
+                           int omode, float w_v, const float *grad_out, float *dvertex, float *dopacity, hipStream_t s);
+hipError_t ts_color_affine_forward(const float *x, int H, int W, const float *Wm, const float *b, float *y, hipStream_t s);
+hipError_t ts_color_affine_backward(const float *x, int H, int W, const float *Wm, const float *b, const float *gy, void *workspace, float *gx,
+                                    float *dW, float *db, hipStream_t s);
+
 // ---- exact nearest-neighbour helpers (knn.hip, include/ts_knn.h) -------------------------------------------------------
 size_t ts_knn_workspace_bytes(int P);
 hipError_t ts_knn_mean_dist3(int P, const float *points, float *mean_dist2, void *ws, hipStream_t s);

@@ -20,6 +20,10 @@
                           (reference: src/diff_recon/models/VanillaTS_model.py:585-694)
     model_init.py         create_from_pcd (point cloud -> distCUDA2 -> equilateral triangles, back-face twins), grid / random / direct sampling
                           (reference: src/diff_recon/models/VanillaTS_model.py:761-804, 830-917; model_utils.py:34-57, 95-149)
+    regularizers.py       triangle_regularization (scaling / opacity / vertex regularisers fused, one pass each way), prepare_nearest, TrainerRegularizers
+                          (the regularisation schedule of _get_loss with affine_reg), ColorAffine (the per-view colour affine and its optimizer groups)
+                          (reference: src/diff_recon/trainers/VanillaTS_trainer.py:86-116, trainer_utils.py:339-346,
+                           src/diff_recon/models/VanillaTS_model.py:72-76, 86-94, 118-121, 146-152, 678-684)
     graphed.py            GraphedStep: a whole training step (sync-free forward, loss, backward, optimizer) captured once into a HIP graph and
                           replayed with one launch -- no counterpart in the reference, whose forward reads num_rendered back every step
 
@@ -34,4 +38,5 @@ from . import schedulers  # noqa: F401
 from .raw_triangle import RawTriangle  # noqa: F401
 from .optim import FusedAdam, ShardedAdam, ShFactors  # noqa: F401
 from .graphed import GraphedStep  # noqa: F401
+from .regularizers import triangle_regularization, prepare_nearest, PreparedNearest, TrainerRegularizers, ColorAffine, AffineReg, affine_reg  # noqa: F401
 from .model_init import create_from_pcd, grid_sampling, grid_size_search, get_inside_mask, inter_point_distance, sample_points  # noqa: F401

@@ -9,7 +9,8 @@ scope) and performs, in the reference's order:
   * bg_depth = max |camera_center - vertex| (:623; `background_depth`: one kernel, stays a 0-dim device tensor that the rasterizer
     package converts);
   * render_up_scale: render at s x resolution, bilinear resize of render / depth / normal back, radii // s (:625-659);
-  * rich_info = is_training, sh_degree = min(active, max) (:639-641).
+  * rich_info = is_training, sh_degree = min(active, max) (:639-641);
+  * the per-view colour affine, when asked for (:678-684).
 """
 from __future__ import annotations
 
@@ -73,8 +74,10 @@ def render_view(camera, vertex: torch.Tensor, f_dc: torch.Tensor, f_rest: torch.
                 bg_color: torch.Tensor, gamma: float = 1.0, active_sh_degree: int = 0, max_sh_degree: int = 3,
                 is_training: bool = True, back_culling: bool = False, gamma_rescale: bool = False,
                 ste_threshold: Optional[float] = None, render_up_scale: Optional[int] = None,
-                rasterizer_type: str = "3D", shs: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
-    """`shs` (P, M, 3): the colour coefficients as ONE tensor (then f_dc and f_rest are None) -- the layout that saves the reference's
+                rasterizer_type: str = "3D", shs: Optional[torch.Tensor] = None, color_affine=None) -> Dict[str, torch.Tensor]:
+    """`color_affine` = (module, uid): the per-view colour affine of :678-684 -- pkg["render"] becomes module(render, uid) (a
+    regularizers.ColorAffine), pkg["render_original"] the raw render; without it the output is unchanged.
+    `shs` (P, M, 3): the colour coefficients as ONE tensor (then f_dc and f_rest are None) -- the layout that saves the reference's
     torch.cat((f_dc, f_rest)) of every forward (VanillaTS_model.py:79-80: 2 x 12 M bytes per triangle moved per step, and again in its
     backward); the reference's two tensors remain the default."""
     if shs is None:
@@ -107,4 +110,8 @@ def render_view(camera, vertex: torch.Tensor, f_dc: torch.Tensor, f_rest: torch.
     if is_training:  # :664-679
         pkg.update(radii=out["radii"], center2D=out["center2D"], contrib_sum=out["contrib_sum"], contrib_max=out["contrib_max"],
                    depth=out["depth"], normal=out["normal"], opacity=opacity, vertex=vertex, visible_mask=out["radii"] > 0)
+    if color_affine is not None:  # :678-684
+        module, uid = color_affine
+        pkg["render_original"] = pkg["render"]
+        pkg["render"] = module(pkg["render"], uid)
     return pkg

@@ -1,12 +1,13 @@
 """The drop-in boundary from the side the reference's own FFI binds: `bindings/_ts2d_torch_C.so` is a compiled torch C++
 extension (pybind, the reference's `ext.cpp` signatures, R2D/ext.cpp:4-9 + R2D/src/extension_interface.h:7-62) that links
 libts2d.so.  Three parity cases go through ITS `rasterize_triangles` / `rasterize_triangles_backward` and are checked against
-the CPU oracle; the error path and the P = 0 path mirror the reference's."""
+the CPU oracle; the error path and the P = 0 path mirror the reference's.  The package's caller-side `center2D_sink` is checked here too."""
 import importlib.util
 import os
 
 import numpy as np
 import pytest
+import torch
 
 import helpers
 import synthetic
@@ -107,3 +108,12 @@ def test_the_package_runs_on_both_bindings():
                         "-k", "not full_size and not lab and not forced and not one_launch"], env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert " passed" in r.stdout
+
+
+def test_center2D_sink_is_a_fresh_leaf_over_cached_zeros():
+    from diff_triangle_rasterization_2D import center2D_sink
+    a, b = center2D_sink(1000, "cuda"), center2D_sink(1000, "cuda")
+    assert a.is_leaf and b.is_leaf and a.requires_grad and a is not b and a.grad is None
+    assert a.data_ptr() == b.data_ptr() and float(a.abs().sum()) == 0.0 and a.shape == (1000, 2)
+    a.backward(torch.ones_like(a))
+    assert b.grad is None and float(a.grad.sum()) == 2000.0

@@ -42,7 +42,8 @@ def test_library_exports_every_declared_symbol(lib):
 
 def test_product_library_reads_no_environment_and_has_one_blend_path(hip_lib_built):
     """libts2d.so carries one blend kernel family per variant (the lane-group kernels) and no run-time switch: the measurement
-    kernels of earlier rounds and their TS2D_BLEND / TS2D_BWD / TS2D_ABLATE variables were removed and must not come back."""
+    kernels of earlier rounds and their TS2D_BLEND / TS2D_BWD / TS2D_ABLATE variables were removed and must not come back, nor
+    the side-stream colour kernel of round 6."""
     import subprocess
     blob = open(hip_lib_built, "rb").read()
     for name in (b"TS2D_BLEND", b"TS2D_BWD", b"TS2D_ABLATE"):
@@ -51,6 +52,7 @@ def test_product_library_reads_no_environment_and_has_one_blend_path(hip_lib_bui
     launchers = sorted(set(re.findall(r"ts_launch_render\w*?(?=RK)", syms)))
     assert launchers, "nm found no blend launchers"
     assert all("group" in n for n in launchers), launchers
+    assert "preprocess_colour" not in syms
 
 
 def test_product_library_exports_only_the_declared_c_abi(hip_lib_built):

@@ -2,7 +2,7 @@
 # tools/lease.sh -- ONE parameterised script for every GPU lease (round 6 on).  Rounds 3-5 kept one script per lease (tools/r03_prof.sh, r04_*.sh,
 # r05_call1.sh ... r05_call19.sh, final_*.sh: ~30 files, deleted in round 6 -- `git log -- tools/r05_call7.sh` has them; every one was a sequence of
 # the steps below: tests, bench lines, A/B of two libraries, rocprofv3 trace, counter pass).  A lease is a list of steps, each a shell function:
-#     gpurun --timeout 1500 -- 'bash tools/lease.sh r06_a "t tests/test_side_stream_gpu.py; bench head; ab r05 2; prof head"'
+#     bash tools/lease.sh r06_a "t tests/test_binding_gpu.py; bench head; ab r05 2; prof head"
 # Output goes to gpurun_out/<tag>/ (merged back by gpurun); what is worth judging is copied from there into profiles/ by hand.
 R=${GRAFT_REPO_ROOT:-/root/repo}
 TAG=$1; shift
@@ -70,7 +70,7 @@ loss() { timeout 600 python tools/bench_loss.py "$@" 2>/dev/null | tee -a $O/los
 # gaps, counter passes (HBM traffic with both calibrations, SQ counters of the blend kernels), the other configurations, forward-only lines, training
 # iterations, the loss kernels.  Copy what is worth judging from gpurun_out/<tag>/ into profiles/ (named r<NN>_*).
 final() {
-    t tests/test_side_stream_gpu.py tests/test_loss_gpu.py tests/test_model_init_gpu.py tests/test_binding_gpu.py
+    t tests/test_loss_gpu.py tests/test_model_init_gpu.py tests/test_binding_gpu.py
     for i in 1 2 3 4; do bench bench_series --steps 20 --warmup 5 $([ $i -gt 1 ] && echo --no-cpu-baseline); done
     prof driver --steps 20 --warmup 5
     bash tools/prof_gaps.sh > $O/gaps.txt 2>&1; tail -20 $O/gaps.txt

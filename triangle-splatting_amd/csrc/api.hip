@@ -113,8 +113,6 @@ void prof_drain()
 
 #ifdef TS2D_LAB
 bool g_lab_all_quadrants = false; // ts2d_lab_force_all_quadrants (csrc/ts2d_lab.h)
-bool g_lab_side_stream = false; // ts2d_lab_side_stream: the SH colours on a side stream (measured, not adopted: see SideLane)
-int g_lab_colour_blocks = 0;    // ts2d_lab_colour_blocks: resident single-wave workgroups of the colour kernel (0 = TS_COLOUR_BLOCKS)
 #endif
 
 int validate(const ts2d_camera *cam, const ts2d_geometry *geom, uint32_t flags)
@@ -167,50 +165,6 @@ RenderArgs make_render(const ts2d_camera *cam, const ts2d_geometry *geom, uint32
     r.rich_info = flags & TS2D_FLAG_RICH_INFO;
     return r;
 }
-#ifdef TS2D_LAB
-// ---- a side stream for the SH colours: LAB LIBRARY ONLY, a measured negative result (round 6, profiles/r06_side_stream.txt) --------------------
-// one forward = an HBM-bound per-triangle kernel in front of a chain of latency-bound launches (depth sort, scan, emission,
-// tile sort: 2-3 waves per SIMD, the HBM mostly idle), and 228 of the 327 bytes per triangle that kernel moves (the SH row -> r g b) are first
-// read by the blend kernel.  Built: the per-triangle kernel without the colours (PRE_NOCOLOUR, 72 -> 34 us) and a colour kernel on a library-owned
-// stream, forked behind it and joined in front of the blend kernel, throttled by its grid.  Measured at the headline, product and variant
-// alternating on one box: NO grid wins -- the chain's kernels are chains of dependent memory round trips, and any background stream of bytes
-// stretches every one of them (grid 512 = 2.3 TB/s beside them: depth sort 40 -> 67 us, census 21 -> 31, emission 53 -> 60: step 1.581 against
-// 1.563; grid 128: the colours arrive 0.17 ms late).  A lowest-priority stream made EVERY later kernel of the process slower (preprocess_bwd +13 %)
-// and a capture of the forked stream into a HIP graph crashed in hipStreamEndCapture on this stack.  The product keeps ONE launch on ONE stream.
-struct SideLane { hipStream_t s = nullptr; hipEvent_t fork = nullptr, join = nullptr; };
-#ifndef TS_COLOUR_BLOCKS
-#define TS_COLOUR_BLOCKS 512 /* resident single-wave workgroups of the colour kernel: the throttle (2 per compute unit) */
-#endif
-SideLane *acquire_side_lane()
-{
-    constexpr int LANES = 4, MAXDEV = 16;
-    static SideLane lanes[MAXDEV][LANES];
-    static std::atomic<unsigned> next[MAXDEV];
-    static std::mutex mu;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV) return nullptr;
-    SideLane &l = lanes[dev][next[dev].fetch_add(1) % LANES];
-    if (!l.s)
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (!l.s)
-        {
-            hipStream_t st = nullptr; // default priority: see above
-            if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-            if (hipEventCreateWithFlags(&l.fork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&l.join, hipEventDisableTiming) != hipSuccess)
-            {
-                (void)hipGetLastError();
-                (void)hipStreamDestroy(st);
-                return nullptr;
-            }
-            l.s = st;
-        }
-    }
-    return &l;
-}
-#else
-struct SideLane; // (lab library only)
-#endif
 
 // Early read-back of the instance count (binning.hip, count_instances_kernel): a pinned host word + an event per call in flight
 struct EarlyCount
@@ -219,7 +173,7 @@ struct EarlyCount
     hipEvent_t ev = nullptr;
 };
 int forward_bin_impl(const ts2d_camera *cam, const ts2d_geometry *geom, uint32_t flags, int32_t *radii, const ts2d_state *state, hipStream_t s,
-                     EarlyCount *early, SideLane **pending = nullptr);
+                     EarlyCount *early);
 bool acquire_early_count(EarlyCount &e)
 {
     constexpr int SLOTS = 64, MAXDEV = 16; // calls that may be between their launch and their wait at the same time, per device
@@ -325,6 +279,32 @@ void record_instance_count(int variant, int W, int H, int P, unsigned long long 
     slot->per_triangle = per > 0.97 * slot->per_triangle ? per : 0.97 * slot->per_triangle; // a decaying maximum over the recent views
     slot->stamp = ++g_hint_clock;
 }
+
+// The instance count of a forward whose bin phase is queued on `s`, for the host: the early read-back (early != nullptr) or, when there is no
+// pinned word (allocation refused), a copy behind everything that was queued -- slower, same results.  Stored in *num_rendered and recorded
+// for the capacity hints.
+int read_instance_count(const ts2d_camera *cam, const ts2d_geometry *geom, uint32_t flags, const ts2d_state *state, const EarlyCount *early,
+                        hipStream_t s, int64_t *num_rendered)
+{
+    const int P = geom->P;
+    unsigned long long n = 0;
+    if (early)
+    {
+        if (int rc = wait_early_count(*early, &n)) return rc;
+    }
+    else
+    {
+        GeometryStateView g;
+        ts_carve_geometry((char *)state->geometry, P, g);
+        TS_HIP(hipMemcpyAsync(&n, ts_instance_count_dev(g, P), sizeof(n), hipMemcpyDeviceToHost, s));
+        TS_HIP(hipStreamSynchronize(s));
+    }
+    if (n > 0x7fffffffull) // the reference's int num_rendered wraps here; instance slots are 32-bit
+        return fail(TS2D_ERR_CAPACITY, "%llu tile instances exceed the 2^31 - 1 the instance list can address", n);
+    *num_rendered = (int64_t)n;
+    record_instance_count((flags & TS2D_FLAG_3D) ? 3 : 2, cam->width, cam->height, P, n);
+    return TS2D_OK;
+}
 } // namespace
 
 extern "C" {
@@ -392,33 +372,17 @@ int ts2d_forward_bin(const ts2d_camera *cam, const ts2d_geometry *geom, uint32_t
     EarlyCount early;
     const bool have_early = acquire_early_count(early);
     if (int rc = forward_bin_impl(cam, geom, flags, radii, state, s, have_early ? &early : nullptr)) return rc;
-    unsigned long long n = 0;
-    if (have_early)
-    {
-        if (int rc = wait_early_count(early, &n)) return rc;
-    }
-    else
-    {
-        GeometryStateView g;
-        ts_carve_geometry((char *)state->geometry, P, g);
-        TS_HIP(hipMemcpyAsync(&n, ts_instance_count_dev(g, P), sizeof(n), hipMemcpyDeviceToHost, s));
-        TS_HIP(hipStreamSynchronize(s));
-    }
-    if (n > 0x7fffffffull) // the reference's int num_rendered wraps here; instance slots are 32-bit
-        return fail(TS2D_ERR_CAPACITY, "%llu tile instances exceed the 2^31 - 1 the instance list can address", n);
-    *num_rendered = (int64_t)n;
-    record_instance_count((flags & TS2D_FLAG_3D) ? 3 : 2, cam->width, cam->height, P, n);
-    return TS2D_OK;
+    return read_instance_count(cam, geom, flags, state, have_early ? &early : nullptr, s, num_rendered);
 }
 
 } // extern "C" (reopened below, after the internal helpers)
 
 namespace
 {
-// Everything after the instance count is known -- on the host (n_dev == nullptr, N exact: the reference's sequence) or only on
-// the device (n_dev != nullptr, N = the capacity the binning state was carved for).
-int forward_render_impl(const ts2d_camera *cam, const ts2d_geometry *geom, uint32_t flags, int64_t N, const unsigned long long *n_dev,
-                        const ts2d_state *state, const ts2d_forward_out *out, hipStream_t s, SideLane *pending = nullptr)
+// Everything after the instance count is known -- on the host (count_on_device = false, N exact: the reference's sequence) or only on
+// the device (count_on_device = true, N = the capacity the binning state was carved for).
+int forward_render_impl(const ts2d_camera *cam, const ts2d_geometry *geom, uint32_t flags, int64_t N, bool count_on_device,
+                        const ts2d_state *state, const ts2d_forward_out *out, hipStream_t s)
 {
     const bool rich = flags & TS2D_FLAG_RICH_INFO;
     const int P = geom->P, W = cam->width, H = cam->height;
@@ -430,12 +394,12 @@ int forward_render_impl(const ts2d_camera *cam, const ts2d_geometry *geom, uint3
     {
         // the layout follows from the buffer's size (ts_binning_capacity): the backward finds it again without being told the capacity
         ts_carve_binning((char *)state->binning, ts_binning_capacity(state->binning_bytes, W, H), W, H, b);
-        if (!n_dev) ts_binning_set_count(b, N); // the host knows the count: no launch covers more than it
+        if (!count_on_device) ts_binning_set_count(b, N); // the host knows the count: no launch covers more than it
     }
     ts_carve_image((char *)state->image, W, H, im);
     const RenderArgs r = make_render(cam, geom, flags);
     const int ntiles = r.grid_x * r.grid_y;
-    if (n_dev) n_dev = ts_instance_count_dev(g, P);
+    const unsigned long long *n_dev = count_on_device ? ts_instance_count_dev(g, P) : nullptr;
 
     // tile ranges (rasterizer.cu:223) and the contribution statistics are cleared by the emission kernel, not by memsets
     if (P > 0)
@@ -466,9 +430,6 @@ int forward_render_impl(const ts2d_camera *cam, const ts2d_geometry *geom, uint3
         }
         TS_CHECK(flags, s, "tile_ranges");
     }
-#ifdef TS2D_LAB
-    if (pending) TS_HIP(hipStreamWaitEvent(s, pending->join, 0)); // the SH colours: the blend kernel is their first reader
-#endif
     {
         ProfScope ps("render_fwd", s);
         if (flags & TS2D_FLAG_3D)
@@ -502,36 +463,18 @@ int check_forward_args(const ts2d_camera *cam, const ts2d_geometry *geom, uint32
 
 // preprocess + depth order + instance count on the device (no host read)
 int forward_bin_impl(const ts2d_camera *cam, const ts2d_geometry *geom, uint32_t flags, int32_t *radii, const ts2d_state *state, hipStream_t s,
-                     EarlyCount *early, SideLane **pending)
+                     EarlyCount *early)
 {
-    if (pending) *pending = nullptr;
     const int P = geom->P;
     GeometryStateView g;
     ts_carve_geometry((char *)state->geometry, P, g);
     const PreprocessArgs a = make_pre(cam, geom, flags);
-    SideLane *lane = nullptr;
-#ifdef TS2D_LAB
-    // lab library only: the SH colours on a side stream beside the ordering chain (see SideLane: measured, not adopted)
-    if (g_lab_side_stream && P >= 131072 && !(flags & TS2D_FLAG_DEBUG) && ts_preprocess_fwd_splittable(a)) lane = acquire_side_lane();
-#endif
     {
         ProfScope ps("preprocess_fwd", s);
-        if (flags & TS2D_FLAG_3D) ts_launch_preprocess3d_fwd(a, radii, g, s, lane ? 1 : 0);
-        else ts_launch_preprocess_fwd(a, radii, g, s, lane ? 1 : 0);
+        if (flags & TS2D_FLAG_3D) ts_launch_preprocess3d_fwd(a, radii, g, s);
+        else ts_launch_preprocess_fwd(a, radii, g, s);
     }
     TS_CHECK(flags, s, "preprocess_fwd");
-#ifdef TS2D_LAB
-    if (lane)
-    {
-        TS_HIP(hipEventRecord(lane->fork, s)); // behind the per-triangle kernel: the colour kernel reads its tile counts and writes into its records
-        TS_HIP(hipStreamWaitEvent(lane->s, lane->fork, 0));
-        {
-            ProfScope ps("preprocess_colour", lane->s);
-            ts_launch_preprocess_colour(a, g, (flags & TS2D_FLAG_3D) ? 3 : 2, g_lab_colour_blocks > 0 ? g_lab_colour_blocks : TS_COLOUR_BLOCKS, lane->s);
-        }
-        TS_HIP(hipEventRecord(lane->join, lane->s));
-    }
-#endif
     {
         // the first histogram of the depth sort also sums the instance count and writes it to the pinned host word itself: the host
         // waits for the event behind THIS launch only and allocates the binning buffer while the rest of the sort runs
@@ -549,13 +492,6 @@ int forward_bin_impl(const ts2d_camera *cam, const ts2d_geometry *geom, uint32_t
         ts_scan_offsets(g, P, s);
     }
     TS_CHECK(flags, s, "scan");
-#ifdef TS2D_LAB
-    if (lane)
-    {
-        if (pending) *pending = lane; // the caller queues the rest of the forward on `s` and joins in front of the blend kernel
-        else TS_HIP(hipStreamWaitEvent(s, lane->join, 0)); // two-call form: the join sits in front of whatever `s` runs next
-    }
-#endif
     return TS2D_OK;
 }
 } // namespace
@@ -566,7 +502,7 @@ int ts2d_forward_render(const ts2d_camera *cam, const ts2d_geometry *geom, uint3
                         const ts2d_state *state, const ts2d_forward_out *out, void *stream)
 {
     if (int rc = check_forward_args(cam, geom, flags, N, state, out)) return rc;
-    return forward_render_impl(cam, geom, flags, N, nullptr, state, out, (hipStream_t)stream);
+    return forward_render_impl(cam, geom, flags, N, false, state, out, (hipStream_t)stream);
 }
 
 int ts2d_forward(const ts2d_camera *cam, const ts2d_geometry *geom, uint32_t flags, int32_t *radii, const ts2d_state *state,
@@ -574,13 +510,11 @@ int ts2d_forward(const ts2d_camera *cam, const ts2d_geometry *geom, uint32_t fla
 {
     if (int rc = check_forward_args(cam, geom, flags, instance_capacity, state, out)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (geom->P == 0) return forward_render_impl(cam, geom, flags, 0, nullptr, state, out, s);
+    if (geom->P == 0) return forward_render_impl(cam, geom, flags, 0, false, state, out, s);
     if (!radii) return fail(TS2D_ERR_INVALID, "radii is null");
     if (instance_capacity <= 0) return fail(TS2D_ERR_INVALID, "instance_capacity must be positive");
-    SideLane *pending = nullptr;
-    if (int rc = forward_bin_impl(cam, geom, flags, radii, state, s, nullptr, &pending)) return rc;
-    static const unsigned long long on_device = 0; // any non-null marker: forward_render_impl resolves the real address
-    return forward_render_impl(cam, geom, flags, instance_capacity, &on_device, state, out, s, pending);
+    if (int rc = forward_bin_impl(cam, geom, flags, radii, state, s, nullptr)) return rc;
+    return forward_render_impl(cam, geom, flags, instance_capacity, true, state, out, s);
 }
 
 int ts2d_forward_speculative(const ts2d_camera *cam, const ts2d_geometry *geom, uint32_t flags, int32_t *radii, const ts2d_state *state,
@@ -591,7 +525,7 @@ int ts2d_forward_speculative(const ts2d_camera *cam, const ts2d_geometry *geom, 
     if (int rc = check_forward_args(cam, geom, flags, 0, state, out)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int P = geom->P, W = cam->width, H = cam->height;
-    if (P == 0) return forward_render_impl(cam, geom, flags, 0, nullptr, state, out, s); // extension_interface.cu:130: background only
+    if (P == 0) return forward_render_impl(cam, geom, flags, 0, false, state, out, s); // extension_interface.cu:130: background only
     if (!radii) return fail(TS2D_ERR_INVALID, "radii is null");
     int64_t cap = state->binning ? ts_binning_capacity(state->binning_bytes, W, H) : 0;
     // a buffer too small for even an empty binning state would queue no render, and a scene of zero instances would then leave the outputs
@@ -600,31 +534,14 @@ int ts2d_forward_speculative(const ts2d_camera *cam, const ts2d_geometry *geom, 
     if (state->binning && cap <= 0) return fail(TS2D_ERR_CAPACITY, "binning state buffer too small for any instance (pass NULL to size it from num_rendered)");
     EarlyCount early;
     const bool have_early = acquire_early_count(early);
-    SideLane *pending = nullptr;
-    if (int rc = forward_bin_impl(cam, geom, flags, radii, state, s, have_early ? &early : nullptr, cap > 0 ? &pending : nullptr)) return rc;
+    if (int rc = forward_bin_impl(cam, geom, flags, radii, state, s, have_early ? &early : nullptr)) return rc;
     if (cap > 0)
     {
         // everything behind the count is queued for the CAPACITY before the host has seen the count: the GPU never waits for the host
-        static const unsigned long long on_device = 0; // any non-null marker: forward_render_impl resolves the real address
-        if (int rc = forward_render_impl(cam, geom, flags, cap, &on_device, state, out, s, pending)) return rc;
+        if (int rc = forward_render_impl(cam, geom, flags, cap, true, state, out, s)) return rc;
     }
-    unsigned long long n = 0;
-    if (have_early)
-    {
-        if (int rc = wait_early_count(early, &n)) return rc;
-    }
-    else // no pinned word (allocation refused): the count is copied behind everything that was queued -- slower, same results
-    {
-        GeometryStateView g;
-        ts_carve_geometry((char *)state->geometry, P, g);
-        TS_HIP(hipMemcpyAsync(&n, ts_instance_count_dev(g, P), sizeof(n), hipMemcpyDeviceToHost, s));
-        TS_HIP(hipStreamSynchronize(s));
-    }
-    if (n > 0x7fffffffull) // the reference's int num_rendered wraps here; instance slots are 32-bit
-        return fail(TS2D_ERR_CAPACITY, "%llu tile instances exceed the 2^31 - 1 the instance list can address", n);
-    *num_rendered = (int64_t)n;
-    record_instance_count((flags & TS2D_FLAG_3D) ? 3 : 2, W, H, P, n);
-    if (cap > 0 && (int64_t)n > cap) g_speculative_overflows.fetch_add(1, std::memory_order_relaxed); // the caller now renders a second time
+    if (int rc = read_instance_count(cam, geom, flags, state, have_early ? &early : nullptr, s, num_rendered)) return rc;
+    if (cap > 0 && *num_rendered > cap) g_speculative_overflows.fetch_add(1, std::memory_order_relaxed); // the caller now renders a second time
     return TS2D_OK;
 }
 
@@ -1348,8 +1265,6 @@ int ts2d_debug_read_state(const ts2d_state *state, int32_t P, int64_t N, int32_t
 // ts2d_test_sort_pairs / ts2d_test_inclusive_scan_rocprim: tools/lab/lab_hooks.hip (the rocPRIM comparators live there, outside the product's objects)
 void ts2d_lab_force_ticket_passes(int on) { ts_force_ticket_passes(on != 0); }
 void ts2d_lab_force_all_quadrants(int on) { g_lab_all_quadrants = on != 0; }
-void ts2d_lab_side_stream(int on) { g_lab_side_stream = on != 0; }
-void ts2d_lab_colour_blocks(int blocks) { g_lab_colour_blocks = blocks; }
 void ts2d_lab_force_depth_pass4(int on) { ts_force_depth_pass4(on != 0); }
 void ts2d_lab_depth_split(int mode, int bucket_cap) { ts_lab_depth_split(mode, bucket_cap); }
 #endif // TS2D_LAB

@@ -19,9 +19,6 @@ using namespace ts;
 namespace
 {
 // One triangle.  `vp` = its 9 vertex floats, `shp` = its SH row (3 M floats); either global memory or an LDS row.
-// MODE (ts2d_preprocess_launch.h): PRE_ALL = everything; PRE_NOCOLOUR = everything except the SH colour (SH mode only: the record's r g b and the
-// clamp flags are left 0, preprocess_colour_kernel fills them in on the library's side stream beside the ordering chain).
-template <int MODE>
 __device__ __forceinline__ void preprocess_fwd_one(const PreprocessArgs &a, int32_t *__restrict__ radii, const GeometryStateView &g,
                                                    int idx, const float *vp, const float *shp, float4 *rec_row)
 {
@@ -87,8 +84,7 @@ __device__ __forceinline__ void preprocess_fwd_one(const PreprocessArgs &a, int3
 
         {
         f3 rgb = {0, 0, 0};
-        if (MODE == PRE_NOCOLOUR) {}
-        else if (a.use_shs)
+        if (a.use_shs)
         {
             const f3 cp = {a.campos[0], a.campos[1], a.campos[2]};
             rgb = sh_to_rgb(a.D, shp, center, cp);
@@ -267,21 +263,14 @@ __device__ __forceinline__ void preprocess_bwd_one(const PreprocessArgs &a, cons
 
 struct Raster2D
 {
-    template <int MODE, class... T> static __device__ __forceinline__ void fwd(T... t) { preprocess_fwd_one<MODE>(t...); }
+    template <class... T> static __device__ __forceinline__ void fwd(T... t) { preprocess_fwd_one(t...); }
     template <class... T> static __device__ __forceinline__ void bwd(T... t) { preprocess_bwd_one(t...); }
 };
 } // namespace
 
-void ts_launch_preprocess_fwd(const PreprocessArgs &a, int32_t *radii, const GeometryStateView &g, hipStream_t s, int mode)
+void ts_launch_preprocess_fwd(const PreprocessArgs &a, int32_t *radii, const GeometryStateView &g, hipStream_t s)
 {
-    launch_preprocess_fwd<Raster2D>(a, radii, g, s, mode);
-}
-
-bool ts_preprocess_fwd_splittable(const PreprocessArgs &a) { return preprocess_fwd_splittable(a); }
-void ts_launch_preprocess_colour(const PreprocessArgs &a, const GeometryStateView &g, int variant, int blocks, hipStream_t s)
-{
-    if (variant == 3) launch_preprocess_colour<13>(a, g, blocks, s); // record layouts: ts2d_common.h
-    else launch_preprocess_colour<7>(a, g, blocks, s);
+    launch_preprocess_fwd<Raster2D>(a, radii, g, s);
 }
 
 void ts_launch_preprocess_bwd(const PreprocessArgs &a, const int32_t *radii, const GeometryStateView &g,

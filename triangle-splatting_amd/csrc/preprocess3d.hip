@@ -21,7 +21,6 @@ namespace
 __device__ __forceinline__ float proj_to_pix(float v, int S) { return (v + 1.0f) * S * 0.5f - 0.5f; } // R3D auxiliary.h:35-38
 
 // One triangle; `vp` / `shp` = its vertex / SH rows (global memory or LDS, ts2d_preprocess_launch.h).
-template <int MODE> // PRE_ALL / PRE_NOCOLOUR, see preprocess.hip
 __device__ __forceinline__ void preprocess3d_fwd_one(const PreprocessArgs &a, int32_t *__restrict__ radii, const GeometryStateView &g,
                                                      int idx, const float *vp, const float *shp, float4 *rec_row)
 {
@@ -64,8 +63,7 @@ __device__ __forceinline__ void preprocess3d_fwd_one(const PreprocessArgs &a, in
         if (rmaxx <= rminx || rmaxy <= rminy) break;
 
         f3 rgb = {0, 0, 0};
-        if (MODE == PRE_NOCOLOUR) {}
-        else if (a.use_shs)
+        if (a.use_shs)
         {
             const f3 cp = {a.campos[0], a.campos[1], a.campos[2]};
             rgb = sh_to_rgb(a.D, shp, center, cp);
@@ -174,14 +172,14 @@ __device__ __forceinline__ void preprocess3d_bwd_one(const PreprocessArgs &a, co
 }
 struct Raster3D
 {
-    template <int MODE, class... T> static __device__ __forceinline__ void fwd(T... t) { preprocess3d_fwd_one<MODE>(t...); }
+    template <class... T> static __device__ __forceinline__ void fwd(T... t) { preprocess3d_fwd_one(t...); }
     template <class... T> static __device__ __forceinline__ void bwd(T... t) { preprocess3d_bwd_one(t...); }
 };
 } // namespace
 
-void ts_launch_preprocess3d_fwd(const PreprocessArgs &a, int32_t *radii, const GeometryStateView &g, hipStream_t s, int mode)
+void ts_launch_preprocess3d_fwd(const PreprocessArgs &a, int32_t *radii, const GeometryStateView &g, hipStream_t s)
 {
-    launch_preprocess_fwd<Raster3D>(a, radii, g, s, mode);
+    launch_preprocess_fwd<Raster3D>(a, radii, g, s);
 }
 
 void ts_launch_preprocess3d_bwd(const PreprocessArgs &a, const int32_t *radii, const GeometryStateView &g,

@@ -237,9 +237,7 @@ struct PreprocessArgs
     const float *vertex, *shs, *feature, *opacity;
 };
 
-void ts_launch_preprocess_fwd(const PreprocessArgs &a, int32_t *radii, const GeometryStateView &g, hipStream_t s, int mode = 0); // mode: ts2d_preprocess_launch.h (PRE_ALL / PRE_NOCOLOUR)
-bool ts_preprocess_fwd_splittable(const PreprocessArgs &a);
-void ts_launch_preprocess_colour(const PreprocessArgs &a, const GeometryStateView &g, int variant, int blocks, hipStream_t s); // the SH colours behind a PRE_NOCOLOUR launch
+void ts_launch_preprocess_fwd(const PreprocessArgs &a, int32_t *radii, const GeometryStateView &g, hipStream_t s);
 // binning.hip -- every step hand-written for gfx950 (the round-1 rocPRIM calls survive only as test comparators)
 void ts_sort_by_depth_begin(const GeometryStateView &g, int32_t P, unsigned long long *host_out, hipStream_t s); // first histogram + N + key-bit census
 void ts_sort_by_depth_finish(const GeometryStateView &g, int32_t P, hipStream_t s);          // the rest: (depth bits, id) -> sorted ids
@@ -294,7 +292,7 @@ void ts_launch_preprocess_bwd(const PreprocessArgs &a, const int32_t *radii, con
 // ---- 3D variant (TS2D_FLAG_3D): same states and binning, its own record contents and blend maths -----------------
 // Render record: [0..8] v1_view v2_view v3_view   [9..11] normal_view (unnormalised)   [12] opacity   [13..15] r g b
 // Gradient record: [0..8] dL/dv{1,2,3}_view   [9..11] dL/dnormal_view   [12] dL/dopacity   [13..15] dL/drgb
-void ts_launch_preprocess3d_fwd(const PreprocessArgs &a, int32_t *radii, const GeometryStateView &g, hipStream_t s, int mode = 0);
+void ts_launch_preprocess3d_fwd(const PreprocessArgs &a, int32_t *radii, const GeometryStateView &g, hipStream_t s);
 void ts_launch_preprocess3d_bwd(const PreprocessArgs &a, const int32_t *radii, const GeometryStateView &g,
                                 const float *grad_rec, float *dL_dvertex, float *dL_dcenter2D, float *dL_dshs,
                                 float *dL_dfeature, float *dL_dopacity, hipStream_t s);

@@ -48,13 +48,6 @@ void ts2d_lab_depth_split(int mode, int bucket_cap); // mode 0: the product's ch
  * tests/test_qmask_gpu.py compares the two, bit for bit where the arithmetic is ordered. */
 void ts2d_lab_force_all_quadrants(int on);
 
-/* Round 6, a measured negative result kept reproducible (csrc/api.hip: SideLane; profiles/r06_side_stream.txt): on != 0 -> SH scenes of 131 072
- * triangles and more run the per-triangle kernel WITHOUT the SH colours and evaluate those with a throttled kernel on a library-owned stream,
- * forked behind the per-triangle kernel and joined in front of the blend kernel (bench.py --side-stream [--colour-blocks n]; n = the colour
- * kernel's grid = its throttle).  State and outputs are those of the single launch, bit for bit (tests/test_side_stream_gpu.py). */
-void ts2d_lab_side_stream(int on);
-void ts2d_lab_colour_blocks(int blocks);
-
 #ifdef __cplusplus
 }
 #endif

@@ -109,6 +109,8 @@ def lab_library():
         import ctypes as C
         if not os.path.exists(LAB_LIB):
             raise RuntimeError(f"{LAB_LIB} not found: build it with `python triangle-splatting_amd/build.py --lab`")
+        # the package first: the lab library carries the soname libts2d.so too, and the extension binds the first library of that name loaded
+        from diff_triangle_rasterization_2D import _C as product
         L = C.CDLL(LAB_LIB)
         L.ts2d_last_error.restype = C.c_char_p
         L.ts2d_debug_read_state.restype = C.c_int
@@ -122,7 +124,6 @@ def lab_library():
         L.ts2d_test_inclusive_scan_rocprim.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.ts2d_lab_force_ticket_passes.argtypes = [C.c_int]
         # same layout code as the product library?  (a lab library left over from before a change of csrc/ts2d_common.h decodes other offsets)
-        from diff_triangle_rasterization_2D import _C as product
         for f, args in (("ts2d_geometry_state_bytes", (C.c_int32(12345),)), ("ts2d_binning_state_bytes", (C.c_int64(54321), C.c_int32(640), C.c_int32(480))),
                         ("ts2d_binning_state_bytes", (C.c_int64(7654321), C.c_int32(1920), C.c_int32(1080))), ("ts2d_image_state_bytes", (C.c_int32(640), C.c_int32(480)))):
             mine, theirs = getattr(L, f), getattr(product._lib, f)

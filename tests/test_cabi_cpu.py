@@ -184,39 +184,95 @@ def test_argument_checks_mirror_reference_errors(hip_lib_built):
 
 
 def test_missing_library_fails_loudly(tmp_path, hip_lib_built):
-    """The product must not degrade silently when the HIP library is absent."""
+    """The product must not degrade silently when the HIP library is absent, nor when the library is there but its torch extension is not."""
     import shutil
     import subprocess
     import sys
     pkg_src = os.path.join(ROOT, "triangle-splatting_amd", "diff_triangle_rasterization_2D")
     pkg = tmp_path / "diff_triangle_rasterization_2D"
     shutil.copytree(pkg_src, pkg, ignore=shutil.ignore_patterns("*.so", "__pycache__"))
-    r = subprocess.run([sys.executable, "-c", "import diff_triangle_rasterization_2D"], cwd=tmp_path, capture_output=True,
-                       text=True, env={**os.environ, "PYTHONPATH": str(tmp_path)})
+
+    def imported():
+        return subprocess.run([sys.executable, "-c", "import diff_triangle_rasterization_2D"], cwd=tmp_path, capture_output=True,
+                              text=True, env={**os.environ, "PYTHONPATH": str(tmp_path)})
+    r = imported()
     assert r.returncode != 0 and "libts2d.so" in r.stderr and "no CPU fallback" in r.stderr
+    shutil.copy(hip_lib_built, pkg / "libts2d.so")  # the library, but no bindings/ beside the package
+    r = imported()
+    assert r.returncode != 0 and "_ts2d_torch_C.so" in r.stderr and "triangle-splatting_amd/build.py" in r.stderr
 
 
-def test_compiled_reference_side_binding_loads(hip_lib_built):
-    """bindings/_ts2d_torch_C.so (torch C++ extension with the reference's ext.cpp signatures, linked against libts2d.so) builds
-    without a GPU and exports the reference's two entry points (R2D/ext.cpp:4-9) plus, since round 6, the package's own two (`*_ex`: the same
-    calls with the variant / capacity / preallocated-output arguments the package adds; diff_triangle_rasterization_2D/_C.py prefers them over ctypes)."""
+def _build_module():
     import importlib.util
-    import torch  # noqa: F401
-    spec = importlib.util.spec_from_file_location("ts2d_build_ext", os.path.join(ROOT, "triangle-splatting_amd", "bindings", "build_torch_ext.py"))
+    spec = importlib.util.spec_from_file_location("ts2d_build", os.path.join(ROOT, "triangle-splatting_amd", "build.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    so = mod.build()
+    return mod
+
+
+def test_compiled_binding_is_built_with_the_library_and_loaded_by_the_package(hip_lib_built):
+    """bindings/_ts2d_torch_C.so (torch C++ extension with the reference's ext.cpp signatures, linked against libts2d.so) builds
+    without a GPU and exports the reference's two entry points (R2D/ext.cpp:4-9) plus the package's own two (`*_ex`: the same calls with the
+    variant / capacity / preallocated-output arguments the package adds; diff_triangle_rasterization_2D/_C.py binds them)."""
+    import importlib.util
+    import torch  # noqa: F401
+    build = _build_module()
+    build.build()
+    so = build.EXT
     spec = importlib.util.spec_from_file_location("_ts2d_torch_C", so)
     ext = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(ext)
     assert sorted(n for n in dir(ext) if not n.startswith("_")) == ["rasterize_triangles", "rasterize_triangles_backward", "rasterize_triangles_backward_ex",
                                                                     "rasterize_triangles_ex"]
     from diff_triangle_rasterization_2D import _C
-    assert _C.binding() == ("ctypes" if (os.environ.get("TS2D_BINDING") == "ctypes" or os.environ.get("TS2D_LIBRARY_PATH")) else "compiled")
+    assert os.path.samefile(_C._ext.__file__, so)
     with pytest.raises(RuntimeError):  # CPU tensors: the checks pass, the library refuses host pointers or the device guard raises
         z = torch.zeros
         ext.rasterize_triangles(8, 8, 0.3, 0.3, z(4, 4), z(4, 4), z(3), 0, 1.0, 1.0, 1.0, z(3), z(2, 3, 3), z(2, 1, 3), torch.empty(0), z(2, 1),
                                 False, True, False)
+
+
+_CHILD = """
+import torch
+from diff_triangle_rasterization_2D import _C
+z = torch.zeros
+try:
+    _C.rasterize_triangles(8, 8, 0.3, 0.3, z(4, 4), z(4, 4), z(3), 0, 1.0, 1.0, 1.0, z(3), z(2, 3, 3), z(2, 1, 3), torch.empty(0), z(2, 1), False, True, False)
+except RuntimeError as e:
+    print("refused:", e)
+print(open("/proc/self/maps").read())
+"""
+
+
+def _run_on_library(lib):
+    import subprocess
+    import sys
+    env = {**os.environ, "PYTHONPATH": os.path.join(ROOT, "triangle-splatting_amd"), "TS2D_LIBRARY_PATH": str(lib)}
+    return subprocess.run([sys.executable, "-c", _CHILD], capture_output=True, text=True, env=env)
+
+
+def test_the_extension_calls_the_library_the_package_loaded(tmp_path, hip_lib_built):
+    """TS2D_LIBRARY_PATH swaps the library under the extension too: the extension needs libts2d.so by name, every library build.py links has that
+    soname, so the dynamic loader takes the one _C.py loaded first.  The product file is never mapped."""
+    import shutil
+    copy = tmp_path / "libts2d_copy.so"
+    shutil.copy(hip_lib_built, copy)
+    r = _run_on_library(copy)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert "refused:" in r.stdout and "no CPU fallback" in r.stdout
+    mapped = {l.split()[-1] for l in r.stdout.splitlines() if l.split()}  # the path ends each line of /proc/self/maps that has one
+    assert os.path.realpath(copy) in mapped and os.path.realpath(_build_module().EXT) in mapped
+    assert os.path.realpath(hip_lib_built) not in mapped
+
+
+def test_a_library_without_the_soname_is_refused(tmp_path, hip_lib_built):
+    """A library linked without the soname libts2d.so would leave the extension on the product library, a second instance: the import fails."""
+    import subprocess
+    build = _build_module()
+    lib = tmp_path / "libts2d_nosoname.so"
+    subprocess.run([build.hipcc(), "-shared", "-fPIC", f"--offload-arch={build.ARCH}", "-o", str(lib), *build.objects()], check=True)
+    r = _run_on_library(lib)
+    assert r.returncode != 0 and "lacks the soname libts2d.so" in r.stderr and "triangle-splatting_amd/build.py" in r.stderr
 
 
 def test_ctypes_structures_match_the_c_headers(tmp_path, hip_lib_built):

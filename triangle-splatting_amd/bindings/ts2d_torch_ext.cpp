@@ -6,7 +6,7 @@
 // backward.cu for this one file and links -lts2d; `diff_triangle_rasterization_2D/__init__.py` of the reference then works
 // unchanged on top of it.  Argument checks, error texts, output shapes / dtypes and ownership mirror the reference; device
 // memory comes from torch's allocator, kernels are enqueued on torch's current stream.
-// Built by bindings/build_torch_ext.py (hipcc, in-tree); exercised by tests/test_binding_gpu.py.
+// Built by build.py (hipcc, in-tree, with the product library); exercised by tests/test_binding_gpu.py.
 #include <torch/extension.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h> // ROCm builds of torch: guard / stream types behind the "cuda" device type
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
@@ -45,7 +45,7 @@ void check(int rc, const char *what)
 }
 } // namespace
 
-// The package's own entry point (diff_triangle_rasterization_2D/_C.py, which prefers this module over its ctypes binding since round 6: a forward +
+// The package's own entry point (diff_triangle_rasterization_2D/_C.py calls it, not ctypes, for its two hot entry points: a forward +
 // backward through ctypes costs 0.3-0.4 ms of host time, what bounds every scene below ~100 k triangles).  The reference's signature plus what the
 // package adds to it: variant (2 / 3 = the 3D rasterizer, TS2D_FLAG_3D), instance_capacity (> 0: the sync-free ts2d_forward; 0: the speculative
 // forward), background_depth_dev (the model's 0-dim device tensor handed over as a pointer instead of a synchronising float).

@@ -1,9 +1,11 @@
-"""Builds libts2d.so (the C-ABI HIP library of include/ts2d.h) for gfx950 with hipcc, in-tree.
+"""Builds libts2d.so (the C-ABI HIP library of include/ts2d.h) for gfx950 with hipcc, in-tree, and the package's binding of it.
 
     python triangle-splatting_amd/build.py [--force] [--verbose] [--lab]
     python triangle-splatting_amd/build.py --variant TAG [--lab] [--all "FLAGS"] [--unit NAME="FLAGS" ...]
 
-Output: triangle-splatting_amd/diff_triangle_rasterization_2D/libts2d.so (git-ignored, travels with gpurun).
+Output: triangle-splatting_amd/diff_triangle_rasterization_2D/libts2d.so and the torch extension bindings/_ts2d_torch_C.so (bindings/
+ts2d_torch_ext.cpp, linked -lts2d with an $ORIGIN-relative runpath), both git-ignored.  Every library carries the soname libts2d.so, so the
+extension's dependency on libts2d.so is met by whichever of them _C.py loaded first (TS2D_LIBRARY_PATH).
 --lab builds tools/bin/libts2d_lab.so as well: the same objects + the test hooks of tools/lab/lab_hooks.hip and api.hip compiled with
 -DTS2D_LAB, which exports the switches and readers of csrc/ts2d_lab.h.  The product library contains one blend path per variant and reads no
 environment; only tools/ and tests/ load the lab library (TS2D_LIBRARY_PATH, see _C.py).
@@ -34,6 +36,8 @@ OUT_DIR = os.path.join(HERE, "diff_triangle_rasterization_2D")
 OBJ_DIR = os.path.join(HERE, "build")
 VARIANT_DIR = os.path.join(OBJ_DIR, "variants")
 LIB = os.path.join(OUT_DIR, "libts2d.so")
+EXT_SRC = os.path.join(HERE, "bindings", "ts2d_torch_ext.cpp")
+EXT = os.path.join(HERE, "bindings", "_ts2d_torch_C.so")
 ARCH = "gfx950"
 
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function",
@@ -141,9 +145,28 @@ def command(unit: str, extra=(), variant: str | None = None, cc: str = "hipcc") 
     return [cc, *COMMON, *flags, *extra, "-c", src, "-o", _object(unit, variant if extra else None)]
 
 
+def ext_command(cc: str = "hipcc") -> list:
+    """The build command of the torch extension (the reference's ext.cpp signatures plus the package's *_ex entry points over the C ABI)."""
+    import sysconfig
+    import torch  # include / library directories only
+    ti = os.path.dirname(torch.__file__)
+    return [cc, "-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1", "-DTORCH_EXTENSION_NAME=_ts2d_torch_C",
+            f"-I{ti}/include", f"-I{ti}/include/torch/csrc/api/include", f"-I{sysconfig.get_paths()['include']}", "-I/opt/rocm/include", "-w", "-x",
+            "c++", EXT_SRC, "-x", "none", f"-L{ti}/lib", "-ltorch", "-ltorch_cpu", "-ltorch_hip", "-lc10", "-lc10_hip", "-ltorch_python", f"-L{OUT_DIR}",
+            "-lts2d", "-Wl,-rpath,$ORIGIN/../diff_triangle_rasterization_2D", "-o", EXT]
+
+
+def _fresh(out: str, key: str, newer_than: float) -> bool:
+    # an output is only reused when it was produced by this very command line with this very compiler (its stamp out.cmd holds `key`): a toolchain
+    # update must not leave its outputs behind for the next build
+    stamp = out + ".cmd"
+    return os.path.exists(out) and os.path.exists(stamp) and open(stamp).read() == key and os.path.getmtime(out) >= newer_than
+
+
 def build(force: bool = False, verbose: bool = False, lab: bool = False, variant: str | None = None, extra: dict | None = None) -> str:
-    """Compiles the stale objects and links libts2d.so (lab: and libts2d_lab.so, returned).  variant = TAG: tools/bin/libts2d_TAG.so (lab: and
-    libts2d_lab_TAG.so, returned) instead, the units named in extra = {unit: [flags]} compiled with those flags appended."""
+    """Compiles the stale objects and links libts2d.so (lab: and libts2d_lab.so, returned), then builds the torch extension.  variant = TAG:
+    tools/bin/libts2d_TAG.so (lab: and libts2d_lab_TAG.so, returned) instead, the units named in extra = {unit: [flags]} compiled with those
+    flags appended."""
     extra = {u: list(f) for u, f in (extra or {}).items() if f}
     if variant is None and extra:
         raise ValueError("extra flags need a variant tag")
@@ -155,28 +178,22 @@ def build(force: bool = False, verbose: bool = False, lab: bool = False, variant
     if unknown:
         raise ValueError(f"unknown unit(s) {', '.join(unknown)}; the units are {', '.join(known)}" + ("" if lab else " (lab units need --lab)"))
     cc = hipcc()
-    hdr_t = max(_newest_header(), os.path.getmtime(os.path.abspath(__file__)))
+    tool = _toolchain_id(cc)
+    me = os.path.abspath(__file__)
+    hdr_t = max(_newest_header(), os.path.getmtime(me))
     jobs = []
     for u in known:
         cmd = command(u, extra.get(u, ()), variant, cc)
         s, o = cmd[-3], cmd[-1]
         os.makedirs(os.path.dirname(o), exist_ok=True)
-        # the object is only reused when it was produced by this very command line with this very compiler: a toolchain update must not leave
-        # its objects behind for the next build
-        stamp, key = o + ".cmd", _toolchain_id(cc) + "\n" + " ".join(cmd)
-        fresh = os.path.exists(o) and os.path.exists(stamp) and open(stamp).read() == key
-        if force or not fresh or os.path.getmtime(o) < max(os.path.getmtime(s), hdr_t):
-            jobs.append((cmd, stamp, key))
+        key = tool + "\n" + " ".join(cmd)
+        if force or not _fresh(o, key, max(os.path.getmtime(s), hdr_t)):
+            jobs.append((o, cmd, key))
 
-    def compile_one(job):
-        cmd, stamp, key = job
+    def make(out, cmd, key):
+        stamp = out + ".cmd"
         if os.path.exists(stamp):
             os.remove(stamp)
-        run(cmd)
-        with open(stamp, "w") as f:
-            f.write(key)
-
-    def run(cmd):
         if verbose:
             print(" ".join(cmd), flush=True)
         r = subprocess.run(cmd, capture_output=True, text=True)
@@ -184,15 +201,26 @@ def build(force: bool = False, verbose: bool = False, lab: bool = False, variant
             raise RuntimeError(f"hipcc failed:\n{' '.join(cmd)}\n{r.stdout}\n{r.stderr}")
         if verbose and r.stderr.strip():
             print(r.stderr, file=sys.stderr)
+        with open(stamp, "w") as f:
+            f.write(key)
 
     with ThreadPoolExecutor(max_workers=4) as ex:
-        list(ex.map(compile_one, jobs))
-    compiled = {cmd[-1] for cmd, _, _ in jobs}
+        list(ex.map(lambda job: make(*job), jobs))
+    compiled = {o for o, _, _ in jobs}
     for l in libs:
         lib, objs = library(l, variant), objects(l, variant, extra)
-        if force or not os.path.exists(lib) or compiled.intersection(objs) or os.path.getmtime(lib) < max(os.path.getmtime(o) for o in objs):
+        cmd = [cc, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-Wl,-soname,libts2d.so", "-o", lib, *objs]
+        key = tool + "\n" + " ".join(cmd)
+        if force or compiled.intersection(objs) or not _fresh(lib, key, max(os.path.getmtime(o) for o in objs)):
             os.makedirs(os.path.dirname(lib), exist_ok=True)
-            run([cc, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", lib, *objs])
+            make(lib, cmd, key)
+    if variant is None:  # the package has no other binding, so a build against another torch must not be reused: torch's version is in the key
+        import torch
+        cmd = ext_command(cc)
+        key = f"{tool}\ntorch {torch.__version__}\n" + " ".join(cmd)
+        deps = (EXT_SRC, os.path.join(os.path.dirname(HERE), "include", "ts2d.h"), me)
+        if force or not _fresh(EXT, key, max(os.path.getmtime(d) for d in deps)):
+            make(EXT, cmd, key)
     return lib
 
 

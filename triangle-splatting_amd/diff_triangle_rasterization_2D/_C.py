@@ -1,5 +1,6 @@
 """`_C` of the drop-in `diff_triangle_rasterization_2D` package: the two entry points the reference exports
-through pybind (R2D/ext.cpp:6-8), here bound with ctypes onto the C ABI of libts2d.so (include/ts2d.h).
+through pybind (R2D/ext.cpp:6-8), here the torch extension bindings/_ts2d_torch_C.so (bindings/ts2d_torch_ext.cpp) over the C ABI
+of libts2d.so (include/ts2d.h); the rest of that ABI is bound with ctypes.
 
     rasterize_triangles(image_width, image_height, tan_fovx, tan_fovy, viewmatrix, projmatrix, campos,
                         sh_degree, gamma, scale_modifier, background_depth, background, vertex, shs, feature,
@@ -14,12 +15,13 @@ through pybind (R2D/ext.cpp:6-8), here bound with ctypes onto the C ABI of libts
 
 Same positional signatures, same argument checks and RuntimeErrors, same ownership (the callee allocates every
 output on vertex.device; the three uint8 buffers are opaque).  torch is used only for device memory (caching
-allocator) and the current stream.  There is NO CPU or eager fallback: if libts2d.so is missing or the tensors
-are not on a HIP device, this module raises.
+allocator) and the current stream.  There is NO CPU or eager fallback: if libts2d.so or the extension is missing or the
+tensors are not on a HIP device, this module raises.
 """
 from __future__ import annotations
 
 import ctypes as C
+import importlib.util
 import os
 
 import torch
@@ -38,35 +40,23 @@ if not os.path.exists(_LIB_PATH):
     )
 _lib = C.CDLL(_LIB_PATH)
 
-# ---- the compiled binding (bindings/ts2d_torch_ext.cpp -> bindings/_ts2d_torch_C.so) is the default since round 6 ---------------------------------
-# The two hot entry points below cost 0.3-0.4 ms of host time per forward + backward through ctypes (argument marshalling, ~15 torch allocations from
-# Python) -- what bounds every scene below ~100 k triangles.  The torch extension built by __graft_entry__.build() does the same
-# work in C++ on the same libts2d.so; it is used whenever it exists.  ctypes remains (a) the fallback when the extension was not built, (b) the path
-# of every measurement that swaps the library (TS2D_LIBRARY_PATH: the extension is linked against the product library), (c) selectable with
-# TS2D_BINDING=ctypes (tests/test_binding_gpu.py runs the package through both).  Everything that is not on the per-step path (profile hooks,
-# capacity hints, sh_grad_expand, forward_status) stays on ctypes: same library instance, loaded once.
-_ext = None
+# The two hot entry points go through the compiled extension: through ctypes, their argument marshalling and ~15 torch allocations from Python cost
+# 0.3-0.4 ms of host time per forward + backward, what bounds every scene below ~100 k triangles (profiles/r06_binding.txt).
+# The extension needs libts2d.so by name.  Every library build.py links carries that soname, so the dynamic loader meets the need with the library
+# loaded above -- the product's or the one TS2D_LIBRARY_PATH names -- and both bindings call one instance of it.
 _EXT_PATH = os.path.join(os.path.dirname(_HERE), "bindings", "_ts2d_torch_C.so")
-if os.environ.get("TS2D_BINDING", "") != "ctypes" and not os.environ.get("TS2D_LIBRARY_PATH") and os.path.exists(_EXT_PATH):
-    try:
-        import importlib.util as _ilu
-        _spec = _ilu.spec_from_file_location("_ts2d_torch_C", _EXT_PATH)
-        _mod = _ilu.module_from_spec(_spec)
-        _spec.loader.exec_module(_mod)
-        if hasattr(_mod, "rasterize_triangles_ex") and hasattr(_mod, "rasterize_triangles_backward_ex"):
-            _ext = _mod
-    except (ImportError, OSError) as _e:  # a stale build against another torch: fall back, loudly
-        import warnings
-        warnings.warn(f"{_EXT_PATH} could not be loaded ({_e}); using the ctypes binding (rebuild with bindings/build_torch_ext.py --force)")
-
-
-def binding() -> str:
-    """'compiled' or 'ctypes': which binding rasterize_triangles / rasterize_triangles_backward go through."""
-    return "compiled" if _ext is not None else "ctypes"
+try:
+    _spec = importlib.util.spec_from_file_location("_ts2d_torch_C", _EXT_PATH)
+    _ext = importlib.util.module_from_spec(_spec)
+    _spec.loader.exec_module(_ext)
+except (ImportError, OSError) as _e:
+    raise ImportError(f"{_EXT_PATH} could not be loaded ({_e}): build it with `python triangle-splatting_amd/build.py`") from _e
+if C.cast(C.CDLL("libts2d.so", mode=os.RTLD_NOLOAD).ts2d_version, C.c_void_p).value != C.cast(_lib.ts2d_version, C.c_void_p).value:
+    raise ImportError(f"{_LIB_PATH} lacks the soname libts2d.so, so the extension would call another copy of the library: rebuild it with "
+                      "`python triangle-splatting_amd/build.py`")
 
 
 FLAG_BACK_CULLING, FLAG_RICH_INFO, FLAG_DEBUG, FLAG_USE_SHS, FLAG_3D, FLAG_SH_FACTORED = 1, 2, 4, 8, 16, 32
-MAX_CHANNELS = 3
 
 _fp = C.c_void_p
 
@@ -179,11 +169,6 @@ def _ptr(t):
     return t.data_ptr()
 
 
-def _use_shs(shs: torch.Tensor, feature: torch.Tensor) -> bool:
-    # R2D/src/extension_interface.cu:44
-    return feature.dim() <= 1 or (feature.size(0) == 0 and shs.size(0) > 0)
-
-
 def _require_device(vertex: torch.Tensor):
     if not vertex.is_cuda:
         raise RuntimeError(
@@ -204,27 +189,6 @@ def _f32_or_raise(*tensors):
             raise RuntimeError("expected scalar type Float")  # what data_ptr<float>() raises in the reference
 
 
-def _marshal(W, H, tan_fovx, tan_fovy, viewmatrix, projmatrix, campos, sh_degree, gamma, scale_modifier,
-             background_depth, background, vertex, shs, feature, opacity, use_shs, Cn, M):
-    cam = _Camera(int(W), int(H), float(tan_fovx), float(tan_fovy), _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos))
-    # background_depth: a float like the reference's binding takes -- or a one-element float32 tensor on the device (what the reference's
-    # model computes every step, VanillaTS_model.py:623), handed to the kernels as a pointer: no device synchronisation for the conversion
-    bg_dev = None
-    if isinstance(background_depth, torch.Tensor):
-        if not (background_depth.is_cuda and background_depth.dtype == torch.float32 and background_depth.numel() == 1):
-            raise RuntimeError("background_depth must be a float or a one-element float32 tensor on the HIP device")
-        bg_dev, background_depth = background_depth.data_ptr(), 0.0
-    geom = _Geometry(int(vertex.size(0)), int(sh_degree), int(M), int(Cn), float(gamma), float(scale_modifier),
-                     float(background_depth), _ptr(background), _ptr(vertex), _ptr(shs) if use_shs else None,
-                     None if use_shs else _ptr(feature), _ptr(opacity), bg_dev)
-    return cam, geom
-
-
-def _state(geometryBuffer, binningBuffer, imageBuffer) -> _State:
-    return _State(_ptr(geometryBuffer), geometryBuffer.numel(), _ptr(binningBuffer), binningBuffer.numel(),
-                  _ptr(imageBuffer), imageBuffer.numel())
-
-
 def rasterize_triangles(image_width, image_height, tan_fovx, tan_fovy, viewmatrix, projmatrix, campos, sh_degree, gamma,
                         scale_modifier, background_depth, background, vertex, shs, feature, opacity, back_culling,
                         rich_info, debug, *, variant=2, instance_capacity=None):
@@ -232,97 +196,14 @@ def rasterize_triangles(image_width, image_height, tan_fovx, tan_fovy, viewmatri
     `instance_capacity` (an int > 0) selects the SYNC-FREE forward (ts2d_forward): the binning state is sized for that many tile
     instances, nothing is read back, and the returned `num_rendered` is the capacity (it only sizes the state for the backward
     call); whether the true count fitted is reported by `forward_status`.  Default None = the reference's sequence with its one
-    blocking read of num_rendered."""
-    if _ext is not None:
-        bg_t = background_depth if isinstance(background_depth, torch.Tensor) else None
-        return _ext.rasterize_triangles_ex(int(image_width), int(image_height), tan_fovx, tan_fovy, viewmatrix, projmatrix, campos, int(sh_degree), gamma,
-                                           scale_modifier, 0.0 if bg_t is not None else float(background_depth), background, vertex, shs, feature, opacity,
-                                           bool(back_culling), bool(rich_info), bool(debug), int(variant),
-                                           int(instance_capacity) if (instance_capacity is not None and vertex.size(0) > 0) else 0, bg_t)
-    P = vertex.size(0)
-    H, W = int(image_height), int(image_width)
-    use_shs = _use_shs(shs, feature)
-    Cn = 3 if use_shs else feature.size(1)
-    M = shs.size(1) if (shs.size(0) != 0 and shs.dim() >= 2) else 0
-
-    # R2D/src/extension_interface.cu:53-81
-    if vertex.dim() != 3 or vertex.size(1) != 3 or vertex.size(2) != 3:
-        raise RuntimeError("vertex must have dimensions (num_points, 3, 3)")
-    if not use_shs and feature.dim() != 2:
-        raise RuntimeError("feature must have dimensions (num_points, num_channels)")
-    if use_shs and shs.dim() != 3:
-        raise RuntimeError("shs must have dimensions (num_points, (1 + sh_degree) ** 2, 3)")
-    if Cn > MAX_CHANNELS:
-        raise RuntimeError("feature's num_channels can't be larger than MAX_CHANNELS")
-    if Cn != background.size(0):
-        raise RuntimeError("background must have the same number of channels as feature")
-    if gamma < 0.0:
-        raise RuntimeError("gamma must be larger than 0")
-    if variant == 3:  # R3D/src/extension_interface.cu:82-92 takes .contiguous() of every input instead of raising
-        viewmatrix, projmatrix, campos, background, vertex, shs, feature, opacity = (
-            t.contiguous() for t in (viewmatrix, projmatrix, campos, background, vertex, shs, feature, opacity))
-    else:
-        _contiguous_or_raise(viewmatrix, projmatrix, campos, background, vertex, shs, feature, opacity)
-    _require_device(vertex)
-    _f32_or_raise(viewmatrix, projmatrix, campos, background, vertex, shs if use_shs else None,
-                  None if use_shs else feature, opacity)
-
-    dev = vertex.device
-    f32 = dict(device=dev, dtype=torch.float32)
-    with torch.cuda.device(dev):  # OptionalCUDAGuard, extension_interface.cu:83
-        stream = torch.cuda.current_stream().cuda_stream
-        # every element of these is written by the library (ts2d.h), so no zero-fill pass is needed when P > 0
-        alloc = torch.zeros if P == 0 else torch.empty
-        out_feature = alloc((Cn, H, W), **f32)
-        radii = alloc((P,), device=dev, dtype=torch.int32)
-        if rich_info:
-            depth = alloc((H, W), **f32)
-            normal = alloc((3, H, W), **f32)
-            contrib_sum = alloc((P,), **f32)
-            contrib_max = alloc((P,), **f32)
-        else:
-            depth = torch.empty((0,), **f32)
-            normal = torch.empty((0,), **f32)
-            contrib_sum = torch.empty((0,), **f32)
-            contrib_max = torch.empty((0,), **f32)
-        u8 = dict(device=dev, dtype=torch.uint8)
-        if P == 0:  # extension_interface.cu:130: zero images, empty state
-            return (0, out_feature, radii, depth, normal, contrib_sum, contrib_max, torch.empty((0,), **u8),
-                    torch.empty((0,), **u8), torch.empty((0,), **u8))
-
-        flags = ((FLAG_BACK_CULLING if back_culling else 0) | (FLAG_RICH_INFO if rich_info else 0) |
-                 (FLAG_DEBUG if debug else 0) | (FLAG_USE_SHS if use_shs else 0) | (FLAG_3D if variant == 3 else 0))
-        cam, geom = _marshal(W, H, tan_fovx, tan_fovy, viewmatrix, projmatrix, campos, sh_degree, gamma, scale_modifier,
-                             background_depth, background, vertex, shs, feature, opacity, use_shs, Cn, M)
-        geometryBuffer = torch.empty((_lib.ts2d_geometry_state_bytes(P),), **u8)
-        imageBuffer = torch.empty((_lib.ts2d_image_state_bytes(W, H),), **u8)
-        if instance_capacity is not None:
-            cap = int(instance_capacity)
-            binningBuffer = torch.empty((_lib.ts2d_binning_state_bytes(cap, W, H),), **u8)
-            st = _state(geometryBuffer, binningBuffer, imageBuffer)
-            out = _ForwardOut(_ptr(out_feature), _ptr(depth), _ptr(normal), _ptr(contrib_sum), _ptr(contrib_max))
-            _check(_lib.ts2d_forward(C.byref(cam), C.byref(geom), flags, _ptr(radii), C.byref(st), cap, C.byref(out), stream),
-                   "rasterize_triangles")
-            return (cap, out_feature, radii, depth, normal, contrib_sum, contrib_max, geometryBuffer, binningBuffer, imageBuffer)
-        # The reference's sequence (num_rendered comes back to the host, rasterizer.cu:189-191) without its stall: the binning buffer is
-        # sized from what recent forwards of this image size rendered (x 1.25), EVERYTHING is queued for that capacity, and only then does
-        # the host wait for the exact count, which the GPU publishes ~0.1 ms into the forward (ts2d_forward_speculative).  Without a
-        # history (first call) or when the guess was too small (nothing was emitted then), the second half runs again with the exact size.
-        cap_guess = int(_lib.ts2d_instance_capacity_hint(P, W, H, flags))
-        binningBuffer = torch.empty((_lib.ts2d_binning_state_bytes(cap_guess, W, H) if cap_guess > 0 else 0,), **u8)
-        st = _state(geometryBuffer, binningBuffer, imageBuffer)
-        out = _ForwardOut(_ptr(out_feature), _ptr(depth), _ptr(normal), _ptr(contrib_sum), _ptr(contrib_max))
-        n = C.c_int64(0)
-        _check(_lib.ts2d_forward_speculative(C.byref(cam), C.byref(geom), flags, _ptr(radii), C.byref(st), C.byref(out), C.byref(n), stream),
-               "rasterize_triangles")
-        num_rendered = int(n.value)
-        if cap_guess <= 0 or num_rendered > _lib.ts2d_binning_capacity(binningBuffer.numel(), W, H):
-            binningBuffer = torch.empty((_lib.ts2d_binning_state_bytes(num_rendered, W, H),), **u8)
-            st = _state(geometryBuffer, binningBuffer, imageBuffer)
-            _check(_lib.ts2d_forward_render(C.byref(cam), C.byref(geom), flags, num_rendered, C.byref(st), C.byref(out), stream),
-                   "rasterize_triangles")
-    return (num_rendered, out_feature, radii, depth, normal, contrib_sum, contrib_max, geometryBuffer, binningBuffer,
-            imageBuffer)
+    blocking read of num_rendered.
+    `background_depth`: a float like the reference's binding takes, or a one-element float32 tensor on the device (what the reference's
+    model computes every step, VanillaTS_model.py:623), handed to the kernels as a pointer: no device synchronisation for the conversion."""
+    bg_t = background_depth if isinstance(background_depth, torch.Tensor) else None
+    return _ext.rasterize_triangles_ex(int(image_width), int(image_height), tan_fovx, tan_fovy, viewmatrix, projmatrix, campos, int(sh_degree), gamma,
+                                       scale_modifier, 0.0 if bg_t is not None else float(background_depth), background, vertex, shs, feature, opacity,
+                                       bool(back_culling), bool(rich_info), bool(debug), int(variant),
+                                       int(instance_capacity) if (instance_capacity is not None and vertex.size(0) > 0) else 0, bg_t)
 
 
 def rasterize_triangles_backward(tan_fovx, tan_fovy, viewmatrix, projmatrix, campos, sh_degree, gamma, scale_modifier,
@@ -335,76 +216,14 @@ def rasterize_triangles_backward(tan_fovx, tan_fovy, viewmatrix, projmatrix, cam
     "color" = dL_dshs (P,M,3) or dL_dfeature (P,C)) that the library writes instead of fresh allocations (parallel.GradBucket).
     `range_events`: a list of K torch.cuda.Event (each recorded at least once before): the per-triangle kernel runs as K launches over
     consecutive triangle ranges of `backward_range_rows(P, K)` rows and event k is recorded behind range k (ts2d_backward_ranged)."""
-    if _ext is not None:
-        bg_t = background_depth if isinstance(background_depth, torch.Tensor) else None
-        o = out or {}
-        return _ext.rasterize_triangles_backward_ex(tan_fovx, tan_fovy, viewmatrix, projmatrix, campos, int(sh_degree), gamma, scale_modifier,
-                                                    0.0 if bg_t is not None else float(background_depth), background, vertex, shs, feature, opacity,
-                                                    int(num_rendered), radii, geometryBuffer, binningBuffer, imageBuffer, dL_dout_feature, dL_dout_depth,
-                                                    dL_dout_normal, bool(rich_info), bool(debug), int(variant), bool(sh_factored), o.get("vertex"),
-                                                    o.get("center2D"), o.get("color"), o.get("opacity"), bg_t,
-                                                    [int(e.cuda_event) for e in range_events] if range_events else [])
-    P = vertex.size(0)
-    H, W = dL_dout_feature.size(1), dL_dout_feature.size(2)  # extension_interface.cu:182-183
-    use_shs = _use_shs(shs, feature)
-    Cn = 3 if use_shs else feature.size(1)
-    M = shs.size(1) if (shs.size(0) != 0 and shs.dim() >= 2) else 0
-    if variant == 3:  # R3D/src/extension_interface.cu:186-206: .contiguous() instead of the 2D module's error
-        (viewmatrix, projmatrix, campos, background, vertex, shs, feature, opacity, radii, dL_dout_feature, dL_dout_depth,
-         dL_dout_normal) = (t.contiguous() for t in (viewmatrix, projmatrix, campos, background, vertex, shs, feature, opacity,
-                                                     radii, dL_dout_feature, dL_dout_depth, dL_dout_normal))
-    _contiguous_or_raise(viewmatrix, projmatrix, campos, background, vertex, shs, feature, opacity, radii, geometryBuffer,
-                         binningBuffer, imageBuffer, dL_dout_feature, dL_dout_depth, dL_dout_normal)
-    _require_device(vertex)
-    _f32_or_raise(dL_dout_feature, dL_dout_depth, dL_dout_normal)
-
-    dev = vertex.device
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        alloc = torch.zeros if P == 0 else torch.empty  # every element is written by the library when P > 0
-        opts = dict(device=dev, dtype=vertex.dtype)
-        out = out or {}
-
-        def placed(name, shape, fallback):
-            t = out.get(name)
-            if t is None:
-                return fallback(shape, **opts)
-            if tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.dtype != torch.float32 or t.device != dev:
-                raise RuntimeError(f"preallocated gradient output '{name}' must be a contiguous float32 {tuple(shape)} tensor on {dev}")
-            if P == 0:
-                t.zero_()
-            return t
-
-        dL_dvertex = placed("vertex", (P, 3, 3), alloc)
-        dL_dcenter2D = placed("center2D", (P, 2), alloc)
-        sh_factored = bool(sh_factored and use_shs)
-        if sh_factored:
-            dL_dshs = None
-        else:
-            dL_dshs = placed("color", (P, M, 3), alloc) if use_shs else torch.zeros((P, M, 3), **opts)
-        dL_dfeature = alloc((P, Cn), **opts) if use_shs else placed("color", (P, Cn), alloc)
-        dL_dopacity = placed("opacity", (P, 1), alloc)
-        if P == 0:
-            return dL_dvertex, dL_dcenter2D, dL_dshs, dL_dfeature, dL_dopacity
-        flags = ((FLAG_RICH_INFO if rich_info else 0) | (FLAG_DEBUG if debug else 0) | (FLAG_USE_SHS if use_shs else 0) |
-                 (FLAG_3D if variant == 3 else 0) | (FLAG_SH_FACTORED if sh_factored else 0))
-        cam, geom = _marshal(W, H, tan_fovx, tan_fovy, viewmatrix, projmatrix, campos, sh_degree, gamma, scale_modifier,
-                             background_depth, background, vertex, shs, feature, opacity, use_shs, Cn, M)
-        st = _state(geometryBuffer, binningBuffer, imageBuffer)
-        loss = _LossGrads(_ptr(dL_dout_feature), _ptr(dL_dout_depth) if rich_info else None,
-                          _ptr(dL_dout_normal) if rich_info else None)
-        scratch = torch.empty((_lib.ts2d_backward_scratch_bytes(P),), device=dev, dtype=torch.uint8)
-        scratch_bytes = scratch.numel()
-        out = _BackwardOut(_ptr(dL_dvertex), _ptr(dL_dcenter2D), _ptr(dL_dshs), _ptr(dL_dfeature), _ptr(dL_dopacity))
-        if range_events:
-            handles = (_fp * len(range_events))(*[int(e.cuda_event) for e in range_events])
-            _check(_lib.ts2d_backward_ranged(C.byref(cam), C.byref(geom), flags, int(num_rendered), _ptr(radii), C.byref(st), C.byref(loss), _ptr(scratch),
-                                             scratch_bytes, C.byref(out), len(range_events), handles, stream), "rasterize_triangles_backward")
-        else:
-            _check(_lib.ts2d_backward(C.byref(cam), C.byref(geom), flags, int(num_rendered), _ptr(radii), C.byref(st),
-                                      C.byref(loss), _ptr(scratch), scratch_bytes, C.byref(out), stream),
-                   "rasterize_triangles_backward")
-    return dL_dvertex, dL_dcenter2D, dL_dshs, dL_dfeature, dL_dopacity
+    bg_t = background_depth if isinstance(background_depth, torch.Tensor) else None
+    o = out or {}
+    return _ext.rasterize_triangles_backward_ex(tan_fovx, tan_fovy, viewmatrix, projmatrix, campos, int(sh_degree), gamma, scale_modifier,
+                                                0.0 if bg_t is not None else float(background_depth), background, vertex, shs, feature, opacity,
+                                                int(num_rendered), radii, geometryBuffer, binningBuffer, imageBuffer, dL_dout_feature, dL_dout_depth,
+                                                dL_dout_normal, bool(rich_info), bool(debug), int(variant), bool(sh_factored), o.get("vertex"),
+                                                o.get("center2D"), o.get("color"), o.get("opacity"), bg_t,
+                                                [int(e.cuda_event) for e in range_events] if range_events else [])
 
 
 def backward_range_rows(P: int, num_ranges: int) -> int:

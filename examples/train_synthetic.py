@@ -9,10 +9,13 @@ trainer + model use their own (src/diff_recon/trainers/VanillaTS_trainer.py:60-1
 
 `views_per_step` views are rendered per optimisation step and their gradients summed, which is what one step of image-parallel
 training computes across ranks (BASELINE.json configs[3]: 8 views per step over 8 GPUs; here the views run one after the other
-on one GPU -- the cross-rank exchange itself is covered by tests/test_multigpu_gpu.py and bench.py --gpus N).
+on one GPU).  With --world N the same step runs image-parallel instead: N processes, each rendering views_per_step / N of the step's views,
+gradients and statistics exchanged, the model replicated (diff_recon_hip.ImageParallelLoop), and a ReplicaGuard that proves every
+--check-every iterations, and after every structural update, that the replicas still hold the same bits.
 
 A "ground truth" is rendered from a hidden set of triangles from several cameras; a perturbed, sparser copy is optimised.
     python examples/train_synthetic.py [--rasterizer 2D|3D] [--iters 400] [--triangles 20000] [--views 4]
+    python examples/train_synthetic.py --world 2 [--exchange dense|factored_sh] [--check-every 50]
 """
 import argparse
 import math
@@ -94,19 +97,17 @@ class SyntheticModel(DensificationStats):
         self.gamma_scheduler = exponential_scheduler(1.0, 4.0, iters - q)  # the reference's configs go 1 -> 50 over 30 k iterations
         self.log = []
 
-    def model_update(self, iteration, render_pkgs):
-        """VanillaTSModel.model_update (:567-581), same order (diff_recon_hip.model_update.run_model_update)."""
-        for name, res in D.run_model_update(self, iteration, render_pkgs):
+    def model_update(self, iteration, render_pkgs, **kw):
+        """VanillaTSModel.model_update (:567-581), same order (diff_recon_hip.model_update.run_model_update).  Returns the rules that fired."""
+        fired = D.run_model_update(self, iteration, render_pkgs, **kw)
+        for name, res in fired:
             self.log.append((iteration, name, res, self._vertex.shape[0]))
+        return fired
 
 
-def train(rasterizer="2D", iters=200, triangles=20000, width=256, height=192, seed=0, views=2, views_per_step=2, log=print, updates=True,
-          w_geometry=0.0, single_sh=False, init_from_pcd=False, factored_sh=False):
-    """w_geometry > 0 adds the depth / normal consistency term of the *_VanillaTS_mesh.yaml configurations (geometry_loss: w_geometry 0.05,
-    scale_factor 0.5, from iteration start_iter on; VanillaTS_trainer.py:30-31,64-65,84,111) -- the producer of dL_dout_depth / dL_dout_normal.
-    factored_sh: the backward passes hand the optimizer (dL_dRGB, camera centre) per view instead of writing the dense dL_dshs, and FusedAdam
-    steps the colour parameters from those (include/ts_optim.h: tso_adam_step_sh_factored) -- the same numbers, 12 M bytes per triangle less
-    written and as many less read."""
+def _setup(rasterizer, iters, triangles, width, height, seed, views, w_geometry, single_sh, init_from_pcd):
+    """Scene, cameras, hidden targets and the model to optimise, on the current HIP device: the same numbers in every process that calls it with
+    the same arguments (every draw comes from a seeded generator), which is what makes the ranks of --world N start as replicas."""
     dev = torch.device("cuda")
     geometry_loss = DepthNormalLoss(scale_factor=0.5) if w_geometry > 0 else None
     g_start_iter = iters // 2  # the reference's configs start it at half of the schedule (15 000 of 30 000)
@@ -132,6 +133,25 @@ def train(rasterizer="2D", iters=200, triangles=20000, width=256, height=192, se
     else:
         m = SyntheticModel(vertex, torch.full((n0, 1, 3), 0.5, device=dev), torch.zeros((n0, (D_sh + 1) ** 2 - 1, 3), device=dev),
                            torch.zeros((n0, 1), device=dev), iters, D_sh, single_sh=single_sh)
+    return dev, m, cams, gts, kw, geometry_loss, g_start_iter
+
+
+def train(rasterizer="2D", iters=200, triangles=20000, width=256, height=192, seed=0, views=2, views_per_step=2, log=print, updates=True,
+          w_geometry=0.0, single_sh=False, init_from_pcd=False, factored_sh=False, world=None, exchange="dense", check_every=50, on_iteration=None,
+          collect=False):
+    """w_geometry > 0 adds the depth / normal consistency term of the *_VanillaTS_mesh.yaml configurations (geometry_loss: w_geometry 0.05,
+    scale_factor 0.5, from iteration start_iter on; VanillaTS_trainer.py:30-31,64-65,84,111) -- the producer of dL_dout_depth / dL_dout_normal.
+    factored_sh: the backward passes hand the optimizer (dL_dRGB, camera centre) per view instead of writing the dense dL_dshs, and FusedAdam
+    steps the colour parameters from those (include/ts_optim.h: tso_adam_step_sh_factored) -- the same numbers, 12 M bytes per triangle less
+    written and as many less read.
+    world = N: image-parallel over N fresh processes (train_ranks below; exchange, check_every, on_iteration and collect belong to it).  The
+    default, None, is the one-process loop."""
+    if world is not None:
+        cfg = dict(rasterizer=rasterizer, iters=iters, triangles=triangles, width=width, height=height, seed=seed, views=views,
+                   views_per_step=views_per_step, updates=updates, w_geometry=w_geometry, single_sh=single_sh, init_from_pcd=init_from_pcd)
+        return train_ranks(world, cfg, exchange=exchange, check_every=check_every, on_iteration=on_iteration, collect=collect, log=log)
+    dev, m, cams, gts, kw, geometry_loss, g_start_iter = _setup(rasterizer, iters, triangles, width, height, seed, views, w_geometry, single_sh,
+                                                                init_from_pcd)
     losses, t0 = [], time.perf_counter()
     for it in range(1, iters + 1):
         m.optimizer.zero_grad(set_to_none=True)
@@ -167,6 +187,129 @@ def train(rasterizer="2D", iters=200, triangles=20000, width=256, height=192, se
     return [float(x) for x in torch.stack(losses).cpu()], m, sec
 
 
+# ---- image-parallel: the same training over N processes (diff_recon_hip/multirank.py) ------------------------------------------------------
+def _rank_state(m):
+    """The replicated state of a rank as host arrays (collect=True: what the tests compare between the ranks, bit for bit)."""
+    return {k: v.detach().cpu().numpy() for k, v in D.replicated_state(m).items()}
+
+
+def _train_rank(rank, world, cfg, exchange, check_every, on_iteration, collect, log):
+    """What one rank runs: train()'s loop with the step handed to ImageParallelLoop.  The process group is initialised by the caller."""
+    iters, views, views_per_step, updates, w_geometry = cfg["iters"], cfg["views"], cfg["views_per_step"], cfg["updates"], cfg["w_geometry"]
+    dev, m, cams, gts, kw, geometry_loss, g_start_iter = _setup(cfg["rasterizer"], iters, cfg["triangles"], cfg["width"], cfg["height"], cfg["seed"],
+                                                                views, w_geometry, cfg["single_sh"], cfg["init_from_pcd"])
+    it_now = [0]
+
+    def render_and_loss(v):
+        colour = dict(shs=m._shs) if m.single_sh else {}
+        pkg = render_view(cams[v], m._vertex, None if m.single_sh else m._f_dc, None if m.single_sh else m._f_rest, m._opacity, is_training=True,
+                          gamma=m.gamma, active_sh_degree=m.active_sh_degree, **colour, **kw)
+        loss = photometric_loss(pkg["render"], gts[v], 0.8, 0.2)
+        if geometry_loss is not None and it_now[0] > g_start_iter:
+            loss = loss + w_geometry * geometry_loss(pkg["depth"], pkg["normal"], cams[v].tan_fovx, cams[v].tan_fovy)
+        return loss, pkg
+
+    def statistics_only(iteration, pkgs):  # train(updates=False): the statistics of all views, no rule
+        for pkg in pkgs:
+            m.update(pkg, all_views=True)
+        return []
+
+    guard = D.ReplicaGuard(every=check_every)
+    loop = D.ImageParallelLoop(m, render_and_loss, exchange=exchange, guard=guard,
+                               model_update=(lambda iteration, pkgs: m.model_update(iteration, pkgs, all_views=True)) if updates else statistics_only)
+    losses, rows, t0 = [], [], time.perf_counter()
+    for it in range(1, iters + 1):
+        it_now[0] = it
+        total = loop.step(it, [(it * views_per_step + k) % views for k in range(views_per_step)])
+        losses.append(total / views_per_step)
+        rows.append(m._vertex.shape[0])
+        if on_iteration is not None:
+            on_iteration(it, m, rank)
+        if log and rank == 0 and (it % 50 == 0 or it == 1 or it == iters):
+            log(f"iter {it:4d}  loss {float(losses[-1]):.5f}  triangles {m._vertex.shape[0]}  gamma {m.gamma:.2f}  sh {m.active_sh_degree}  ranks {world}")
+    torch.cuda.synchronize()
+    sec = (time.perf_counter() - t0) / iters
+    out = dict(losses=[float(x) for x in torch.stack(losses).cpu()], log=list(m.log), sec=sec, rows=rows, gamma=m.gamma,
+               active_sh_degree=m.active_sh_degree, guard_checks=guard.checks)
+    if collect:
+        out["state"] = _rank_state(m)
+    return out
+
+
+def _rank_main(rank, world, port, backend, cfg, exchange, check_every, on_iteration, collect, verbose, q):
+    import torch.distributed as dist
+    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
+    torch.cuda.set_device(rank % torch.cuda.device_count())
+    dist.init_process_group(backend, rank=rank, world_size=world)
+    try:
+        try:
+            q.put((rank, _train_rank(rank, world, cfg, exchange, check_every, on_iteration, collect, print if verbose else None)))
+        except D.ReplicaDivergence as e:  # every rank raises it: each reports what it saw and ends in an orderly way
+            q.put((rank, dict(divergence=(e.iteration, e.names, e.ranks))))
+    finally:
+        dist.destroy_process_group()
+
+
+def train_ranks(world, cfg, exchange="dense", check_every=50, on_iteration=None, collect=False, log=print, timeout=1800.0):
+    """train(world=N): N fresh child processes (spawn: never a fork or an exec of a process that has opened the GPU), rank r on GPU
+    r % device_count; RCCL ("nccl") when every rank has a GPU of its own, gloo otherwise (several ranks sharing a card: a functional run).
+    Returns (losses, summary, seconds per iteration) of rank 0; summary.ranks holds every rank's report (collect=True: with its final state as
+    host arrays).  A ReplicaDivergence of the ranks is raised here again, with every rank's report in `.reports`."""
+    import multiprocessing
+    import queue as queue_mod
+    import socket
+    if exchange not in ("dense", "factored_sh"):
+        raise ValueError(f"exchange must be 'dense' or 'factored_sh', not {exchange!r}")
+    if world < 1 or cfg["views_per_step"] % world:
+        raise ValueError(f"views_per_step ({cfg['views_per_step']}) must be a multiple of the number of ranks ({world})")
+    backend = "nccl" if torch.cuda.device_count() >= world else "gloo"  # device_count() opens no device
+    with socket.socket() as sock:
+        sock.bind(("127.0.0.1", 0))
+        port = sock.getsockname()[1]
+    ctx = multiprocessing.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_rank_main, args=(r, world, port, backend, cfg, exchange, check_every, on_iteration, collect, log is print, q))
+             for r in range(world)]
+    for p in procs:
+        p.start()
+    reports, deadline = {}, time.monotonic() + timeout
+    try:
+        while len(reports) < world:  # the reports are read BEFORE the join: a child cannot end while its report sits in the pipe
+            try:
+                rank, rep = q.get(timeout=1.0)
+                reports[rank] = rep
+            except queue_mod.Empty:
+                dead = [(r, p.exitcode) for r, p in enumerate(procs) if p.exitcode not in (None, 0)]
+                if dead:
+                    raise RuntimeError(f"rank(s) ended abnormally (rank, exit code): {dead}")
+                if all(p.exitcode == 0 for p in procs) and q.empty():
+                    raise RuntimeError(f"ranks ended without a report: got {sorted(reports)} of {world}")
+                if time.monotonic() > deadline:
+                    raise RuntimeError(f"no report from every rank within {timeout:.0f} s")
+        for p in procs:
+            p.join(120)
+    finally:
+        for p in procs:  # first failure: nothing is left running
+            if p.is_alive():
+                p.terminate()
+                p.join(30)
+    codes = [p.exitcode for p in procs]
+    if any(c != 0 for c in codes):
+        raise RuntimeError(f"exit codes of the ranks: {codes}")
+    ranks = [reports[r] for r in range(world)]
+    diverged = {r: rep["divergence"] for r, rep in enumerate(ranks) if "divergence" in rep}
+    if diverged:
+        err = D.ReplicaDivergence(*diverged[min(diverged)])
+        err.reports, err.exitcodes = diverged, codes
+        raise err
+    head = ranks[0]
+    summary = NS(log=head["log"], ranks=ranks, world=world, backend=backend, exchange=exchange, gamma=head["gamma"],
+                 active_sh_degree=head["active_sh_degree"], num_triangles=head["rows"][-1] if head["rows"] else None)
+    if log and log is not print:
+        log(f"{world} ranks over {backend}: {head['guard_checks']} guard checks passed")
+    return head["losses"], summary, head["sec"]
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--rasterizer", default="2D", choices=["2D", "3D"])
@@ -177,9 +320,14 @@ if __name__ == "__main__":
     ap.add_argument("--init-from-pcd", action="store_true", help="start from diff_recon_hip.create_from_pcd (point cloud -> distCUDA2 -> equilateral triangles) like the reference's trainer")
     ap.add_argument("--factored-sh", action="store_true", help="Adam on the SH coefficients from the factored gradient (dL_dRGB per view) instead of the dense dL_dshs")
     ap.add_argument("--w-geometry", type=float, default=0.0, help="weight of the depth / normal consistency loss (0.05 in the *_VanillaTS_mesh configs)")
+    ap.add_argument("--world", type=int, default=None, help="image-parallel over this many processes (rank r on GPU r %% device_count); views per step = 2, or N when N > 2")
+    ap.add_argument("--exchange", default="dense", choices=["dense", "factored_sh"], help="--world: how the colour gradients travel between the ranks")
+    ap.add_argument("--check-every", type=int, default=50, help="--world: iterations between two replica-guard checks (one is forced after every structural update)")
     a = ap.parse_args()
+    parallel = {} if a.world is None else dict(world=a.world, exchange=a.exchange, check_every=a.check_every,
+                                               views_per_step=2 if 2 % a.world == 0 else a.world)
     losses, m, sec = train(a.rasterizer, a.iters, a.triangles, views=a.views, w_geometry=a.w_geometry, single_sh=a.single_sh_tensor, init_from_pcd=a.init_from_pcd,
-                           factored_sh=a.factored_sh)
+                           factored_sh=a.factored_sh, **parallel)
     for row in m.log:
         print("  update", row)
     print(f"{a.rasterizer}: loss {losses[0]:.5f} -> {losses[-1]:.5f} in {a.iters} iterations, {sec * 1e3:.2f} ms/iteration (incl. Python)")

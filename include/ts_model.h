@@ -13,8 +13,9 @@
  *     max_radii2D[visible]   = max(max_radii2D[visible], radii[visible])                (:363)
  * Eager torch turns each line into nonzero + gather + op + scatter (with a host synchronisation per mask); here it is one
  * HBM-bound pass.  `num_views` > 1 applies the update for several views of the same step in one launch (image-parallel
- * training: ranks all-gather the four per-view arrays; every operation is order independent, so all ranks end up with
- * identical state).  All pointers are device pointers. */
+ * training: ranks all-gather the four per-view arrays; every rank applies the same views in the same order, so all ranks end up with
+ * identical state, and the views are accumulated one after the other from the state's value, so the result is bit for bit that of
+ * num_views launches of one view each, i.e. of the one-process loop).  All pointers are device pointers. */
 #ifndef TS_MODEL_H
 #define TS_MODEL_H
 
@@ -64,6 +65,19 @@ int tsm_opacity_reset(int32_t P, float reset_value, float *opacity, float *exp_a
  * (camera_center: 3 floats in DEVICE memory; out: 1 float in device memory; 0 for n_vertices == 0; NaN when a distance is NaN, like torch's max).  One read of the vertices instead of
  * torch's subtract / norm / max. */
 int tsm_max_vertex_distance(int32_t n_vertices, const float *vertex, const float *camera_center, float *out, void *stream);
+
+/* ---- replica guard of image-parallel training ---------------------------------------------------------------------------------------
+ * Order-independent 64-bit digests of `num_segments` device buffers in ONE launch, so that ranks can prove with one small collective that
+ * their replicated state is still bit-identical.  Segment s is num_words[s] 32-bit words at segments[s] (4-byte aligned; 16-byte aligned
+ * bases take the 16-byte load path).  Bit patterns count: -0.0 differs from 0.0, NaN payloads are distinguished.  With the words paired
+ * up, x_j = w[2j] | (uint64)w[2j+1] << 32 (a missing last high half is 0),
+ *     digests[s] = sum_j mix64(x_j ^ (j + 1) * 0x9E3779B97F4A7C15)   mod 2^64,
+ * mix64 = the splitmix64 finaliser (z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31).  The sum
+ * is over integers: the result does not depend on block shape, grid size or atomic order.  An empty segment has digest 0.
+ * `segments` and `num_words` are HOST arrays, read before the call returns; `digests` is device memory (num_segments values), zeroed on
+ * `stream` in front of the launch.  num_segments > TSM_DIGEST_MAX_SEGMENTS or num_words[s] >= 2^32 is an error, nothing is launched. */
+#define TSM_DIGEST_MAX_SEGMENTS 32
+int tsm_state_digest(int32_t num_segments, const void *const *segments, const uint64_t *num_words, uint64_t *digests, void *stream);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,7 @@ step alone at the same size (forward + backward with fixed upstream gradients = 
 this library outside the rasterizer its average duration, its algorithmic bytes and the fraction of the 8 TB/s HBM roofline that makes.
 
     python tools/bench_train_step.py --config headline|mesh93k|mesh93k_g50|lego300k [--iters 40]
+    python tools/bench_train_step.py --config headline --digest      # the replica guard's state digest beside the FusedAdam step, same process
 Algorithmic bytes (f32 elements x 4): photometric_fwd 5 n (2 images in, 3 derivative maps out), photometric_bwd 6 n (5 in, 1 out), n = C h w;
 downsample_fwd / _bwd (s^2 + 1) per OUTPUT element; adam_step 28 per parameter float (param, grad, 2 moments in; param, 2 moments out);
 depth_normal_fwd 16 per pixel (depth + normal in -- a lower bound: the kernels keep low-resolution intermediates), depth_normal_bwd 32 per pixel
@@ -65,9 +66,13 @@ def main():
     ap.add_argument("--mimic-dense-alloc", action="store_true", help="experiment: the factored iteration with the dense iteration's allocation pattern "
                     "(a (P, M, 3) tensor allocated and dropped where the backward would have allocated dL_dshs)")
     ap.add_argument("--hold-mb", type=int, default=0, help="experiment: a tensor of this many MB allocated before anything else and kept")
+    ap.add_argument("--digest", action="store_true", help="time ONLY the state digest of the replica guard (diff_recon_hip.state_digest over parameters, both "
+                    "Adam moments and the six statistics arrays) and the dense FusedAdam step over the same parameters, in this one process")
     a = ap.parse_args()
     c = NS(**CONFIGS[a.config])
     dev = torch.device("cuda")
+    if a.digest:
+        return digest_vs_adam(c, a.config, dev, a.iters)
     W, H = c.w * c.up, c.h * c.up  # the rasterizer's resolution
     hold = torch.empty(a.hold_mb << 20, dtype=torch.uint8, device=dev) if a.hold_mb else None  # noqa: F841
     s = synthetic.scene(c.P, W, H, c.D, seed=42)
@@ -203,6 +208,52 @@ def main():
     except Exception as e:
         emit(None, repr(e)[:200])
     gc.enable()
+
+
+def digest_vs_adam(c, name, dev, iters):
+    """The cost target of the replica guard: one digest of the model state (one launch, reads every array once) against one dense FusedAdam step
+    over the same parameters (reads four arrays of that size, writes three).  Both in this process, interleaved in rounds, HIP events around
+    `iters` back-to-back calls each; the median round is reported."""
+    M = (c.D + 1) ** 2
+    g = torch.Generator(device="cuda").manual_seed(2)
+    shapes = {"vertex": (c.P, 3, 3), "opacity": (c.P, 1), "shs": (c.P, M, 3)}
+    params = {k: torch.nn.Parameter(torch.randn(sh, device=dev, generator=g)) for k, sh in shapes.items()}
+    opt = D.FusedAdam([{"params": [p], "lr": 0.0, "name": k} for k, p in params.items()], lr=0.0, eps=1e-15)
+    for p in params.values():
+        p.grad = torch.randn(p.shape, device=dev, generator=g)
+    model = D.DensificationStats(c.P, dev)
+    model.optimizer = opt
+    opt.step()  # creates the moments
+    state = D.replicated_state(model)
+    assert len(state) == 3 * len(params) + 6, sorted(state)
+    nparam = sum(p.numel() for p in params.values())
+    digest_bytes = sum(t.numel() * t.element_size() for t in state.values())
+    adam_bytes = 28 * nparam
+    keep = []
+
+    def batch(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            keep.append(fn())
+        e1.record()
+        e1.synchronize()
+        keep.clear()
+        return e0.elapsed_time(e1) / iters
+
+    do_digest, do_adam = (lambda: D.state_digest(state)), (lambda: opt.step())
+    for _ in range(3):  # warm: clocks, allocator, code objects
+        batch(do_digest), batch(do_adam)
+    rounds = [(batch(do_digest), batch(do_adam)) for _ in range(7)]
+    dg, ad = sorted(r[0] for r in rounds)[3], sorted(r[1] for r in rounds)[3]
+    first, again = D.state_digest(state).cpu(), D.state_digest(state).cpu()
+    line = {"config": name, "workload": f"model state of P={c.P}, SH degree {c.D}: {len(params)} parameters + 2 Adam moments each + 6 statistics arrays = {len(state)} segments",
+            "calls_per_round": iters, "rounds": len(rounds), "state_digest_ms": round(dg, 4), "adam_step_ms": round(ad, 4), "digest_over_adam": round(dg / ad, 4),
+            "target_met": bool(dg <= ad), "digest_bytes": int(digest_bytes), "digest_GBps": round(digest_bytes / (dg * 1e-3) / 1e9, 1),
+            "digest_hbm_frac": round(digest_bytes / (dg * 1e-3) / 1e9 / HBM, 4), "adam_algorithmic_bytes": int(adam_bytes),
+            "adam_GBps": round(adam_bytes / (ad * 1e-3) / 1e9, 1), "rounds_ms": [[round(x, 4), round(y, 4)] for x, y in rounds],
+            "repeatable": bool(torch.equal(first, again))}
+    print(json.dumps(line), flush=True)
 
 
 def _last_num_rendered(pkg):

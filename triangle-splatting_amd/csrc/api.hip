@@ -1153,6 +1153,24 @@ int tsm_max_vertex_distance(int32_t n_vertices, const float *vertex, const float
     return TS2D_OK;
 }
 
+int tsm_state_digest(int32_t num_segments, const void *const *segments, const uint64_t *num_words, uint64_t *digests, void *stream)
+{
+    if (num_segments < 0 || num_segments > TSM_DIGEST_MAX_SEGMENTS)
+        return fail(TS2D_ERR_INVALID, "num_segments must be in 0..%d (got %d)", TSM_DIGEST_MAX_SEGMENTS, (int)num_segments);
+    if (num_segments == 0) return TS2D_OK;
+    if (!segments || !num_words || !digests) return fail(TS2D_ERR_INVALID, "null pointer");
+    for (int i = 0; i < num_segments; i++)
+    {
+        if (num_words[i] >= (1ull << 32)) return fail(TS2D_ERR_INVALID, "segment %d: num_words must be below 2^32", i);
+        if (num_words[i] && !segments[i]) return fail(TS2D_ERR_INVALID, "segment %d: null pointer", i);
+        if (num_words[i] && ((uintptr_t)segments[i] & 3)) return fail(TS2D_ERR_INVALID, "segment %d: not aligned to 4 bytes", i);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps("state_digest", s);
+    TS_HIP(ts_model_state_digest(num_segments, segments, num_words, digests, s));
+    return TS2D_OK;
+}
+
 #ifdef TS2D_LAB // csrc/ts2d_lab.h: diagnostics and comparators that only tools/bin/libts2d_lab.so carries
 int ts2d_debug_read_state(const ts2d_state *state, int32_t P, int64_t N, int32_t W, int32_t H, int32_t field, void *dst,
                           size_t dst_bytes, void *stream)

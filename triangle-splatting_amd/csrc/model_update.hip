@@ -25,7 +25,9 @@ __global__ void __launch_bounds__(256) training_statistic_kernel(int P, int V, c
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= P) return;
-    float ga = 0.0f, cnt = 0.0f, mr = -1.0f, ms = 0.0f, mm = 0.0f;
+    // the accumulated gradient starts from the state and takes the views in order: V views in one launch give the very bits that V launches
+    // of one view give -- (acc + a) + b, not acc + (a + b) -- so ranks that gather their views reproduce the one-process loop's statistics
+    float ga = g_accum[i], cnt = 0.0f, mr = -1.0f, ms = 0.0f, mm = 0.0f;
     for (int v = 0; v < V; v++)
     {
         const size_t o = (size_t)v * P + i;
@@ -38,7 +40,7 @@ __global__ void __launch_bounds__(256) training_statistic_kernel(int P, int V, c
         if (csum) { ms = fmaxf(ms, csum[o]); mm = fmaxf(mm, cmax[o]); } // :360-361 (contributions are >= 0)
     }
     if (cnt == 0.0f) return; // invisible in every view: state untouched, like the masked assignments
-    g_accum[i] += ga;
+    g_accum[i] = ga;
     g_denom[i] += cnt;
     c_denom[i] += cnt;
     max_radii[i] = fmaxf(max_radii[i], mr);
@@ -274,6 +276,107 @@ __global__ void __launch_bounds__(256) max_distance_kernel(int n, const float *_
     if (threadIdx.x == 0)
         atomicMax(out, __float_as_uint(sqrtf(nan_max(nan_max(wmax[0], wmax[1]), nan_max(wmax[2], wmax[3])))));
 }
+// ---- state digest (include/ts_model.h: tsm_state_digest) ------------------------------------------------------------------------------
+// digest(segment) = sum over its 64-bit pairs x_j of mix64(x_j ^ (j + 1) * GOLDEN) mod 2^64: an integer sum, so block shape, grid size and
+// the order of the atomics cannot change it.  ONE launch for every segment: the segments are cut into chunks of DG_CHUNK_WORDS words, the
+// blocks stride over the concatenated chunk list (segment numbers only rise along a block's walk, so a block meets each segment in one
+// run) with the next chunk's loads issued ahead of the current chunk's arithmetic, every lane keeps a 64-bit accumulator, and a run ends in a wave64 reduction, one LDS step over the four waves and ONE 64-bit
+// atomicAdd.  Loads are 16 bytes per lane (two pairs); a segment whose base is not 16-byte aligned, and the last 1..3 words of any
+// segment, are read word by word.
+constexpr uint64_t DG_GOLDEN = 0x9E3779B97F4A7C15ull;
+constexpr int DG_ITER = 4;                             // 16-byte loads in flight per lane
+constexpr uint32_t DG_CHUNK_WORDS = 256 * 4 * DG_ITER; // 16 KiB per block and chunk
+
+struct DigestTable
+{
+    const uint32_t *base[TSM_DIGEST_MAX_SEGMENTS];
+    uint32_t words[TSM_DIGEST_MAX_SEGMENTS];
+    uint32_t chunk0[TSM_DIGEST_MAX_SEGMENTS + 1]; // first chunk of segment s in the concatenated list; [n] = total
+    int n;
+};
+
+__device__ __forceinline__ uint64_t dg_mix(uint64_t z)
+{ // splitmix64 finaliser
+    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
+    z ^= z >> 27; z *= 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+__device__ __forceinline__ uint64_t dg_pair(uint32_t lo, uint32_t hi, uint64_t key) { return dg_mix((((uint64_t)hi << 32) | lo) ^ key); }
+
+// the 16 bytes at words [o, o + 4) of a segment of n words, zero beyond its end
+__device__ __forceinline__ void dg_load(const DigestTable &t, uint32_t c, int s, uint4 (&v)[DG_ITER])
+{
+    const uint32_t *__restrict__ w = t.base[s];
+    const uint32_t n = t.words[s];
+    const bool vec = (reinterpret_cast<uintptr_t>(w) & 15) == 0;
+    const uint32_t w0 = (c - t.chunk0[s]) * DG_CHUNK_WORDS + threadIdx.x * 4; // < 2^32: n < 2^32 and the chunk starts below n
+    for (int k = 0; k < DG_ITER; k++)
+    {
+        const uint64_t o = (uint64_t)w0 + (uint64_t)k * 1024; // 64 bits: the last chunk's lanes may point past 2^32
+        v[k] = make_uint4(0u, 0u, 0u, 0u);
+        if (o + 4 <= n && vec) v[k] = *reinterpret_cast<const uint4 *>(w + o);
+        else if (o < n)
+        {
+            v[k].x = w[o];
+            if (o + 1 < n) v[k].y = w[o + 1];
+            if (o + 2 < n) v[k].z = w[o + 2];
+            if (o + 3 < n) v[k].w = w[o + 3];
+        }
+    }
+}
+
+__device__ __forceinline__ uint64_t dg_sum(const DigestTable &t, uint32_t c, int s, const uint4 (&v)[DG_ITER])
+{
+    const uint32_t n = t.words[s];
+    const uint32_t w0 = (c - t.chunk0[s]) * DG_CHUNK_WORDS + threadIdx.x * 4;
+    uint64_t acc = 0;
+    for (int k = 0; k < DG_ITER; k++)
+    {
+        const uint64_t o = (uint64_t)w0 + (uint64_t)k * 1024;
+        const uint64_t key = (o / 2 + 1) * DG_GOLDEN;
+        if (o < n) acc += dg_pair(v[k].x, v[k].y, key);
+        if (o + 2 < n) acc += dg_pair(v[k].z, v[k].w, key + DG_GOLDEN);
+    }
+    return acc;
+}
+
+__global__ void __launch_bounds__(256) state_digest_kernel(const DigestTable t, unsigned long long *__restrict__ digests)
+{
+    __shared__ unsigned long long wsum[4];
+    const uint32_t total = t.chunk0[t.n];
+    uint32_t c = blockIdx.x; // the walk is block-uniform: every barrier below is met by all 256 threads
+    if (c >= total) return;
+    int s = 0;
+    while (c >= t.chunk0[s + 1]) s++; // empty segments own no chunk and are stepped over
+    uint4 cur[DG_ITER], nxt[DG_ITER];
+    dg_load(t, c, s, cur);
+    uint64_t acc = 0;
+    for (;;)
+    {
+        const uint32_t cn = c + gridDim.x;
+        const bool more = cn < total;
+        int sn = s;
+        if (more)
+        { // the next chunk's loads go out before this chunk's multiplies
+            while (cn >= t.chunk0[sn + 1]) sn++;
+            dg_load(t, cn, sn, nxt);
+        }
+        acc += dg_sum(t, c, s, cur);
+        if (!more || sn != s)
+        { // the block's run of segment s has ended: wave64 reduction, one LDS step over the four waves, ONE atomic
+            for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor((unsigned long long)acc, o);
+            if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+            __syncthreads();
+            if (threadIdx.x == 0) atomicAdd(digests + s, wsum[0] + wsum[1] + wsum[2] + wsum[3]);
+            if (!more) return;
+            __syncthreads();
+            acc = 0;
+        }
+        for (int k = 0; k < DG_ITER; k++) cur[k] = nxt[k];
+        c = cn;
+        s = sn;
+    }
+}
 } // namespace
 
 hipError_t ts_model_training_statistic(int P, int V, const int32_t *radii, const float *c2d_grad, const float *csum, const float *cmax,
@@ -367,5 +470,28 @@ hipError_t ts_model_max_distance(int n_vertices, const float *vertex, const floa
         const int blocks = (n_vertices + 255) / 256;
         hipLaunchKernelGGL(max_distance_kernel, dim3(blocks < 2048 ? blocks : 2048), dim3(256), 0, s, n_vertices, vertex, campos, (uint32_t *)out);
     }
+    return hipGetLastError();
+}
+
+hipError_t ts_model_state_digest(int n, const void *const *segments, const uint64_t *num_words, uint64_t *digests, hipStream_t s)
+{
+    // checked by the caller: 0 <= n <= TSM_DIGEST_MAX_SEGMENTS, every count < 2^32, every non-empty segment 4-byte aligned
+    if (n <= 0) return hipSuccess;
+    hipError_t e = hipMemsetAsync(digests, 0, (size_t)n * sizeof(uint64_t), s);
+    if (e != hipSuccess) return e;
+    DigestTable t{};
+    t.n = n;
+    uint32_t total = 0;
+    for (int i = 0; i < n; i++)
+    {
+        t.base[i] = (const uint32_t *)segments[i];
+        t.words[i] = (uint32_t)num_words[i];
+        t.chunk0[i] = total;
+        total += (uint32_t)((num_words[i] + DG_CHUNK_WORDS - 1) / DG_CHUNK_WORDS); // <= n * 2^20
+    }
+    t.chunk0[n] = total;
+    if (total == 0) return hipSuccess;
+    const uint32_t cap = 256 * 8; // 8 resident blocks per CU: enough loads in flight for HBM, few enough atomics to vanish
+    hipLaunchKernelGGL(state_digest_kernel, dim3(total < cap ? total : cap), dim3(256), 0, s, t, (unsigned long long *)digests);
     return hipGetLastError();
 }

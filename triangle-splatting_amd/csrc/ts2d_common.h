@@ -376,3 +376,4 @@ hipError_t ts_model_update_mask(int P, int mode, const float *opacity, const flo
 hipError_t ts_model_clip(int P, int mode, const uint8_t *mask, float value, float *param, float *exp_avg, float *exp_avg_sq, hipStream_t s);
 hipError_t ts_model_opacity_reset(int P, float reset_value, float *opacity, float *exp_avg, float *exp_avg_sq, hipStream_t s);
 hipError_t ts_model_max_distance(int n_vertices, const float *vertex, const float *campos, float *out, hipStream_t s);
+hipError_t ts_model_state_digest(int n, const void *const *segments, const uint64_t *num_words, uint64_t *digests, hipStream_t s);

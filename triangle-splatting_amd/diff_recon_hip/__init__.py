@@ -24,6 +24,9 @@
                           (the regularisation schedule of _get_loss with affine_reg), ColorAffine (the per-view colour affine and its optimizer groups)
                           (reference: src/diff_recon/trainers/VanillaTS_trainer.py:86-116, trainer_utils.py:339-346,
                            src/diff_recon/models/VanillaTS_model.py:72-76, 86-94, 118-121, 146-152, 678-684)
+    multirank.py          ImageParallelLoop (image-parallel training end to end: shard the views, exchange gradients and statistics, replicated Adam and
+                          structural rules), ReplicaGuard / ReplicaDivergence and state_digest (one-launch 64-bit digests of device state that prove the
+                          replicas bit-identical) -- no counterpart in the reference, which has no distributed path
     graphed.py            GraphedStep: a whole training step (sync-free forward, loss, backward, optimizer) captured once into a HIP graph and
                           replayed with one launch -- no counterpart in the reference, whose forward reads num_rendered back every step
 
@@ -40,3 +43,5 @@ from .optim import FusedAdam, ShardedAdam, ShFactors  # noqa: F401
 from .graphed import GraphedStep  # noqa: F401
 from .regularizers import triangle_regularization, prepare_nearest, PreparedNearest, TrainerRegularizers, ColorAffine, AffineReg, affine_reg  # noqa: F401
 from .model_init import create_from_pcd, grid_sampling, grid_size_search, get_inside_mask, inter_point_distance, sample_points  # noqa: F401
+from .multirank import (ImageParallelLoop, ReplicaGuard, ReplicaDivergence, state_digest, state_digest_reference, digest_segments,  # noqa: F401
+                        replicated_state, MAX_DIGEST_SEGMENTS)

@@ -428,10 +428,13 @@ def set_sh_degree(m, iteration: int):
         m.active_sh_degree = sh_degree_at(iteration, args.one_up_iters, m.max_sh_degree)
 
 
-def run_model_update(m, iteration: int, render_pkgs=()):
+def run_model_update(m, iteration: int, render_pkgs=(), all_views: bool = False, group=None):
     """VanillaTSModel.model_update (:567-581), same order: statistics of the step's views, densification, the pruning / clipping
     rules, opacity reset, then the gamma and SH-degree schedules.  `m` carries the reference's attribute names and inherits
-    DensificationStats (its `update` is `_training_statistic`).  Returns [(rule, result)] of the rules that fired."""
+    DensificationStats (its `update` is `_training_statistic`).  Returns [(rule, result)] of the rules that fired.
+    all_views / group (image-parallel training, diff_recon_hip/multirank.py): every package's per-view arrays are all-gathered over `group`
+    first, so every rank applies the statistics of ALL views of the step -- package after package, rank order inside each -- and the rules
+    below take the same decisions on every rank.  The defaults are the one-process behaviour."""
     if m.config.model_update is None:
         return []
     # _training_statistic (:347-350) returns early when config.model_update.statistic is None, outside (start_iter, end_iter], or
@@ -441,7 +444,7 @@ def run_model_update(m, iteration: int, render_pkgs=()):
     if args is not None and args.start_iter < iteration <= args.end_iter:
         for pkg in render_pkgs:
             if pkg is not None:
-                m.update(pkg)
+                m.update(pkg, all_views=all_views, group=group) if all_views else m.update(pkg)
     fired = []
     for rule in (densification, opacity_pruning, opacity_clipping, scale_pruning, scale_clipping, contribution_pruning, opacity_reset):
         res = rule(m, iteration)

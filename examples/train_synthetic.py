@@ -16,6 +16,8 @@ gradients and statistics exchanged, the model replicated (diff_recon_hip.ImagePa
 A "ground truth" is rendered from a hidden set of triangles from several cameras; a perturbed, sparser copy is optimised.
     python examples/train_synthetic.py [--rasterizer 2D|3D] [--iters 400] [--triangles 20000] [--views 4]
     python examples/train_synthetic.py --world 2 [--exchange dense|factored_sh] [--check-every 50]
+    python examples/train_synthetic.py --eval-mesh      after training, score the OPAQUE mesh of the model (what saveGLB would export, rendered
+                                                        by diff_recon_hip.MeshRenderer) on the training views: PSNR / SSIM per view and their means
 """
 import argparse
 import math
@@ -187,6 +189,16 @@ def train(rasterizer="2D", iters=200, triangles=20000, width=256, height=192, se
     return [float(x) for x in torch.stack(losses).cpu()], m, sec
 
 
+def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, height=192, seed=0, views=2):
+    """PSNR / SSIM of the model's opaque mesh -- mesh_from_triangles: one colour per face from the DC coefficients, back faces as reversed
+    twins, the soup saveGLB writes -- against the hidden targets of train() called with the same arguments (diff_recon_hip.evaluate_mesh)."""
+    _, _, cams, gts, kw, _, _ = _setup(rasterizer, iters, triangles, width, height, seed, views, 0.0, False, False)
+    for cam, gt in zip(cams, gts):
+        cam.gt_image = gt
+    shs = m._shs if m.single_sh else m._f_dc
+    return D.evaluate_mesh(cams, *D.mesh_from_triangles(m._vertex, shs), bg_color=kw["bg_color"])
+
+
 # ---- image-parallel: the same training over N processes (diff_recon_hip/multirank.py) ------------------------------------------------------
 def _rank_state(m):
     """The replicated state of a rank as host arrays (collect=True: what the tests compare between the ranks, bit for bit)."""
@@ -323,7 +335,10 @@ if __name__ == "__main__":
     ap.add_argument("--world", type=int, default=None, help="image-parallel over this many processes (rank r on GPU r %% device_count); views per step = 2, or N when N > 2")
     ap.add_argument("--exchange", default="dense", choices=["dense", "factored_sh"], help="--world: how the colour gradients travel between the ranks")
     ap.add_argument("--check-every", type=int, default=50, help="--world: iterations between two replica-guard checks (one is forced after every structural update)")
+    ap.add_argument("--eval-mesh", action="store_true", help="after training, render the model as an opaque mesh (diff_recon_hip.MeshRenderer) from the training views and print PSNR / SSIM")
     a = ap.parse_args()
+    if a.eval_mesh and a.world is not None:
+        ap.error("--eval-mesh scores the model of the one-process loop (with --world the trained replicas live in the rank processes)")
     parallel = {} if a.world is None else dict(world=a.world, exchange=a.exchange, check_every=a.check_every,
                                                views_per_step=2 if 2 % a.world == 0 else a.world)
     losses, m, sec = train(a.rasterizer, a.iters, a.triangles, views=a.views, w_geometry=a.w_geometry, single_sh=a.single_sh_tensor, init_from_pcd=a.init_from_pcd,
@@ -331,3 +346,8 @@ if __name__ == "__main__":
     for row in m.log:
         print("  update", row)
     print(f"{a.rasterizer}: loss {losses[0]:.5f} -> {losses[-1]:.5f} in {a.iters} iterations, {sec * 1e3:.2f} ms/iteration (incl. Python)")
+    if a.eval_mesh:
+        res = mesh_scores(m, a.rasterizer, a.iters, a.triangles, views=a.views)
+        for v, (p_, s_) in enumerate(zip(res["psnr"], res["ssim"])):
+            print(f"  opaque mesh, view {v}: PSNR {p_:.2f} dB  SSIM {s_:.4f}")
+        print(f"opaque mesh of {m._vertex.shape[0]} triangles: mean PSNR {res['mean_psnr']:.2f} dB, mean SSIM {res['mean_ssim']:.4f} over {len(res['psnr'])} views")

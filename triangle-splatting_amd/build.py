@@ -45,6 +45,8 @@ COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-a
 SOURCES = {
     "preprocess.hip": ["-ffp-contract=off"],
     "preprocess3d.hip": ["-ffp-contract=off"],
+    "mesh_preprocess.hip": ["-ffp-contract=off"],  # the opaque mesh renderer (include/ts_mesh.h): per-face setup ...
+    "mesh_resolve.hip": ["-ffp-contract=off"],     # ... and the per-pixel depth test (what is fused there is written as fmaf)
     "shgrad.hip": ["-ffp-contract=off"],
     "photometric.hip": [],
     "depth_normal.hip": ["-ffp-contract=off"],
@@ -74,7 +76,8 @@ HEADERS = ["ts2d_common.h", "ts2d_lab.h", "ts2d_math.h", "ts2d_wave.h", "ts2d_gr
            os.path.join("..", "..", "include", "ts_loss.h"),
            os.path.join("..", "..", "include", "ts_knn.h"),
            os.path.join("..", "..", "include", "ts_model.h"),
-           os.path.join("..", "..", "include", "ts_optim.h")]
+           os.path.join("..", "..", "include", "ts_optim.h"),
+           os.path.join("..", "..", "include", "ts_mesh.h")]
 
 
 def hipcc() -> str:

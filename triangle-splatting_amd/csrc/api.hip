@@ -12,6 +12,7 @@
 #include "../../include/ts_knn.h"
 #include "../../include/ts_model.h"
 #include "../../include/ts_optim.h"
+#include "../../include/ts_mesh.h"
 #ifdef TS2D_LAB
 #include "ts2d_lab.h"
 #endif
@@ -281,12 +282,10 @@ void record_instance_count(int variant, int W, int H, int P, unsigned long long 
 }
 
 // The instance count of a forward whose bin phase is queued on `s`, for the host: the early read-back (early != nullptr) or, when there is no
-// pinned word (allocation refused), a copy behind everything that was queued -- slower, same results.  Stored in *num_rendered and recorded
-// for the capacity hints.
-int read_instance_count(const ts2d_camera *cam, const ts2d_geometry *geom, uint32_t flags, const ts2d_state *state, const EarlyCount *early,
-                        hipStream_t s, int64_t *num_rendered)
+// pinned word (allocation refused), a copy behind everything that was queued -- slower, same results.  Stored in *num_rendered
+// (wait_instance_count; the mesh renderer's bin phase ends here) and recorded for the capacity hints (read_instance_count).
+int wait_instance_count(int P, const ts2d_state *state, const EarlyCount *early, hipStream_t s, int64_t *num_rendered)
 {
-    const int P = geom->P;
     unsigned long long n = 0;
     if (early)
     {
@@ -302,7 +301,13 @@ int read_instance_count(const ts2d_camera *cam, const ts2d_geometry *geom, uint3
     if (n > 0x7fffffffull) // the reference's int num_rendered wraps here; instance slots are 32-bit
         return fail(TS2D_ERR_CAPACITY, "%llu tile instances exceed the 2^31 - 1 the instance list can address", n);
     *num_rendered = (int64_t)n;
-    record_instance_count((flags & TS2D_FLAG_3D) ? 3 : 2, cam->width, cam->height, P, n);
+    return TS2D_OK;
+}
+int read_instance_count(const ts2d_camera *cam, const ts2d_geometry *geom, uint32_t flags, const ts2d_state *state, const EarlyCount *early,
+                        hipStream_t s, int64_t *num_rendered)
+{
+    if (int rc = wait_instance_count(geom->P, state, early, s, num_rendered)) return rc;
+    record_instance_count((flags & TS2D_FLAG_3D) ? 3 : 2, cam->width, cam->height, geom->P, (unsigned long long)*num_rendered);
     return TS2D_OK;
 }
 } // namespace
@@ -1313,5 +1318,139 @@ int ts2d_profile_read(int32_t index, char *name, size_t name_bytes, double *tota
     if (total_ms) *total_ms = r.ms;
     if (launches) *launches = r.launches;
     return TS2D_OK;
+}
+// ---- opaque mesh renderer (include/ts_mesh.h) ------------------------------------------------------------------------------------
+namespace
+{
+int validate_mesh_camera(const ts2d_camera *cam)
+{
+    if (!cam) return fail(TS2D_ERR_INVALID, "null camera");
+    if (cam->width <= 0 || cam->height <= 0) return fail(TS2D_ERR_INVALID, "image size must be positive");
+    if (cam->width > 65535 * TS_TILE || cam->height > 65535 * TS_TILE) return fail(TS2D_ERR_INVALID, "image too large");
+    if (!(cam->tan_fovx > 0.0f) || !(cam->tan_fovy > 0.0f)) return fail(TS2D_ERR_INVALID, "tan_fovx / tan_fovy must be positive");
+    return TS2D_OK;
+}
+int validate_mesh_faces(int32_t F)
+{
+    if (F < 0) return fail(TS2D_ERR_INVALID, "F must be >= 0");
+    if (F > (int)TS_ID_MASK) return fail(TS2D_ERR_CAPACITY, "more than 2^28 - 1 faces: the instance values keep four bits of each face index");
+    return TS2D_OK;
+}
+MeshArgs make_mesh(const ts2d_camera *cam, float znear, int32_t V, const float *vertices, int32_t F, const int32_t *faces)
+{
+    MeshArgs a;
+    a.W = cam->width; a.H = cam->height; a.V = V; a.F = F;
+    a.grid_x = (cam->width + TS_TILE - 1) / TS_TILE; a.grid_y = (cam->height + TS_TILE - 1) / TS_TILE;
+    a.tan_fovx = cam->tan_fovx; a.tan_fovy = cam->tan_fovy; a.znear = znear;
+    a.viewmatrix = cam->viewmatrix; a.vertices = vertices; a.faces = faces;
+    return a;
+}
+} // namespace
+
+size_t ts2d_mesh_geometry_state_bytes(int32_t F) { return ts2d_geometry_state_bytes(F); }
+
+int ts2d_mesh_bin(const ts2d_camera *cam, float znear, int32_t V, const float *vertices, int32_t F, const int32_t *faces,
+                  const ts2d_state *state, int64_t *num_rendered, void *stream)
+{
+    if (int rc = validate_mesh_camera(cam)) return rc;
+    if (int rc = validate_mesh_faces(F)) return rc;
+    if (!cam->viewmatrix) return fail(TS2D_ERR_INVALID, "viewmatrix is null");
+    if (!(znear >= 0.0f)) return fail(TS2D_ERR_INVALID, "znear must be >= 0"); // the depth keys are ordered by their bit patterns
+    if (V < 0) return fail(TS2D_ERR_INVALID, "V must be >= 0");
+    if (!state || !num_rendered) return fail(TS2D_ERR_INVALID, "null state/num_rendered");
+    *num_rendered = 0;
+    if (F == 0) return TS2D_OK;
+    if (!faces || (V > 0 && !vertices)) return fail(TS2D_ERR_INVALID, "vertices/faces is null");
+    if (!state->geometry || state->geometry_bytes < ts2d_geometry_state_bytes(F))
+        return fail(TS2D_ERR_CAPACITY, "geometry state buffer too small: %zu < %zu", state->geometry_bytes, ts2d_geometry_state_bytes(F));
+    hipStream_t s = (hipStream_t)stream;
+    GeometryStateView g;
+    ts_carve_geometry((char *)state->geometry, F, g);
+    const MeshArgs a = make_mesh(cam, znear, V, vertices, F, faces);
+    EarlyCount early;
+    const bool have_early = acquire_early_count(early);
+    {
+        ProfScope ps("mesh_preprocess", s);
+        ts_launch_mesh_preprocess(a, g, s);
+    }
+    TS_CHECK(0u, s, "mesh_preprocess");
+    {
+        ProfScope ps("depth_census", s);
+        ts_sort_by_depth_begin(g, F, have_early ? early.host : nullptr, s);
+    }
+    if (have_early) TS_HIP(hipEventRecord(early.ev, s));
+    {
+        ProfScope ps("depth_sort", s);
+        ts_sort_by_depth_finish(g, F, s);
+    }
+    {
+        ProfScope ps("scan", s);
+        ts_scan_offsets(g, F, s);
+    }
+    TS_CHECK(0u, s, "depth order");
+    return wait_instance_count(F, state, have_early ? &early : nullptr, s, num_rendered);
+}
+
+int ts2d_mesh_render_counted(const ts2d_camera *cam, int32_t F, const float *faces_color, const float *background, int64_t N,
+                             const ts2d_state *state, float *render, float *mask, float *depth, int32_t *face_idx,
+                             unsigned long long *wave_visits, void *stream)
+{
+    if (int rc = validate_mesh_camera(cam)) return rc;
+    if (int rc = validate_mesh_faces(F)) return rc;
+    if (!background || (F > 0 && !faces_color)) return fail(TS2D_ERR_INVALID, "faces_color/background is null");
+    if (!state || !render || !mask) return fail(TS2D_ERR_INVALID, "null state/output");
+    if (N < 0) return fail(TS2D_ERR_INVALID, "num_rendered < 0");
+    if (N > 0x7fffffffll) return fail(TS2D_ERR_CAPACITY, "the instance list addresses at most 2^31 - 1 instances");
+    const int W = cam->width, H = cam->height;
+    if (F == 0 && N > 0) return fail(TS2D_ERR_INVALID, "num_rendered > 0 without faces");
+    if (!state->image || state->image_bytes < ts2d_image_state_bytes(W, H)) return fail(TS2D_ERR_CAPACITY, "image state buffer too small");
+    if (N > 0 && (!state->binning || ts_binning_capacity(state->binning_bytes, W, H) < N))
+        return fail(TS2D_ERR_CAPACITY, "binning state buffer too small");
+    if (F > 0 && (!state->geometry || state->geometry_bytes < ts2d_geometry_state_bytes(F)))
+        return fail(TS2D_ERR_CAPACITY, "geometry state buffer too small");
+    hipStream_t s = (hipStream_t)stream;
+    GeometryStateView g{};
+    BinningStateView b{};
+    ImageStateView im{};
+    if (F > 0) ts_carve_geometry((char *)state->geometry, F, g);
+    if (N > 0)
+    {
+        ts_carve_binning((char *)state->binning, ts_binning_capacity(state->binning_bytes, W, H), W, H, b);
+        ts_binning_set_count(b, N);
+    }
+    ts_carve_image((char *)state->image, W, H, im);
+    const MeshArgs a = make_mesh(cam, 0.0f, 0, nullptr, F, nullptr);
+    const int ntiles = a.grid_x * a.grid_y;
+    if (F > 0)
+    {
+        // variant 0: every instance reaches every quadrant -- the depth test walks whole tiles and ignores the values' mask bits
+        const QuadMaskArgs quad{0, 0.0f, cam->tan_fovx, cam->tan_fovy, W, H, 1.0f / (float)W, 1.0f / (float)H};
+        ProfScope ps("emit_keys", s);
+        ts_launch_emit_keys(F, a.grid_x, ntiles, g, b, im, nullptr, nullptr, -1, im.status, quad, s);
+    }
+    else ts_launch_zero_words((uint32_t *)im.ranges, 2 * (size_t)ntiles, s);
+    if (N > 0)
+    {
+        {
+            ProfScope ps("tile_sort", s);
+            ts_sort_pairs(b, N, nullptr, ntiles, s);
+        }
+        {
+            ProfScope ps("tile_ranges", s);
+            ts_launch_tile_ranges(N, nullptr, b, im, s);
+        }
+    }
+    {
+        ProfScope ps("mesh_resolve", s);
+        ts_launch_mesh_resolve(a, g, b, im, faces_color, background, render, mask, depth, face_idx, wave_visits, s);
+    }
+    TS_CHECK(0u, s, "mesh_resolve");
+    return TS2D_OK;
+}
+
+int ts2d_mesh_render(const ts2d_camera *cam, int32_t F, const float *faces_color, const float *background, int64_t N,
+                     const ts2d_state *state, float *render, float *mask, float *depth, int32_t *face_idx, void *stream)
+{
+    return ts2d_mesh_render_counted(cam, F, faces_color, background, N, state, render, mask, depth, face_idx, nullptr, stream);
 }
 } // extern "C"

@@ -305,6 +305,26 @@ void ts_launch_render3d_bwd_group(const RenderArgs &a, float tan_fovx, float tan
                                   const BinningStateView &b, const ImageStateView &im, const float *dL_dout_feature,
                                   const float *dL_dout_depth, const float *dL_dout_normal, float *grad_rec, hipStream_t s);
 
+// ---- opaque mesh renderer (include/ts_mesh.h): same states and ordering chain, its own record and a depth-test kernel ------------
+// Face record (16 floats = 64 B), written by mesh_preprocess.hip, read by mesh_resolve.hip:
+//   [0..5] screen-space vertices x1 y1 x2 y2 x3 y3 (pixels; the centre of pixel (i, j) is (i + .5, j + .5))
+//   [6..8] normal_view (unnormalised)   [9] normal_view . v1_view   [10] nearest vertex depth (= the sort key)   [11] farthest vertex depth
+//   [12..15] unused (0)
+// Invalid faces (an index outside [0, V), a vertex at depth <= znear, no pixel centre in the bounding box, zero screen area) have
+// tiles_touched = 0 and the sort key 0, like culled triangles.
+struct MeshArgs
+{
+    int W, H, V, F, grid_x, grid_y;
+    float tan_fovx, tan_fovy, znear;
+    const float *viewmatrix; // 16 floats, device
+    const float *vertices;   // V * 3
+    const int32_t *faces;    // F * 3
+};
+void ts_launch_mesh_preprocess(const MeshArgs &a, const GeometryStateView &g, hipStream_t s);
+void ts_launch_mesh_resolve(const MeshArgs &a, const GeometryStateView &g, const BinningStateView &b, const ImageStateView &im,
+                            const float *faces_color, const float *background, float *render, float *mask, float *depth, int32_t *face_idx,
+                            unsigned long long *wave_visits, hipStream_t s);
+
 // ---- factored SH-gradient exchange (multi-GPU, shgrad.hip) ---------------------------------------------------------
 void ts_launch_sh_grad_expand(int P, int D, int M, int V, const float *vertex, const float *campos, const float *dL_dcolor,
                               float *dL_dshs, hipStream_t s);

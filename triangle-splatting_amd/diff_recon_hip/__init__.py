@@ -27,10 +27,15 @@
     multirank.py          ImageParallelLoop (image-parallel training end to end: shard the views, exchange gradients and statistics, replicated Adam and
                           structural rules), ReplicaGuard / ReplicaDivergence and state_digest (one-launch 64-bit digests of device state that prove the
                           replicas bit-identical) -- no counterpart in the reference, which has no distributed path
+    mesh_renderer.py      MeshRenderer (the opaque z-buffer look at an exported mesh: constructor, `render` signature and results of KaolinRenderer,
+                          plus depth and face_idx) and mesh_from_triangles (the mesh saveGLB would write, on the device)
+                          (reference: src/diff_recon/renderer/kaolin_renderer.py:8-72, src/diff_recon/models/raw_triangle.py:183-209)
+    metrics.py            psnr, ssim (= 1 - SSIMLoss) and evaluate_mesh: PSNR / SSIM of a mesh's opaque render against each view's gt_image
+                          (reference: src/diff_recon/trainers/trainer_utils.py:331-336, VanillaTS_trainer.py:156-190)
     graphed.py            GraphedStep: a whole training step (sync-free forward, loss, backward, optimizer) captured once into a HIP graph and
                           replayed with one launch -- no counterpart in the reference, whose forward reads num_rendered back every step
 
-Native code: libts2d.so (include/ts_loss.h, include/ts_model.h, include/ts_optim.h, include/ts2d.h).  No CPU / eager fallback anywhere.
+Native code: libts2d.so (include/ts_loss.h, include/ts_model.h, include/ts_optim.h, include/ts2d.h, include/ts_mesh.h).  No CPU / eager fallback anywhere.
 """
 from .losses import L1, SSIMLoss, ssimLoss, PhotometricLoss, photometric_loss, DepthNormalLoss, DoGLoss, SmoothnessLoss, dogLoss, smoothnessLoss, downsample_bilinear, downsample_bilinear_many  # noqa: F401
 from .triangle_renderer import TriangleRenderer  # noqa: F401
@@ -45,3 +50,5 @@ from .regularizers import triangle_regularization, prepare_nearest, PreparedNear
 from .model_init import create_from_pcd, grid_sampling, grid_size_search, get_inside_mask, inter_point_distance, sample_points  # noqa: F401
 from .multirank import (ImageParallelLoop, ReplicaGuard, ReplicaDivergence, state_digest, state_digest_reference, digest_segments,  # noqa: F401
                         replicated_state, MAX_DIGEST_SEGMENTS)
+from .mesh_renderer import MeshRenderer, mesh_from_triangles  # noqa: F401
+from .metrics import psnr, ssim, evaluate_mesh  # noqa: F401

@@ -7,13 +7,13 @@
 // accum_normal has no background term; the BACKWARD skip test is on G = exp(power), not on alpha (R3D backward.cu:351 vs
 // forward.cu:265), so pairs with G >= 1/255 > alpha that the forward skipped still receive (tiny) gradients.
 //
-// Structure = render_group.hip (four 16-lane groups per wave, one triangle per 4x4 pixel block and step, per-group entry lists,
-// DPP-row transpose-reduce, conflict-aware LDS accumulation, coalesced 64-byte atomic flush).  What is specific here:
+// Structure: the lane-group skeleton of ts2d_group.h (four 16-lane groups per wave, one triangle per 4x4 pixel block and step, per-group
+// entry lists, DPP-row transpose-reduce, conflict-aware LDS accumulation, coalesced 64-byte atomic flush).  What is specific here:
 //   * the per-pixel arithmetic is the REFERENCE'S, expression for expression: depth = v1.n / p_ray.n, p_view = depth p_ray,
 //     p_vk = v_k - p_view, a1 = cross(p_v2, p_v3).n / n.n, a2 = cross(p_v3, p_v1).n / n.n, and the gradient terms of
 //     backward.cu:376-420 -- round 1 used projective affine forms N_k(q) / Den(q) and moment sums, which deliberately left
 //     the reference's rounding behaviour (its parity tests needed explained-outlier clauses);
-//   * the lists are read in DENSE batches (round 5, as render_group.hip since round 4): the emission kernel marks in the top four bits of an
+//   * the lists are read in DENSE batches (ts2d_group.h: stream_refill): the emission kernel marks in the top four bits of an
 //     instance's value which quadrants the triangle's support -- scaled for the backward's G >= 1/255 test, projected -- can reach
 //     (ts2d_support.h: quad_setup_3d), a quadrant wave gathers and culls only those entries, compacted by stream_refill;
 //   * only CULLING uses the affine forms (N_k, Den affine in the in-quadrant pixel offset; a_k >= m  <=>  s (N_k - m Den) >= 0
@@ -99,7 +99,7 @@ __device__ __forceinline__ Cull3 cull3(V3 v1, V3 v2, V3 v3, V3 n, float op, floa
     return c;
 }
 
-// [19] = the entry's position in the tile's list; a list entry is the LDS byte offset of its row (render_group.hip, round 3)
+// [19] = the entry's position in the tile's list
 // backward row: constants, k1 = n x (v3 - v2) and k2 = n x (v1 - v3) (the ray-independent halves of d a1 / d depth = n . ((v3 - v2) x p_ray)
 // = p_ray . k1 and d a2 / d depth = p_ray . k2, backward.cu:389, 395: two dot products per pixel instead of two differences and two cross
 // products), the entry's 16 gradient sums
@@ -120,7 +120,7 @@ __device__ __forceinline__ void publish_row3(float *row, V3 v1, V3 v2, V3 v3, V3
     q[3] = make_float4(c.d0, c.inn, r3.x, r3.y);
     q[4] = make_float4(r3.z, r3.w, w18, __int_as_float(jpos));
 }
-// Second pass of a batch with more than NR surviving entries (rare): the lane gathers its entry's record again (see render_group.hip)
+// Second pass of a batch with more than NR surviving entries (rare): the lane gathers its entry's record again (ts2d_group.h: Compaction)
 __device__ __forceinline__ void republish_row3(float *row, const uint32_t *__restrict__ point_list, const float4 *__restrict__ rec, uint32_t pos,
                                                bool with_id, int jpos)
 {
@@ -192,6 +192,18 @@ __device__ __forceinline__ Hit3 hit3(const float *row, V3 ray)
     return h;
 }
 
+// The pixel's view-space ray, and what the cull needs: the ray of the quadrant's origin and the ray's step per pixel.
+// pixToProj(v, S) = (2 v - S + 1) / S   (R3D auxiliary.h:40-43)
+struct PixelRays { V3 ray, ray0; float sx, sy; };
+__device__ __forceinline__ PixelRays pixel_rays(const RenderArgs &a, const GroupPixel &p, float tan_fovx, float tan_fovy)
+{
+    PixelRays r;
+    r.ray = {tan_fovx * ((2.0f * (float)p.px - (float)a.W + 1.0f) / (float)a.W), tan_fovy * ((2.0f * (float)p.py - (float)a.H + 1.0f) / (float)a.H), 1.0f};
+    r.sx = tan_fovx * 2.0f / (float)a.W; r.sy = tan_fovy * 2.0f / (float)a.H;
+    r.ray0 = {tan_fovx * ((2.0f * (float)p.X0 - (float)a.W + 1.0f) / (float)a.W), tan_fovy * ((2.0f * (float)p.Y0 - (float)a.H + 1.0f) / (float)a.H), 1.0f};
+    return r;
+}
+
 template <bool RICH, bool GAMMA1>
 __global__ void __launch_bounds__(256, 6) render3d_fwd_group_kernel(RenderArgs a, float tan_fovx, float tan_fovy, const uint2 *__restrict__ ranges,
                                                                   const uint32_t *__restrict__ point_list, const float4 *__restrict__ rec,
@@ -201,179 +213,85 @@ __global__ void __launch_bounds__(256, 6) render3d_fwd_group_kernel(RenderArgs a
                                                                   float *__restrict__ contrib_max)
 {
     __shared__ __attribute__((aligned(16))) float cst_all[4][(NR + 1) * ROW];
-    __shared__ __attribute__((aligned(16))) uint32_t list_all[4][4 * NR / 2]; // per group: NR entries of (row | batch position << 8)
-    constexpr int TCAP = 1024; // see render_group.hip: the tile's contribution statistics, merged over the four quadrant waves
+    __shared__ __attribute__((aligned(16))) uint32_t list_all[4][4 * NR / 2]; // per group: NR entries (u16 byte offsets of rows)
+    constexpr int TCAP = 1024; // the tile's contribution statistics, merged over the four quadrant waves (ts2d_group.h: tile_stats_clear)
     __shared__ unsigned long long tsum[RICH ? TCAP : 1]; // 16.48 fixed point (ts2d_group.h)
     __shared__ int tmax[RICH ? TCAP : 1];
 
     const int tile = tile_of_block(blockIdx.x, a.grid_x, a.grid_y);
     if (tile < 0) return; // the grid is padded (ts2d_wave.h)
-    const int tx = tile % a.grid_x, ty = tile / a.grid_x;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int grp = lane >> 4, sub = lane & 15;
-    const int X0 = tx * TS_TILE + (wave & 1) * 8, Y0 = ty * TS_TILE + (wave >> 1) * 8;
-    const int lx = ((grp & 1) << 2) + (sub & 3), ly = ((grp >> 1) << 2) + (sub >> 2);
-    const int px = X0 + lx, py = Y0 + ly;
-    const bool inside = px < a.W && py < a.H;
-    // pixToProj(v, S) = (2 v - S + 1) / S   (R3D auxiliary.h:40-43)
-    const V3 ray = {tan_fovx * ((2.0f * (float)px - (float)a.W + 1.0f) / (float)a.W), tan_fovy * ((2.0f * (float)py - (float)a.H + 1.0f) / (float)a.H), 1.0f};
-    const float sx = tan_fovx * 2.0f / (float)a.W, sy = tan_fovy * 2.0f / (float)a.H;
-    const V3 ray0 = {tan_fovx * ((2.0f * (float)X0 - (float)a.W + 1.0f) / (float)a.W), tan_fovy * ((2.0f * (float)Y0 - (float)a.H + 1.0f) / (float)a.H), 1.0f};
+    const int wave = threadIdx.x >> 6;
+    const GroupPixel p = group_pixel(a, tile, wave);
+    const int lane = p.lane;
+    const PixelRays pr = pixel_rays(a, p, tan_fovx, tan_fovy);
+    const V3 ray = pr.ray;
     const uint2 range = ranges[tile];
     const int len = (int)(range.y - range.x);
-    if (RICH)
-    {
-        for (int k = threadIdx.x; k < min(len, TCAP); k += 256) { tsum[k] = 0ull; tmax[k] = 0; }
-        __syncthreads();
-    }
+    if (RICH) tile_stats_clear<TCAP>(tsum, tmax, len);
     const float g2 = 2.0f * a.gamma;
-    const float bg0 = a.background[0], bg1 = a.C > 1 ? a.background[1] : 0.0f, bg2 = a.C > 2 ? a.background[2] : 0.0f;
     float *cst = cst_all[wave] + ROW;
     uint32_t *list = list_all[wave];
     write_dummy_row3(cst - ROW, lane);
     const char *lds0 = (const char *)cst_all;
-    const uint32_t row0 = (uint32_t)(wave * (NR + 1) + 1) * (ROW * 4), dummy = row0 - ROW * 4;
-    const int stat_step = ((lane >> 3) & 1) | ((lane >> 1) & 2) | ((lane << 1) & 4); // the step of a window whose statistics this lane ends up with
-
-    float T = 1.0f, ar = 0.0f, ag = 0.0f, ab = 0.0f, anx = 0.0f, any_ = 0.0f, anz = 0.0f, ad = 0.0f;
-    bool done = !inside;
-    uint32_t last = (uint32_t)len;
+    const uint32_t row0 = table_row0(wave, ROW), dummy = row0 - ROW * 4;
+    const int stat_step = window_stat_step(lane);
+    FwdPixel P = fwd_pixel(p.inside, len);
 
     // dense batches: only the entries whose quadrant bit is set are gathered and culled (ts2d_group.h, stream_refill); `pos` = list position
     uint32_t id = 0;
     int pos = 0, cursor = 0;
     for (;;)
     {
-        const unsigned long long alive = ballot(!done);
+        const unsigned long long alive = ballot(!P.done);
         if (alive == 0) break;
         int nq = 0;
         stream_refill<false>(id, pos, nq, point_list + range.x, cursor, len, TS_ID_BITS + wave, lane);
         if (nq == 0) break;
         const bool valid = lane < nq;
         float4 r0 = make_float4(0, 0, 1, 0), r1 = make_float4(1, 0, 0, 1), r2 = make_float4(1, 0, 0, 1), r3 = make_float4(0, 0, 0, 0);
-        if (valid)
-        {
-            const float4 *rp = rec + 4 * (size_t)id;
-            r0 = rp[0]; r1 = rp[1]; r2 = rp[2]; r3 = rp[3];
-        }
+        gather_record<true>(rec, id, valid, r0, r1, r2, r3);
         const V3 v1 = {r0.x, r0.y, r0.z}, v2 = {r0.w, r1.x, r1.y}, v3 = {r1.z, r1.w, r2.x}, n = {r2.y, r2.z, r2.w};
-        const Cull3 c = cull3<GAMMA1>(v1, v2, v3, n, r3.x, g2, ray0, sx, sy);
+        const Cull3 c = cull3<GAMMA1>(v1, v2, v3, n, r3.x, g2, pr.ray0, pr.sx, pr.sy);
         unsigned long long M[4];
-#pragma unroll
-        for (int g = 0; g < 4; g++) M[g] = ((alive >> (16 * g)) & 0xFFFFull) ? ballot(valid && c.ov[g] && r3.x * 255.0f >= 1.0f) : 0ull;
-        const unsigned long long any = M[0] | M[1] | M[2] | M[3];
+        const unsigned long long any = fwd_block_masks(M, alive, valid && r3.x * 255.0f >= 1.0f, c.ov);
         if (any == 0) continue;
-        // compacted table rows, at most NR per pass (render_group.hip)
-        const bool anybit = (any >> lane) & 1;
-        const int rank = lane_rank(any), nact = __popcll(any);
-        const int r = rank & (NR - 1);
-        bool mine = anybit && rank < NR;
-        if (mine) publish_row3(cst + r * ROW, v1, v2, v3, n, c, r3, 0.0f, pos);
+        const Compaction cp = compact_rows(any, lane);
+        bool mine = in_pass(cp, false);
+        if (mine) publish_row3(cst + cp.r * ROW, v1, v2, v3, n, c, r3, 0.0f, pos);
         for (int h = 0;;)
         {
-            const unsigned long long mm = nact <= NR ? any : ballot(mine);
-            list[lane] = dummy | (dummy << 16);
-            int steps = 0;
-#pragma unroll
-            for (int g = 0; g < 4; g++)
-            {
-                const unsigned long long Mh = M[g] & mm;
-                if ((Mh >> lane) & 1) ((u16a *)list)[g * NR + lane_rank(Mh)] = (unsigned short)(row0 + r * (ROW * 4));
-                steps = max(steps, __popcll(Mh));
-            }
-            const uint32_t *mylist = list + grp * (NR / 2);
+            const int steps = build_lists(list, M, pass_mask(cp, mine), row0, cp.r, ROW, dummy, lane);
+            const u16a *mylist = (const u16a *)list + p.grp * NR;
             for (int t0 = 0; t0 < steps; t0 += 8)
             {
                 float cw[8];
-                const uint4 packed = *(const uint4 *)(mylist + (t0 >> 1));
+                const uint4 packed = *(const uint4 *)(mylist + t0);
 #pragma unroll
                 for (int st = 0; st < 8; st++)
                 {
                     cw[st] = 0.0f;
                     if (t0 + st < steps)
                     {
-                        const uint32_t word = st < 2 ? packed.x : (st < 4 ? packed.y : (st < 6 ? packed.z : packed.w));
-                        const float *row = (const float *)(lds0 + ((st & 1) ? (word >> 16) : (word & 0xFFFFu)));
+                        const float *row = window_row(lds0, packed, st);
                         const int jpos = __float_as_int(row[19]); // position in the tile's list
                         const Hit3 h = hit3<false>(row, ray);
                         const float pw = GAMMA1 ? h.ecc * h.ecc : pow_nonneg(h.ecc, g2);
                         const float alpha = fminf(0.99f, h.op * __builtin_amdgcn_exp2f(pw * -0.7213475204444817f)); // forward.cu:259-260
-                        const bool hit = !done && h.ok && ecc_in_range(h.ecc) && alpha >= 1.0f / 255.0f;            // forward.cu:241,256,261
-                        const float al = hit ? alpha : 0.0f;
-                        const float contrib = al * T;
-                        ar = fmaf(h.r, contrib, ar);
-                        ag = fmaf(row[16], contrib, ag);
-                        ab = fmaf(row[17], contrib, ab);
-                        if (RICH)
-                        {
-                            anx = fmaf(h.n.x, contrib, anx); // forward.cu:276 (unnormalised normal)
-                            any_ = fmaf(h.n.y, contrib, any_);
-                            anz = fmaf(h.n.z, contrib, anz);
-                            ad = fmaf(h.depth, contrib, ad); // forward.cu:277
-                            cw[st] = contrib;
-                        }
-                        T *= (1.0f - al);
-                        const bool sat = hit && T <= 0.0001f; // forward.cu:280
-                        last = sat ? (uint32_t)(jpos + 1) : last;
-                        done = done || sat;
+                        const bool hit = !P.done && h.ok && ecc_in_range(h.ecc) && alpha >= 1.0f / 255.0f;          // forward.cu:241,256,261
+                        // forward.cu:276-277: the unnormalised normal, the hit point's depth
+                        const float contrib = fwd_blend<RICH>(P, hit, alpha, h.r, row[16], row[17], h.n.x, h.n.y, h.n.z, h.depth, jpos);
+                        if (RICH) cw[st] = contrib;
                     }
                 }
-                if (RICH)
-                {
-                    // contrib_sum / contrib_max (forward.cu:271-273): reduced per 16-lane group, added to the tile's statistics in LDS
-                    // with integer atomics (ts2d_group.h)
-                    float sm, mx;
-                    row_reduce8_sum_max(cw, 0xCCCCCCCCCCCCCCCCull, sm, mx);
-                    int k = 0; // the list position of "its" step, from the step's row (render_group.hip)
-                    if ((lane & 1) == 0 && sm > 0.0f) k = __float_as_int(*(const float *)(lds0 + ((const u16a *)list)[grp * NR + t0 + stat_step] + 19 * 4));
-                    if ((lane & 1) == 0 && sm > 0.0f) tile_stats_add<TCAP>(tsum, tmax, k, sm, mx, point_list + range.x, contrib_sum, contrib_max);
-                }
+                if (RICH) window_stats<TCAP>(cw, lane, stat_step, lds0, mylist, t0, 19, tsum, tmax, point_list + range.x, contrib_sum, contrib_max);
             }
-            if (++h * NR >= nact) break;
-            mine = anybit && rank >= NR;
-            if (mine) republish_row3(cst + r * ROW, point_list, rec, range.x + pos, false, pos);
+            if (++h * NR >= cp.nact) break;
+            mine = in_pass(cp, true);
+            if (mine) republish_row3(cst + cp.r * ROW, point_list, rec, range.x + pos, false, pos);
         }
     }
-    // the wave's pixels leave first; their stores and the ids of the flush are in flight while the wave waits for the others (render_group.hip)
-    if (inside)
-    {
-        const size_t pix = (size_t)py * a.W + px, HW = (size_t)a.H * a.W;
-        final_T[pix] = T;
-        n_contrib[pix] = last;
-        out_feature[pix] = ar + T * bg0;
-        if (a.C > 1) out_feature[HW + pix] = ag + T * bg1;
-        if (a.C > 2) out_feature[2 * HW + pix] = ab + T * bg2;
-        if (RICH)
-        {
-            out_depth[pix] = ad + T * (a.background_depth_dev ? *a.background_depth_dev : a.background_depth);
-            out_normal[pix] = anx;
-            out_normal[HW + pix] = any_;
-            out_normal[2 * HW + pix] = anz;
-        }
-    }
-    if (RICH)
-    {
-        constexpr int NF = (TCAP + 255) / 256;
-        const int nflush = min(len, TCAP);
-        uint32_t ids[NF];
-#pragma unroll
-        for (int j = 0; j < NF; j++)
-        {
-            const int k = (int)threadIdx.x + 256 * j;
-            ids[j] = k < nflush ? point_list[range.x + k] & TS_ID_MASK : 0u;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < NF; j++)
-        {
-            const int k = (int)threadIdx.x + 256 * j;
-            if (k < nflush)
-            {
-                const unsigned long long fx48 = tsum[k];
-                if (fx48 != 0ull) tile_stats_flush(fx48, tmax[k], ids[j], contrib_sum, contrib_max);
-            }
-        }
-    }
+    fwd_store_pixel<RICH>(a, p, P, final_T, n_contrib, out_feature, out_depth, out_normal);
+    if (RICH) tile_stats_leave<TCAP>(tsum, tmax, len, point_list + range.x, contrib_sum, contrib_max);
 }
 
 // Backward (R3D backward.cu:216-454).  Gradient record of the 3D variant: [0..8] dL/dv1_view dL/dv2_view dL/dv3_view,
@@ -384,79 +302,39 @@ __global__ void __launch_bounds__(256, 6) render3d_fwd_group_kernel(RenderArgs a
 //   dL/dv1 = w2 cross(n, p_v3) / n.n + dL_ddepth n / (p_ray.n)        (:391, 402-403)
 //   dL_ddepth = dL_ddepth_pixel contrib + w1 da1_ddepth + w2 da2_ddepth, da1_ddepth = n.cross(v3 - v2, p_ray) / n.n, ...   (:389, 395, 401)
 //   dL/dn  = dL_dnormal_pixel contrib + (w1 (c1 - 2 a1 n) + w2 (c2 - 2 a2 n)) / n.n + dL_ddepth p_v1 / (p_ray.n)   (:388, 394, 403, 406)
-template <bool RICH, bool GAMMA1, int WPB> // WPB = quadrant waves per workgroup (1: single-wave workgroups, see render_group.hip)
-__global__ void __launch_bounds__(64 * WPB, TS3G_BWD_WAVES) render3d_bwd_group_kernel(RenderArgs a, float tan_fovx, float tan_fovy, const uint2 *__restrict__ ranges,
-                                                                     const uint32_t *__restrict__ point_list, const float4 *__restrict__ rec,
-                                                                     const float *__restrict__ final_T, const uint32_t *__restrict__ n_contrib,
-                                                                     const float *__restrict__ dL_dout_feature,
-                                                                     const float *__restrict__ dL_dout_depth,
-                                                                     const float *__restrict__ dL_dout_normal, float *__restrict__ grad_rec)
+template <bool RICH, bool GAMMA1> // one wave per workgroup (ts2d_group.h: tile_of_quadrant_block)
+__global__ void __launch_bounds__(64, TS3G_BWD_WAVES) render3d_bwd_group_kernel(RenderArgs a, float tan_fovx, float tan_fovy, const uint2 *__restrict__ ranges,
+                                                               const uint32_t *__restrict__ point_list, const float4 *__restrict__ rec,
+                                                               const float *__restrict__ final_T, const uint32_t *__restrict__ n_contrib,
+                                                               const float *__restrict__ dL_dout_feature,
+                                                               const float *__restrict__ dL_dout_depth,
+                                                               const float *__restrict__ dL_dout_normal, float *__restrict__ grad_rec)
 {
-    __shared__ __attribute__((aligned(16))) float rows_all[WPB][(NR + 1) * BROW3];
-    __shared__ __attribute__((aligned(16))) uint32_t list_all[WPB][4 * NR / 2];
+    __shared__ __attribute__((aligned(16))) float rows_all[(NR + 1) * BROW3];
+    __shared__ __attribute__((aligned(16))) uint32_t list[4 * NR / 2];
 
-    int tile, quad, wave;
-    if (WPB == 4)
-    {
-        tile = tile_of_block(blockIdx.x, a.grid_x, a.grid_y);
-        quad = wave = threadIdx.x >> 6;
-    }
-    else
-    {
-        // single-wave workgroups: four consecutive units of an XCD are the four quadrants of one tile (they stay neighbours in dispatch order
-        // and on one XCD: shared L2 for the tile's list and records)
-        const int x = blockIdx.x & 7, j = blockIdx.x >> 3;
-        tile = tile_of_block(((j >> 2) << 3) | x, a.grid_x, a.grid_y);
-        quad = j & 3;
-        wave = 0;
-    }
+    int quad;
+    const int tile = tile_of_quadrant_block(blockIdx.x, a.grid_x, a.grid_y, quad);
     if (tile < 0) return; // the grid is padded (ts2d_wave.h)
-    const int tx = tile % a.grid_x, ty = tile / a.grid_x;
-    const int lane = threadIdx.x & 63;
-    const int grp = lane >> 4, sub = lane & 15;
-    const int X0 = tx * TS_TILE + (quad & 1) * 8, Y0 = ty * TS_TILE + (quad >> 1) * 8;
-    const int lx = ((grp & 1) << 2) + (sub & 3), ly = ((grp >> 1) << 2) + (sub >> 2);
-    const int px = X0 + lx, py = Y0 + ly;
-    const bool inside = px < a.W && py < a.H;
-    const V3 ray = {tan_fovx * ((2.0f * (float)px - (float)a.W + 1.0f) / (float)a.W), tan_fovy * ((2.0f * (float)py - (float)a.H + 1.0f) / (float)a.H), 1.0f};
-    const float sx = tan_fovx * 2.0f / (float)a.W, sy = tan_fovy * 2.0f / (float)a.H;
-    const V3 ray0 = {tan_fovx * ((2.0f * (float)X0 - (float)a.W + 1.0f) / (float)a.W), tan_fovy * ((2.0f * (float)Y0 - (float)a.H + 1.0f) / (float)a.H), 1.0f};
+    const GroupPixel p = group_pixel(a, tile, quad);
+    const int lane = p.lane, grp = p.grp, sub = p.sub;
+    const PixelRays pr = pixel_rays(a, p, tan_fovx, tan_fovy);
+    const V3 ray = pr.ray;
     const uint2 range = ranges[tile];
     const float g2 = 2.0f * a.gamma;
-    const size_t pix = (size_t)py * a.W + px, HW = (size_t)a.H * a.W;
-    float *rows = rows_all[wave] + BROW3;
-    uint32_t *list = list_all[wave];
+    float *rows = rows_all + BROW3;
     write_dummy_row3(rows - BROW3, lane);
     if (lane < KROW3) (rows - BROW3)[ROW + lane] = 0.0f; // k1, k2 of the dummy row
     char *lds0 = (char *)rows_all;
-    const uint32_t row0 = (uint32_t)(wave * (NR + 1) + 1) * (BROW3 * 4), dummy = row0 - BROW3 * 4;
+    const uint32_t row0 = table_row0(0, BROW3), dummy = row0 - BROW3 * 4;
     const uint32_t accoff = SOFF3 * 4 + 4 * sub;
 
-    float T = inside ? final_T[pix] : 0.0f;
-    const int last = inside ? (int)n_contrib[pix] : 0;
-    float dpr = 0.0f, dpg = 0.0f, dpb = 0.0f, dnx = 0.0f, dny = 0.0f, dnz = 0.0f, dd = 0.0f, B = 0.0f;
-    if (inside) // backward.cu:283-295; one scalar back-to-front composite B = sum_c dL_dpix_c accum_c (derived at the backward of render_group.hip)
-    {
-        dpr = dL_dout_feature[pix];
-        B = dpr * a.background[0];
-        if (a.C > 1) { dpg = dL_dout_feature[HW + pix]; B = fmaf(dpg, a.background[1], B); }
-        if (a.C > 2) { dpb = dL_dout_feature[2 * HW + pix]; B = fmaf(dpb, a.background[2], B); }
-        if (RICH)
-        {
-            dnx = dL_dout_normal[pix]; dny = dL_dout_normal[HW + pix]; dnz = dL_dout_normal[2 * HW + pix];
-            dd = dL_dout_depth[pix];
-            B = fmaf(dd, a.background_depth_dev ? *a.background_depth_dev : a.background_depth, B);
-        }
-    }
-    float lm = (float)last;
-    lm = fmaxf(lm, dpp<DPP_XOR1>(lm));
-    lm = fmaxf(lm, dpp<DPP_XOR2>(lm));
-    lm = fmaxf(lm, dpp<DPP_HALF_MIRROR>(lm));
-    lm = fmaxf(lm, dpp<DPP_MIRROR>(lm));
+    const BwdPixel P = bwd_pixel<RICH>(a, p, final_T, n_contrib, dL_dout_feature, dL_dout_depth, dL_dout_normal); // backward.cu:283-295
+    float T = P.T, B = P.B;
+    const int last = P.last;
+    const float dpr = P.dpr, dpg = P.dpg, dpb = P.dpb, dnx = P.dnx, dny = P.dny, dnz = P.dnz, dd = P.dd;
     int glast[4];
-#pragma unroll
-    for (int g = 0; g < 4; g++) glast[g] = (int)__builtin_amdgcn_readlane((int)lm, 16 * g);
-    const int maxlast = max(max(glast[0], glast[1]), max(glast[2], glast[3]));
+    const int maxlast = block_lasts(last, glast);
     if (maxlast <= 0) return;
 
     // dense batches, walked back to front: lane 0 holds the entry farthest back (ts2d_group.h, stream_refill<true>); `pos` = list position
@@ -469,59 +347,32 @@ __global__ void __launch_bounds__(64 * WPB, TS3G_BWD_WAVES) render3d_bwd_group_k
         if (nq == 0) break;
         const bool valid = lane < nq;
         float4 r0 = make_float4(0, 0, 1, 0), r1 = make_float4(1, 0, 0, 1), r2 = make_float4(1, 0, 0, 1), r3 = make_float4(0, 0, 0, 0);
-        if (valid)
-        {
-            const float4 *rp = rec + 4 * (size_t)id;
-            r0 = rp[0]; r1 = rp[1]; r2 = rp[2]; r3 = rp[3];
-        }
+        gather_record<true>(rec, id, valid, r0, r1, r2, r3);
         const V3 v1 = {r0.x, r0.y, r0.z}, v2 = {r0.w, r1.x, r1.y}, v3 = {r1.z, r1.w, r2.x}, n = {r2.y, r2.z, r2.w};
         // the backward's skip test is on G (backward.cu:351): support computed with opacity 1
-        const Cull3 c = cull3<GAMMA1>(v1, v2, v3, n, 1.0f, g2, ray0, sx, sy);
+        const Cull3 c = cull3<GAMMA1>(v1, v2, v3, n, 1.0f, g2, pr.ray0, pr.sx, pr.sy);
         unsigned long long M[4];
-#pragma unroll
-        for (int g = 0; g < 4; g++) M[g] = ballot(valid && c.ov[g] && pos < glast[g]); // entries at or behind glast[g] are skipped by all of block g's pixels
-        const unsigned long long any = M[0] | M[1] | M[2] | M[3];
+        const unsigned long long any = bwd_block_masks(M, valid, c.ov, pos, glast);
         if (any == 0) continue;
-        const bool anybit = (any >> lane) & 1;
-        const int rank = lane_rank(any), nact = __popcll(any);
-        const int r = rank & (NR - 1);
-        bool mine = anybit && rank < NR; // back to front = the low lanes first
+        const Compaction cp = compact_rows(any, lane);
+        bool mine = in_pass(cp, false); // back to front = the low lanes first
         if (mine)
         {
-            publish_row3(rows + r * BROW3, v1, v2, v3, n, c, r3, __uint_as_float(id), pos);
-            publish_k3(rows + r * BROW3, v1, v2, v3, n);
+            publish_row3(rows + cp.r * BROW3, v1, v2, v3, n, c, r3, __uint_as_float(id), pos);
+            publish_k3(rows + cp.r * BROW3, v1, v2, v3, n);
         }
-        for (int h = (nact - 1) / NR;;)
+        for (int h = (cp.nact - 1) / NR;;)
         {
-            const unsigned long long mm = nact <= NR ? any : ballot(mine);
-            if (mine)
-            {
-                float4 *z = (float4 *)(rows + r * BROW3 + SOFF3);
-                z[0] = z[1] = z[2] = z[3] = make_float4(0, 0, 0, 0);
-            }
-            list[lane] = dummy | (dummy << 16);
-            int steps = 0;
-#pragma unroll
-            for (int g = 0; g < 4; g++)
-            {
-                const unsigned long long Mh = M[g] & mm;
-                const int nn = __popcll(Mh);
-                if ((Mh >> lane) & 1) ((u16a *)list)[g * NR + lane_rank(Mh)] = (unsigned short)(row0 + r * (BROW3 * 4));
-                steps = max(steps, nn);
-            }
+            const unsigned long long mm = pass_mask(cp, mine);
+            if (mine) zero_sums(rows + cp.r * BROW3 + SOFF3);
+            const int steps = build_lists(list, M, mm, row0, cp.r, BROW3, dummy, lane);
             const u16a *mylist = (const u16a *)list + grp * NR;
-            unsigned long long conflict;
-            {
-                const u16a *l16 = (const u16a *)list + (lane & (NR - 1));
-                const uint32_t l0 = l16[0], l1 = l16[NR], l2 = l16[2 * NR], l3 = l16[3 * NR];
-                conflict = ballot(lane < NR && ((l0 != dummy && (l0 == l1 || l0 == l2 || l0 == l3)) || (l1 != dummy && (l1 == l2 || l1 == l3)) ||
-                                                (l2 != dummy && l2 == l3)));
-            }
+            const unsigned long long conflict = list_conflicts(list, dummy, lane);
             uint32_t ra_next = mylist[0];
             for (int t0 = 0; t0 < steps; t0++)
             {
                 const uint32_t ra = ra_next;
-                ra_next = mylist[min(t0 + 1, NR - 1)]; // one step ahead (render_group.hip)
+                ra_next = mylist[min(t0 + 1, NR - 1)]; // fetched one step ahead: one LDS round trip less on the step's critical path
                 const float *row = (const float *)(lds0 + ra);
                 float *acc = (float *)(lds0 + ra + accoff);
                 const int jpos = __float_as_int(row[19]);
@@ -547,7 +398,7 @@ __global__ void __launch_bounds__(64 * WPB, TS3G_BWD_WAVES) render3d_bwd_group_k
                 const float dL_dcontrib = X - B;
                 B = fmaf(al, X, oma * B);
                 const float dL_dalpha = dL_dcontrib * T; // :383
-                // -3 dL_decc, :384-385 (gamma = 1: pw / (ecc + 1e-8) is ecc to 1e-8 / ecc relative, see render_group.hip)
+                // -3 dL_decc, :384-385 (gamma = 1: pw / (ecc + 1e-8) is ecc to 1e-8 / ecc relative: one multiplication instead of a reciprocal)
                 const float zr = GAMMA1 ? 1.5f * g2 * (dL_dalpha * alpha) * h.ecc : 1.5f * g2 * (dL_dalpha * alpha) * pw * __builtin_amdgcn_rcpf(h.ecc + 1e-8f);
                 const float z = (hit && opG < 0.99f) ? zr : 0.0f;
                 const bool k1 = h.a1 == h.mn;
@@ -572,16 +423,7 @@ __global__ void __launch_bounds__(64 * WPB, TS3G_BWD_WAVES) render3d_bwd_group_k
                 v[bitrev4(12)] = hit ? dL_dalpha * G : 0.0f; // :447
                 v[bitrev4(13)] = dpr * contrib; v[bitrev4(14)] = dpg * contrib; v[bitrev4(15)] = dpb * contrib; // :365
                 const float red = row_reduce16(v, 0xCCCCCCCCCCCCCCCCull, 0xAAAAAAAAAAAAAAAAull);
-                if (!shared_row) *acc = acc0 + red;
-                else
-                {
-#pragma unroll
-                    for (int g = 0; g < 4; g++)
-                    {
-                        if (grp == g) *acc += red;
-                        wave_lds_order();
-                    }
-                }
+                row_add(acc, acc0, red, shared_row, grp);
             }
             {
                 const int nn = __popcll(mm);
@@ -597,30 +439,19 @@ __global__ void __launch_bounds__(64 * WPB, TS3G_BWD_WAVES) render3d_bwd_group_k
                 }
             }
             if (--h < 0) break;
-            mine = anybit && rank >= NR;
-            if (mine) republish_row3(rows + r * BROW3, point_list, rec, range.x + pos, true, pos);
+            mine = in_pass(cp, true);
+            if (mine) republish_row3(rows + cp.r * BROW3, point_list, rec, range.x + pos, true, pos);
         }
     }
 }
 } // namespace
-
-#define TS_DISPATCH_G3(KERNEL, ...)                                                                                                \
-    do                                                                                                                              \
-    {                                                                                                                               \
-        const bool g1 = (a.gamma == 1.0f);                                                                                          \
-        if (a.rich_info && g1) hipLaunchKernelGGL((KERNEL<true, true>), grid, dim3(256), 0, s, __VA_ARGS__);                        \
-        else if (a.rich_info) hipLaunchKernelGGL((KERNEL<true, false>), grid, dim3(256), 0, s, __VA_ARGS__);                        \
-        else if (g1) hipLaunchKernelGGL((KERNEL<false, true>), grid, dim3(256), 0, s, __VA_ARGS__);                                 \
-        else hipLaunchKernelGGL((KERNEL<false, false>), grid, dim3(256), 0, s, __VA_ARGS__);                                        \
-    } while (0)
 
 void ts_launch_render3d_fwd_group(const RenderArgs &a, float tan_fovx, float tan_fovy, const GeometryStateView &g, const BinningStateView &b,
                                   const ImageStateView &im, float *out_feature, float *out_depth, float *out_normal, float *contrib_sum,
                                   float *contrib_max, hipStream_t s)
 {
     if (a.grid_x * a.grid_y == 0) return;
-    const dim3 grid((unsigned)ts_tile_units(a.grid_x, a.grid_y));
-    TS_DISPATCH_G3(render3d_fwd_group_kernel, a, tan_fovx, tan_fovy, im.ranges, b.vals, g.rec, im.final_T, im.n_contrib, out_feature, out_depth,
+    TS_LAUNCH_BLEND(render3d_fwd_group_kernel, a, ts_tile_units(a.grid_x, a.grid_y), 256, s, a, tan_fovx, tan_fovy, im.ranges, b.vals, g.rec, im.final_T, im.n_contrib, out_feature, out_depth,
                    out_normal, contrib_sum, contrib_max);
 }
 
@@ -628,16 +459,7 @@ void ts_launch_render3d_bwd_group(const RenderArgs &a, float tan_fovx, float tan
                                   const ImageStateView &im, const float *dL_dout_feature, const float *dL_dout_depth,
                                   const float *dL_dout_normal, float *grad_rec, hipStream_t s)
 {
-    const dim3 grid((unsigned)(a.grid_x * a.grid_y));
-    if (grid.x == 0) return;
-    constexpr int WPB = 1;
-    const dim3 grid1((unsigned)((WPB == 4 ? 1 : 4) * ts_tile_units(a.grid_x, a.grid_y))); // padded: units past the image return at once
-    const bool g1 = (a.gamma == 1.0f);
-#define TS_BWD3(R, G) hipLaunchKernelGGL((render3d_bwd_group_kernel<R, G, WPB>), grid1, dim3(64 * WPB), 0, s, a, tan_fovx, tan_fovy, im.ranges, b.vals, \
-                                         g.rec, im.final_T, im.n_contrib, dL_dout_feature, dL_dout_depth, dL_dout_normal, grad_rec)
-    if (a.rich_info && g1) TS_BWD3(true, true);
-    else if (a.rich_info) TS_BWD3(true, false);
-    else if (g1) TS_BWD3(false, true);
-    else TS_BWD3(false, false);
-#undef TS_BWD3
+    if (a.grid_x * a.grid_y == 0) return;
+    TS_LAUNCH_BLEND(render3d_bwd_group_kernel, a, ts_quadrant_units(a.grid_x, a.grid_y), 64, s, a, tan_fovx, tan_fovy, im.ranges, b.vals, g.rec, im.final_T,
+                    im.n_contrib, dL_dout_feature, dL_dout_depth, dL_dout_normal, grad_rec);
 }

@@ -5,24 +5,8 @@
 // counts examined entries, stop AFTER the triangle that drives T <= 1e-4, dL_dopacity not gated by the 0.99 clamp,
 // arg-min tie order a1, a2, a3, division by ecc + 1e-8).
 //
-// Why this structure (measured on MI355X, profiles/r02_notes.md):
-//   * a blended (triangle, 8x8 quadrant) pair touches 18 of the 64 pixels on average, so one triangle per wave
-//     iteration leaves 72 % of the lanes idle, and gfx950 does not skip an all-idle 32-lane pass;
-//   * on gfx950 only fma/add/mul (f32) and add/and (u32) issue at the full 32-lanes-per-clock rate; v_cmp, v_cndmask,
-//     v_min/max, every DPP form and the integer shift/mad forms are half rate, transcendentals and v_permlane*_swap
-//     quarter rate -- the blend loops are bound by exactly those, not by FMAs.
-// So: one wave64 still owns one 8x8 pixel quadrant of a 16x16 tile, but its lanes form FOUR 16-lane groups, one per 4x4
-// pixel block, and every group walks ITS OWN culled list of the batch's triangles: four different triangles are blended
-// per wave step (lane occupancy 28 % -> ~45 %), the per-step body is branch-free, and all cross-lane reductions stay
-// inside a 16-lane DPP row (no v_permlane*_swap).
-//
-//   batch   = 64 list entries, one per lane: the lane gathers the 64-byte render record, computes the conservative
-//             support of the triangle (edge functions as affine forms of the in-quadrant pixel offset, used for CULLING
-//             only) against the four 4x4 blocks, and the wave ballots one 64-bit mask per block;
-//   lists   = each block's surviving entries, compacted in visiting order into a 64-byte LDS list (v_mbcnt rank);
-//   step    = every lane reads ITS group's next entry index, then that entry's constants from the wave-private LDS
-//             table (4 distinct rows per ds_read_b128 cost the same as one broadcast row, tools/valu_bench2.hip); a group
-//             whose list is exhausted reads the dummy row -1, which no pixel can hit;
+// Structure: the lane-group skeleton of ts2d_group.h (one wave64 per 8x8 quadrant, four 16-lane groups that each walk their own culled
+// list); the cull's edge functions are affine forms of the in-quadrant pixel offset, used for CULLING only.  What this file holds:
 //   pixels  = barycentrics are evaluated exactly as the reference does, cross(v_j - p, v_k - p) / area2 from
 //             pixel-relative vertex offsets (v - tile origin and (v - origin) - offset are exact in fp32, so the offsets
 //             are bit-identical to the reference's).  Round 1 used affine forms of the pixel offset instead: 4 FMAs
@@ -56,9 +40,7 @@ namespace
 // ROW (ts2d_group.h) = 20 floats per entry row of the constants table:
 //   [0..3] u1x u1y u2x u2y   [4..7] u3x u3y 1/area2 opacity   [8..11] r g b nx   [12..15] ny nz vd1 vd2   [16] vd3   [17] id   [18] the entry's position in the tile's list
 // (u_k = screen vertex k relative to the quadrant origin); row -1 is a dummy that fails every pixel's ecc test.  The backward appends the
-// entry's 16 gradient sums to the row (BROW floats).  A list entry is the LDS BYTE OFFSET of its row (u16): the step loops spend no
-// instruction on unpacking or scaling an index (round 3: four half-rate instructions per step gone; gfx950 issues shifts, bit-field
-// extracts and 24-bit multiply-adds at half rate, tools/valu_bench3.hip).
+// entry's 16 gradient sums to the row (BROW floats).
 [[maybe_unused]] constexpr int BROW = ROW + 16;
 
 struct BlockCull
@@ -86,8 +68,7 @@ __device__ __forceinline__ void entry_geometry(BlockCull &s, float v1x, float v1
     s.u1x = v1x - OX; s.u1y = v1y - OY; s.u2x = v2x - OX; s.u2y = v2y - OY; s.u3x = v3x - OX; s.u3y = v3y - OY;
 }
 
-// Second pass of a batch with more than NR surviving entries (rare): the lane gathers its entry's record again -- keeping the
-// first gather's registers alive across the first pass would cost the occupancy the compaction buys.
+// Second pass of a batch with more than NR surviving entries (rare, ts2d_group.h: Compaction): the lane gathers its entry's record again.
 template <bool RICH>
 __device__ __forceinline__ uint32_t republish_row(float *row, const uint32_t *__restrict__ point_list, const float4 *__restrict__ rec, uint32_t pos,
                                                   int jpos, float OX, float OY)
@@ -187,42 +168,28 @@ __global__ void __launch_bounds__(256, TSG_FWD_WAVES) render_fwd_group_kernel(Re
                                                                 float *__restrict__ contrib_max)
 {
     __shared__ __attribute__((aligned(16))) float cst_all[4][(NR + 1) * ROW];
-    __shared__ __attribute__((aligned(16))) uint32_t list_all[4][4 * NR / 2]; // per group: NR entries of (row | batch position << 8)
-    // contrib_sum / contrib_max of the tile's first TCAP list entries, merged over the four quadrant waves before they leave
-    // as global atomics (one L2 line operation per (tile, triangle) instead of one per (quadrant, triangle))
+    __shared__ __attribute__((aligned(16))) uint32_t list_all[4][4 * NR / 2]; // per group: NR entries (u16 byte offsets of rows)
     constexpr int TCAP = TSG_TCAP; // 960: 960 x 12 bytes + the tables = 23.1 KB per workgroup: seven workgroups per CU (1024 entries would leave six)
     __shared__ unsigned long long tsum[RICH ? TCAP : 1]; // 16.48 fixed point
     __shared__ int tmax[RICH ? TCAP : 1];
 
     const int tile = tile_of_block(blockIdx.x, a.grid_x, a.grid_y);
     if (tile < 0) return; // the grid is padded (ts2d_wave.h)
-    const int tx = tile % a.grid_x, ty = tile / a.grid_x;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int grp = lane >> 4, sub = lane & 15;
-    const int X0 = tx * TS_TILE + (wave & 1) * 8, Y0 = ty * TS_TILE + (wave >> 1) * 8;
-    const int lx = ((grp & 1) << 2) + (sub & 3), ly = ((grp >> 1) << 2) + (sub >> 2);
-    const int px = X0 + lx, py = Y0 + ly;
-    const bool inside = px < a.W && py < a.H;
-    const float fx = (float)lx, fy = (float)ly, OX = (float)X0, OY = (float)Y0;
+    const int wave = threadIdx.x >> 6;
+    const GroupPixel p = group_pixel(a, tile, wave);
+    const int lane = p.lane;
+    const float fx = (float)p.lx, fy = (float)p.ly, OX = (float)p.X0, OY = (float)p.Y0;
     const uint2 range = ranges[tile];
     const int len = (int)(range.y - range.x);
-    if (RICH)
-    {
-        for (int k = threadIdx.x; k < min(len, TCAP); k += 256) { tsum[k] = 0ull; tmax[k] = 0; }
-        __syncthreads();
-    }
+    if (RICH) tile_stats_clear<TCAP>(tsum, tmax, len);
     const float g2 = 2.0f * a.gamma;
-    const float bg0 = a.background[0], bg1 = a.C > 1 ? a.background[1] : 0.0f, bg2 = a.C > 2 ? a.background[2] : 0.0f;
     float *cst = cst_all[wave] + ROW;
     uint32_t *list = list_all[wave];
     write_dummy_row(cst - ROW, lane);
-    const char *lds0 = (const char *)cst_all;                                      // list entries are byte offsets from here
-    const uint32_t row0 = (uint32_t)(wave * (NR + 1) + 1) * (ROW * 4), dummy = row0 - ROW * 4; // row r of this wave: row0 + r * 80
-    const int stat_step = ((lane >> 3) & 1) | ((lane >> 1) & 2) | ((lane << 1) & 4); // the step of a window whose statistics this lane ends up with
-
-    float T = 1.0f, ar = 0.0f, ag = 0.0f, ab = 0.0f, anx = 0.0f, any_ = 0.0f, anz = 0.0f, ad = 0.0f;
-    bool done = !inside;
-    uint32_t last = (uint32_t)len; // a pixel that never saturates examines the whole list (forward.cu:296-297)
+    const char *lds0 = (const char *)cst_all; // list entries are byte offsets from here
+    const uint32_t row0 = table_row0(wave, ROW), dummy = row0 - ROW * 4;
+    const int stat_step = window_stat_step(lane);
+    FwdPixel P = fwd_pixel(p.inside, len);
 
 #ifdef TS2D_STATS
     unsigned long long stat_acc[12] = {0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0};
@@ -232,7 +199,7 @@ __global__ void __launch_bounds__(256, TSG_FWD_WAVES) render_fwd_group_kernel(Re
     int pos = 0, cursor = 0;
     for (;;)
     {
-        const unsigned long long alive = ballot(!done);
+        const unsigned long long alive = ballot(!P.done);
         if (alive == 0) break;
         int nq = 0;
         stream_refill<false, TSG_FWD_CAP>(id, pos, nq, point_list + range.x, cursor, len, TS_ID_BITS + wave, lane);
@@ -240,56 +207,28 @@ __global__ void __launch_bounds__(256, TSG_FWD_WAVES) render_fwd_group_kernel(Re
         const bool valid = lane < nq;
         const int ent = pos;
         float4 r0 = make_float4(0, 0, 0, 0), r1 = r0, r2 = r0, r3 = r0;
-        if (valid)
-        {
-            const float4 *rp = rec + 4 * (size_t)id;
-            r0 = rp[0]; r1 = rp[1]; r2 = rp[2];
-            if (RICH) r3 = rp[3];
-        }
+        gather_record<RICH>(rec, id, valid, r0, r1, r2, r3);
         const BlockCull s = block_cull<GAMMA1>(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, g2, OX, OY);
-        // one entry mask per block; a block whose 16 pixels are all saturated takes no more entries
         unsigned long long M[4];
-#pragma unroll
-        for (int g = 0; g < 4; g++) M[g] = ((alive >> (16 * g)) & 0xFFFFull) ? ballot(valid && s.ov[g]) : 0ull;
-        const unsigned long long any = M[0] | M[1] | M[2] | M[3];
+        const unsigned long long any = fwd_block_masks(M, alive, valid, s.ov);
         TSG_STAT(0, __popcll(ballot(valid)));
         if (any == 0) continue;
         TSG_STAT(1, __popcll(M[0]) + __popcll(M[1]) + __popcll(M[2]) + __popcll(M[3]));
         TSG_STAT(6, 1);
         TSG_STAT(7, __popcll(any));
-        // The entries with work are COMPACTED into at most NR table rows per pass (a batch with more survivors takes two passes):
-        // half the LDS of a row per list entry, hence 7 instead of 5 resident waves per SIMD -- the blend kernels are latency
-        // bound (3 instead of 5 waves: +27 %, profiles/r02_notes.md).
-        const bool anybit = (any >> lane) & 1;
-        const int rank = lane_rank(any), nact = __popcll(any);
-        const int r = rank & (NR - 1);
-        bool mine = anybit && rank < NR;
-        if (mine) publish_row(cst + r * ROW, s, id, ent, r1, r2, r3);
+        const Compaction cp = compact_rows(any, lane);
+        bool mine = in_pass(cp, false);
+        if (mine) publish_row(cst + cp.r * ROW, s, id, ent, r1, r2, r3);
         for (int h = 0;;)
         {
-            const unsigned long long mm = nact <= NR ? any : ballot(mine);
-            list[lane] = dummy | (dummy << 16); // four lists x NR entries: the dummy row
-            int steps = 0;
-#pragma unroll
-            for (int g = 0; g < 4; g++)
-            {
-                const unsigned long long Mh = M[g] & mm;
-                if ((Mh >> lane) & 1) ((u16a *)list)[g * NR + lane_rank(Mh)] = (unsigned short)(row0 + r * (ROW * 4));
-                steps = max(steps, __popcll(Mh));
-            }
-            const u16a *mylist = (const u16a *)list + grp * NR;
+            const int steps = build_lists(list, M, pass_mask(cp, mine), row0, cp.r, ROW, dummy, lane);
+            const u16a *mylist = (const u16a *)list + p.grp * NR;
             TSG_STAT(2, steps);
             TSG_STAT(3, (steps + 7) / 8);
-#ifdef TS2D_STATS
-            {   // [8] steps at which two groups hold the same entry (what the backward must serialise)  [9] passes  [10] second passes
-                const u16a *l16 = (const u16a *)list + (lane & (NR - 1));
-                const uint32_t l0 = l16[0], l1 = l16[NR], l2 = l16[2 * NR], l3 = l16[3 * NR];
-                TSG_STAT(8, __popcll(ballot(lane < NR && ((l0 != dummy && (l0 == l1 || l0 == l2 || l0 == l3)) || (l1 != dummy && (l1 == l2 || l1 == l3)) ||
-                                                          (l2 != dummy && l2 == l3)))));
-                TSG_STAT(9, 1);
-                TSG_STAT(10, h > 0 ? 1 : 0);
-            }
-#endif
+            // [8] steps at which two groups hold the same entry (what the backward must serialise)  [9] passes  [10] second passes
+            TSG_STAT(8, __popcll(list_conflicts(list, dummy, lane)));
+            TSG_STAT(9, 1);
+            TSG_STAT(10, h > 0 ? 1 : 0);
 
             for (int t0 = 0; t0 < steps; t0 += 8)
             {
@@ -301,8 +240,7 @@ __global__ void __launch_bounds__(256, TSG_FWD_WAVES) render_fwd_group_kernel(Re
                     c[st] = 0.0f;
                     if (t0 + st < steps)
                     {
-                        const uint32_t word = st < 2 ? packed.x : (st < 4 ? packed.y : (st < 6 ? packed.z : packed.w));
-                        const float *row = (const float *)(lds0 + ((st & 1) ? (word >> 16) : (word & 0xFFFFu)));
+                        const float *row = window_row(lds0, packed, st);
                         const float4 q0 = *(const float4 *)(row), q1 = *(const float4 *)(row + 4);
                         const Bary b = barycentrics(q0, q1, fx, fy);
                         const float4 q2 = *(const float4 *)(row + 8);
@@ -319,50 +257,18 @@ __global__ void __launch_bounds__(256, TSG_FWD_WAVES) render_fwd_group_kernel(Re
                         else jpos = __float_as_int(row[18]);
                         const float pw = GAMMA1 ? b.ecc * b.ecc : pow_nonneg(b.ecc, g2);
                         const float alpha = fminf(0.99f, q1.w * __builtin_amdgcn_exp2f(pw * -0.7213475204444817f)); // forward.cu:311-312
-                        const bool hit = !done && ecc_in_range(b.ecc) && alpha >= 1.0f / 255.0f;                     // forward.cu:307,313
-                        // branch-free blend: a lane that does not hit runs with alpha = 0 (x + c*0 == x, T*1 == T bit for bit)
-                        const float al = hit ? alpha : 0.0f;
+                        const bool hit = !P.done && ecc_in_range(b.ecc) && alpha >= 1.0f / 255.0f;                   // forward.cu:307,313
                         TSG_STAT(4, __popcll(ballot(hit)));
-                        const float contrib = al * T;
-                        ar = fmaf(q2.x, contrib, ar);
-                        ag = fmaf(q2.y, contrib, ag);
-                        ab = fmaf(q2.z, contrib, ab);
-                        if (RICH)
-                        {
-                            anx = fmaf(q2.w, contrib, anx);
-                            any_ = fmaf(q3.x, contrib, any_);
-                            anz = fmaf(q3.y, contrib, anz);
-                            const float d = q3.z * b.a1 + q3.w * b.a2 + vd3 * b.a3; // forward.cu:328
-                            ad = fmaf(d, contrib, ad);
-                            c[st] = contrib;
-                        }
-                        T *= (1.0f - al);
-                        const bool sat = hit && T <= 0.0001f; // forward.cu:333
-                        last = sat ? (uint32_t)(jpos + 1) : last;
-                        done = done || sat;
+                        const float d = q3.z * b.a1 + q3.w * b.a2 + vd3 * b.a3; // forward.cu:328
+                        const float contrib = fwd_blend<RICH>(P, hit, alpha, q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, d, jpos);
+                        if (RICH) c[st] = contrib;
                     }
                 }
-                if (RICH)
-                {
-                    // contrib_sum / contrib_max (forward.cu:323-324; the reference issues two global atomics per (pixel, triangle)):
-                    // the window's 8 x 64 contributions are reduced inside each 16-lane group, lane pairs (l, l ^ 1) end up with
-                    // (sum, max, batch position) of step `b3 + 2 b2 + 4 b1` of their group, and the even lanes add them to the TILE's
-                    // statistics in LDS with INTEGER atomics (ts2d_group.h: ds_add_u64 / ds_max_i32 cost 5-7 cycles per wave
-                    // instruction, ds_add_f32 193) -- no ordering between groups or waves is needed.
-                    float sm, mx;
-                    row_reduce8_sum_max(c, 0xCCCCCCCCCCCCCCCCull, sm, mx);
-                    // the list position of "its" step: from the step's row (two LDS reads on the few lanes that have something to add) rather
-                    // than carried through the window in eight registers and selected with seven v_cndmask
-                    int k = 0;
-                    if ((lane & 1) == 0 && sm > 0.0f) k = __float_as_int(*(const float *)(lds0 + mylist[t0 + stat_step] + 18 * 4));
-                    if ((lane & 1) == 0 && sm > 0.0f) tile_stats_add<TCAP>(tsum, tmax, k, sm, mx, point_list + range.x, contrib_sum, contrib_max);
-                }
+                if (RICH) window_stats<TCAP>(c, lane, stat_step, lds0, mylist, t0, 18, tsum, tmax, point_list + range.x, contrib_sum, contrib_max);
             }
-            // more survivors than table rows: a second pass (handing them to the next batch instead was measured and dropped, a loss:
-            // profiles/r06_blend_ab.txt)
-            if (++h * NR >= nact) break;
-            mine = anybit && rank >= NR;
-            if (mine) republish_row<RICH>(cst + r * ROW, point_list, rec, range.x + pos, ent, OX, OY);
+            if (++h * NR >= cp.nact) break;
+            mine = in_pass(cp, true);
+            if (mine) republish_row<RICH>(cst + cp.r * ROW, point_list, rec, range.x + pos, ent, OX, OY);
         }
     }
 
@@ -370,46 +276,8 @@ __global__ void __launch_bounds__(256, TSG_FWD_WAVES) render_fwd_group_kernel(Re
     if (lane == 0)
         for (int i = 0; i < 12; i++) atomicAdd(&g_stats_group[i], stat_acc[i]);
 #endif
-    // the wave's pixels leave first: their stores, and the ids the flush below needs, are in flight while the wave waits for the others
-    if (inside)
-    {
-        const size_t pix = (size_t)py * a.W + px, HW = (size_t)a.H * a.W;
-        final_T[pix] = T;
-        n_contrib[pix] = last;
-        out_feature[pix] = ar + T * bg0; // forward.cu:345
-        if (a.C > 1) out_feature[HW + pix] = ag + T * bg1;
-        if (a.C > 2) out_feature[2 * HW + pix] = ab + T * bg2;
-        if (RICH)
-        {
-            out_depth[pix] = ad + T * (a.background_depth_dev ? *a.background_depth_dev : a.background_depth); // forward.cu:349
-            out_normal[pix] = anx;
-            out_normal[HW + pix] = any_;
-            out_normal[2 * HW + pix] = anz;
-        }
-    }
-    if (RICH)
-    {
-        constexpr int NF = (TCAP + 255) / 256;
-        const int nflush = min(len, TCAP);
-        uint32_t ids[NF];
-#pragma unroll
-        for (int j = 0; j < NF; j++)
-        {
-            const int k = (int)threadIdx.x + 256 * j;
-            ids[j] = k < nflush ? point_list[range.x + k] & TS_ID_MASK : 0u;
-        }
-        __syncthreads(); // the only rendezvous of the four quadrant waves: the tile's merged contribution statistics leave
-#pragma unroll
-        for (int j = 0; j < NF; j++)
-        {
-            const int k = (int)threadIdx.x + 256 * j;
-            if (k < nflush)
-            {
-                const unsigned long long fx48 = tsum[k];
-                if (fx48 != 0ull) tile_stats_flush(fx48, tmax[k], ids[j], contrib_sum, contrib_max);
-            }
-        }
-    }
+    fwd_store_pixel<RICH>(a, p, P, final_T, n_contrib, out_feature, out_depth, out_normal);
+    if (RICH) tile_stats_leave<TCAP>(tsum, tmax, len, point_list + range.x, contrib_sum, contrib_max);
 }
 
 #endif // TSG_PART & 1
@@ -418,80 +286,42 @@ __global__ void __launch_bounds__(256, TSG_FWD_WAVES) render_fwd_group_kernel(Re
 // pair's 16 values are formed per lane exactly in the reference's per-pixel form (no moment / epilogue algebra):
 //   dL/dv_j (screen space) = perp(t_j) / area2 with  t_1 = e_3 p_v2 - e_2 p_v3,  t_2 = e_1 p_v3 - e_3 p_v1,  t_3 = e_2 p_v1 - e_1 p_v2,
 //   e_k = dL/da_k - sum_m dL/da_m a_m     (backward.cu:464-479 regrouped: v2_v3 = p_v3 - p_v2 etc.; perp(x, y) = (y, -x)),
-// the division by area2 is applied once per entry when the sums are flushed.  The reference keeps seven back-to-front
-// composites per pixel (accum_feature[3], accum_normal, accum_depth: backward.cu:323-325) but uses them only through
-// dL_dcontrib = sum_c dL_dpix_c * (value_c - accum_c).  With X = sum_c dL_dpix_c * value_c and B = sum_c dL_dpix_c * accum_c
-// that is X - B, and the per-channel update accum_c <- alpha value_c + (1 - alpha) accum_c collapses to
-// B <- alpha X + (1 - alpha) B: one scalar of sequential state instead of seven (same mathematics, different rounding order).
+// the division by area2 is applied once per entry when the sums are flushed.  The pixel's sequential state is one scalar composite B
+// (ts2d_group.h: BwdPixel).
 // Each group reduces its 16 values over its 16 lanes (DPP row transpose-reduce) and adds them into the entry's row of a
 // wave-private LDS table (one group after the other: two groups may be working on the same entry); once per batch the rows
 // leave as coalesced 64-byte atomic adds, one gradient record per 16 lanes.
-// WPB = quadrant waves per workgroup.  The four quadrant waves of a tile never talk to each other here, so the backward launches
-// them as single-wave workgroups (WPB = 1): the dispatcher then fills a freed wave slot with the next quadrant instead of waiting for
-// four slots of one CU, which shortens the tail of the launch (8160 tiles are only 5.3 rounds of 256-thread workgroups).  The four
-// quadrants of a tile stay neighbours in dispatch order and on one XCD (shared L2 for the tile's list and records).
+// One wave per workgroup (ts2d_group.h: tile_of_quadrant_block).
 #if TSG_PART & 2
-template <bool RICH, bool GAMMA1, int WPB>
-__global__ void __launch_bounds__(64 * WPB, TSG_BWD_WAVES) render_bwd_group_kernel(RenderArgs a, const uint2 *__restrict__ ranges,
-                                                                   const uint32_t *__restrict__ point_list, const float4 *__restrict__ rec,
-                                                                   const float *__restrict__ final_T, const uint32_t *__restrict__ n_contrib,
-                                                                   const float *__restrict__ dL_dout_feature,
-                                                                   const float *__restrict__ dL_dout_depth,
-                                                                   const float *__restrict__ dL_dout_normal, float *__restrict__ grad_rec)
+template <bool RICH, bool GAMMA1>
+__global__ void __launch_bounds__(64, TSG_BWD_WAVES) render_bwd_group_kernel(RenderArgs a, const uint2 *__restrict__ ranges,
+                                                             const uint32_t *__restrict__ point_list, const float4 *__restrict__ rec,
+                                                             const float *__restrict__ final_T, const uint32_t *__restrict__ n_contrib,
+                                                             const float *__restrict__ dL_dout_feature,
+                                                             const float *__restrict__ dL_dout_depth,
+                                                             const float *__restrict__ dL_dout_normal, float *__restrict__ grad_rec)
 {
-    __shared__ __attribute__((aligned(16))) float rows_all[WPB][(NR + 1) * BROW]; // constants + gradient sums; row -1 absorbs the adds of idle groups
-    __shared__ __attribute__((aligned(16))) uint32_t list_all[WPB][4 * NR / 2];   // per group: NR entries (u16 byte offsets of rows)
+    __shared__ __attribute__((aligned(16))) float rows_all[(NR + 1) * BROW]; // constants + gradient sums; row -1 absorbs the adds of idle groups
+    __shared__ __attribute__((aligned(16))) uint32_t list[4 * NR / 2];      // per group: NR entries (u16 byte offsets of rows)
 
-    int tile, quad, wave; // quad = which 8x8 quadrant of the tile, wave = index into this workgroup's LDS arrays
-    if (WPB == 4)
-    {
-        tile = tile_of_block(blockIdx.x, a.grid_x, a.grid_y);
-        quad = wave = threadIdx.x >> 6;
-    }
-    else
-    {
-        // single-wave workgroups: four consecutive units of an XCD are the four quadrants of one tile (they stay neighbours in dispatch order
-        // and on one XCD: shared L2 for the tile's list and records)
-        const int x = blockIdx.x & 7, j = blockIdx.x >> 3;
-        tile = tile_of_block(((j >> 2) << 3) | x, a.grid_x, a.grid_y);
-        quad = j & 3;
-        wave = 0;
-    }
+    int quad; // which 8x8 quadrant of the tile
+    const int tile = tile_of_quadrant_block(blockIdx.x, a.grid_x, a.grid_y, quad);
     if (tile < 0) return; // the grid is padded (ts2d_wave.h)
-    const int tx = tile % a.grid_x, ty = tile / a.grid_x;
-    const int lane = threadIdx.x & 63;
-    const int grp = lane >> 4, sub = lane & 15;
-    const int X0 = tx * TS_TILE + (quad & 1) * 8, Y0 = ty * TS_TILE + (quad >> 1) * 8;
-    const int lx = ((grp & 1) << 2) + (sub & 3), ly = ((grp >> 1) << 2) + (sub >> 2);
-    const int px = X0 + lx, py = Y0 + ly;
-    const bool inside = px < a.W && py < a.H;
-    const float fx = (float)lx, fy = (float)ly, OX = (float)X0, OY = (float)Y0;
+    const GroupPixel p = group_pixel(a, tile, quad);
+    const int lane = p.lane, grp = p.grp, sub = p.sub;
+    const float fx = (float)p.lx, fy = (float)p.ly, OX = (float)p.X0, OY = (float)p.Y0;
     const uint2 range = ranges[tile];
     const float g2 = 2.0f * a.gamma;
-    const size_t pix = (size_t)py * a.W + px, HW = (size_t)a.H * a.W;
-    float *rows = rows_all[wave] + BROW;
-    uint32_t *list = list_all[wave];
+    float *rows = rows_all + BROW;
     write_dummy_row(rows - BROW, lane);
-    char *lds0 = (char *)rows_all;                                                   // list entries are byte offsets from here
-    const uint32_t row0 = (uint32_t)(wave * (NR + 1) + 1) * (BROW * 4), dummy = row0 - BROW * 4; // row r of this wave: row0 + r * 144
-    const uint32_t accoff = ROW * 4 + 4 * sub;                                        // this lane's sum inside a row
+    char *lds0 = (char *)rows_all; // list entries are byte offsets from here
+    const uint32_t row0 = table_row0(0, BROW), dummy = row0 - BROW * 4;
+    const uint32_t accoff = ROW * 4 + 4 * sub; // this lane's sum inside a row
 
-    float T = inside ? final_T[pix] : 0.0f;            // backward.cu:318
-    const int last = inside ? (int)n_contrib[pix] : 0; // backward.cu:320
-    float dpr = 0.0f, dpg = 0.0f, dpb = 0.0f, dnx = 0.0f, dny = 0.0f, dnz = 0.0f, dd = 0.0f, B = 0.0f;
-    if (inside) // backward.cu:331-343
-    {
-        dpr = dL_dout_feature[pix];
-        B = dpr * a.background[0];
-        if (a.C > 1) { dpg = dL_dout_feature[HW + pix]; B = fmaf(dpg, a.background[1], B); }
-        if (a.C > 2) { dpb = dL_dout_feature[2 * HW + pix]; B = fmaf(dpb, a.background[2], B); }
-        if (RICH)
-        {
-            dnx = dL_dout_normal[pix]; dny = dL_dout_normal[HW + pix]; dnz = dL_dout_normal[2 * HW + pix];
-            dd = dL_dout_depth[pix];
-            B = fmaf(dd, a.background_depth_dev ? *a.background_depth_dev : a.background_depth, B); // accum_normal starts at 0, accum_depth at background_depth
-        }
-    }
+    const BwdPixel P = bwd_pixel<RICH>(a, p, final_T, n_contrib, dL_dout_feature, dL_dout_depth, dL_dout_normal);
+    float T = P.T, B = P.B;
+    const int last = P.last;
+    const float dpr = P.dpr, dpg = P.dpg, dpb = P.dpb, dnx = P.dnx, dny = P.dny, dnz = P.dnz, dd = P.dd;
     // The six colour / normal columns of the per-step reduction are (dL_dpixel constant) x contrib: their registers are filled
     // pre-swapped (ts2d_group.h, row_reduce16c) with constants that depend on which quarter of its 16-lane group the lane is in.
     // Quad (registers 0..3) = r, b, g, nx by final position; pair (registers 4, 5) = ny, nz.
@@ -504,16 +334,8 @@ __global__ void __launch_bounds__(64 * WPB, TSG_BWD_WAVES) render_bwd_group_kern
     // gradient-record column (0..5 screen vertices, 6 opacity, 7..9 rgb, 10..12 normal, 13..15 vertex depths) of the value lane `sub`
     // ends up with: register reg(sub) of the network, registers -> columns {7, 9, 8, 10, 11, 12, 0, 1, 2, 3, 4, 5, 6, 13, 14, 15}
     const int rcol = (int)((0xF15ADC39E0486B27ull >> (4 * sub)) & 15ull);
-    // entries at list positions >= the largest n_contrib of a block are skipped by all of its pixels (backward.cu:377-379)
-    float lm = (float)last;
-    lm = fmaxf(lm, dpp<DPP_XOR1>(lm));
-    lm = fmaxf(lm, dpp<DPP_XOR2>(lm));
-    lm = fmaxf(lm, dpp<DPP_HALF_MIRROR>(lm));
-    lm = fmaxf(lm, dpp<DPP_MIRROR>(lm));
     int glast[4];
-#pragma unroll
-    for (int g = 0; g < 4; g++) glast[g] = (int)__builtin_amdgcn_readlane((int)lm, 16 * g);
-    const int maxlast = max(max(glast[0], glast[1]), max(glast[2], glast[3]));
+    const int maxlast = block_lasts(last, glast);
     if (maxlast <= 0) return;
 
     // dense batches, walked back to front: lane 0 holds the entry farthest back (ts2d_group.h, stream_refill<true>); `pos` = list position
@@ -527,52 +349,22 @@ __global__ void __launch_bounds__(64 * WPB, TSG_BWD_WAVES) render_bwd_group_kern
         const bool valid = lane < nq;
         const int ent = pos;
         float4 r0 = make_float4(0, 0, 0, 0), r1 = r0, r2 = r0, r3 = r0;
-        if (valid)
-        {
-            const float4 *rp = rec + 4 * (size_t)id;
-            r0 = rp[0]; r1 = rp[1]; r2 = rp[2];
-            if (RICH) r3 = rp[3];
-        }
+        gather_record<RICH>(rec, id, valid, r0, r1, r2, r3);
         const BlockCull s = block_cull<GAMMA1>(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, g2, OX, OY);
         unsigned long long M[4];
-#pragma unroll
-        for (int g = 0; g < 4; g++) M[g] = ballot(valid && s.ov[g] && pos < glast[g]); // entries at or behind glast[g] are skipped by all of block g's pixels
-        const unsigned long long any = M[0] | M[1] | M[2] | M[3];
+        const unsigned long long any = bwd_block_masks(M, valid, s.ov, pos, glast);
         if (any == 0) continue;
-        // compacted table rows, at most NR per pass (see the forward); back to front = the low lanes first (lane 0 is the entry farthest back)
-        const bool anybit = (any >> lane) & 1;
-        const int rank = lane_rank(any), nact = __popcll(any);
-        const int r = rank & (NR - 1);
-        bool mine = anybit && rank < NR;
-        if (mine) publish_row(rows + r * BROW, s, id, ent, r1, r2, r3);
-        for (int h = (nact - 1) / NR;;)
+        // back to front = the low lanes first (lane 0 is the entry farthest back)
+        const Compaction cp = compact_rows(any, lane);
+        bool mine = in_pass(cp, false);
+        if (mine) publish_row(rows + cp.r * BROW, s, id, ent, r1, r2, r3);
+        for (int h = (cp.nact - 1) / NR;;)
         {
-            const unsigned long long mm = nact <= NR ? any : ballot(mine);
-            if (mine)
-            {
-                float4 *z = (float4 *)(rows + r * BROW + ROW);
-                z[0] = z[1] = z[2] = z[3] = make_float4(0, 0, 0, 0);
-            }
-            list[lane] = dummy | (dummy << 16);
-            int steps = 0;
-#pragma unroll
-            for (int g = 0; g < 4; g++) // back to front: the entry with the highest list position first
-            {
-                const unsigned long long Mh = M[g] & mm;
-                const int n = __popcll(Mh);
-                if ((Mh >> lane) & 1) ((u16a *)list)[g * NR + lane_rank(Mh)] = (unsigned short)(row0 + r * (BROW * 4));
-                steps = max(steps, n);
-            }
+            const unsigned long long mm = pass_mask(cp, mine);
+            if (mine) zero_sums(rows + cp.r * BROW + ROW);
+            const int steps = build_lists(list, M, mm, row0, cp.r, BROW, dummy, lane); // back to front: the entry with the highest list position first
             const u16a *mylist = (const u16a *)list + grp * NR;
-
-            // steps at which two groups work on the SAME entry (their sums must then be added to its row one after the other)
-            unsigned long long conflict;
-            {
-                const u16a *l16 = (const u16a *)list + (lane & (NR - 1));
-                const uint32_t l0 = l16[0], l1 = l16[NR], l2 = l16[2 * NR], l3 = l16[3 * NR];
-                conflict = ballot(lane < NR && ((l0 != dummy && (l0 == l1 || l0 == l2 || l0 == l3)) || (l1 != dummy && (l1 == l2 || l1 == l3)) ||
-                                                (l2 != dummy && l2 == l3)));
-            }
+            const unsigned long long conflict = list_conflicts(list, dummy, lane);
             uint32_t ra_next = mylist[0];
             for (int t0 = 0; t0 < steps; t0++)
             {
@@ -645,16 +437,7 @@ __global__ void __launch_bounds__(64 * WPB, TSG_BWD_WAVES) render_bwd_group_kern
                     v[12] = hit ? dL_dalpha * G : 0.0f; // backward.cu:490 (not gated by the clamp)
                     v[13] = w * b.a1; v[14] = w * b.a2; v[15] = w * b.a3; // backward.cu:429-431
                     const float red = row_reduce16c(v, 0xCCCCCCCCCCCCCCCCull, 0xAAAAAAAAAAAAAAAAull); // lane sub: gradient-record column rcol
-                    if (!shared_row) *acc = q0acc + red;
-                    else
-                    {
-#pragma unroll
-                        for (int g = 0; g < 4; g++)
-                        {
-                            if (grp == g) *acc += red;
-                            wave_lds_order();
-                        }
-                    }
+                    row_add(acc, q0acc, red, shared_row, grp);
                 }
             }
 
@@ -676,8 +459,8 @@ __global__ void __launch_bounds__(64 * WPB, TSG_BWD_WAVES) render_bwd_group_kern
                 }
             }
             if (--h < 0) break;
-            mine = anybit && rank >= NR;
-            if (mine) republish_row<RICH>(rows + r * BROW, point_list, rec, range.x + pos, ent, OX, OY);
+            mine = in_pass(cp, true);
+            if (mine) republish_row<RICH>(rows + cp.r * BROW, point_list, rec, range.x + pos, ent, OX, OY);
         }
     }
 }
@@ -685,24 +468,13 @@ __global__ void __launch_bounds__(64 * WPB, TSG_BWD_WAVES) render_bwd_group_kern
 } // namespace
 
 #if TSG_PART & 1
-#define TS_DISPATCH_G(KERNEL, ...)                                                                                    \
-    do                                                                                                                \
-    {                                                                                                                 \
-        const bool g1 = (a.gamma == 1.0f);                                                                            \
-        if (a.rich_info && g1) hipLaunchKernelGGL((KERNEL<true, true>), grid, dim3(256), 0, s, __VA_ARGS__);          \
-        else if (a.rich_info) hipLaunchKernelGGL((KERNEL<true, false>), grid, dim3(256), 0, s, __VA_ARGS__);          \
-        else if (g1) hipLaunchKernelGGL((KERNEL<false, true>), grid, dim3(256), 0, s, __VA_ARGS__);                   \
-        else hipLaunchKernelGGL((KERNEL<false, false>), grid, dim3(256), 0, s, __VA_ARGS__);                          \
-    } while (0)
-
 void ts_launch_render_fwd_group(const RenderArgs &a, const GeometryStateView &g, const BinningStateView &b, const ImageStateView &im,
                                 float *out_feature, float *out_depth, float *out_normal, float *contrib_sum, float *contrib_max,
                                 hipStream_t s)
 {
     if (a.grid_x * a.grid_y == 0) return;
-    const dim3 grid((unsigned)ts_tile_units(a.grid_x, a.grid_y));
-    TS_DISPATCH_G(render_fwd_group_kernel, a, im.ranges, b.vals, g.rec, im.final_T, im.n_contrib, out_feature, out_depth, out_normal,
-                  contrib_sum, contrib_max);
+    TS_LAUNCH_BLEND(render_fwd_group_kernel, a, ts_tile_units(a.grid_x, a.grid_y), 256, s, a, im.ranges, b.vals, g.rec, im.final_T, im.n_contrib,
+                    out_feature, out_depth, out_normal, contrib_sum, contrib_max);
 }
 
 #endif // TSG_PART & 1
@@ -725,17 +497,8 @@ void ts_launch_render_bwd_group(const RenderArgs &a, const GeometryStateView &g,
                                 const float *dL_dout_feature, const float *dL_dout_depth, const float *dL_dout_normal, float *grad_rec,
                                 hipStream_t s)
 {
-    const dim3 grid((unsigned)(a.grid_x * a.grid_y));
-    if (grid.x == 0) return;
-    constexpr int WPB = 1;
-    const dim3 grid1((unsigned)((WPB == 4 ? 1 : 4) * ts_tile_units(a.grid_x, a.grid_y))); // padded: units past the image return at once
-    const bool g1 = (a.gamma == 1.0f);
-#define TS_BWD(R, G) hipLaunchKernelGGL((render_bwd_group_kernel<R, G, WPB>), grid1, dim3(64 * WPB), 0, s, a, im.ranges, b.vals, g.rec, im.final_T, \
-                                        im.n_contrib, dL_dout_feature, dL_dout_depth, dL_dout_normal, grad_rec)
-    if (a.rich_info && g1) TS_BWD(true, true);
-    else if (a.rich_info) TS_BWD(true, false);
-    else if (g1) TS_BWD(false, true);
-    else TS_BWD(false, false);
-#undef TS_BWD
+    if (a.grid_x * a.grid_y == 0) return;
+    TS_LAUNCH_BLEND(render_bwd_group_kernel, a, ts_quadrant_units(a.grid_x, a.grid_y), 64, s, a, im.ranges, b.vals, g.rec, im.final_T, im.n_contrib,
+                    dL_dout_feature, dL_dout_depth, dL_dout_normal, grad_rec);
 }
 #endif // TSG_PART & 2

@@ -18,6 +18,9 @@ A "ground truth" is rendered from a hidden set of triangles from several cameras
     python examples/train_synthetic.py --world 2 [--exchange dense|factored_sh] [--check-every 50]
     python examples/train_synthetic.py --eval-mesh      after training, score the OPAQUE mesh of the model (what saveGLB would export, rendered
                                                         by diff_recon_hip.MeshRenderer) on the training views: PSNR / SSIM per view and their means
+    python examples/train_synthetic.py --eval-mesh --refine-mesh
+                                                        then census that mesh over the same views (diff_recon_hip.MeshCensus), drop the triangles
+                                                        that win no pixel, bake every face's colour from the pixels it wins, and score it again
 """
 import argparse
 import math
@@ -189,14 +192,23 @@ def train(rasterizer="2D", iters=200, triangles=20000, width=256, height=192, se
     return [float(x) for x in torch.stack(losses).cpu()], m, sec
 
 
-def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, height=192, seed=0, views=2):
+def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, height=192, seed=0, views=2, refine=False):
     """PSNR / SSIM of the model's opaque mesh -- mesh_from_triangles: one colour per face from the DC coefficients, back faces as reversed
-    twins, the soup saveGLB writes -- against the hidden targets of train() called with the same arguments (diff_recon_hip.evaluate_mesh)."""
+    twins, the soup saveGLB writes -- against the hidden targets of train() called with the same arguments (diff_recon_hip.evaluate_mesh).
+    refine: the result also holds "refined", the same scores (plus "kept" and "triangles") of the mesh after a census over these views
+    (diff_recon_hip.MeshCensus): the triangles that win no pixel from any view dropped (visible_triangle_mask), every remaining triangle
+    coloured with the mean of the target pixels it wins (bake_face_colors).  The views are the training views: a fit, not a generalisation."""
     _, _, cams, gts, kw, _, _ = _setup(rasterizer, iters, triangles, width, height, seed, views, 0.0, False, False)
     for cam, gt in zip(cams, gts):
         cam.gt_image = gt
     shs = m._shs if m.single_sh else m._f_dc
-    return D.evaluate_mesh(cams, *D.mesh_from_triangles(m._vertex, shs), bg_color=kw["bg_color"])
+    res = D.evaluate_mesh(cams, *D.mesh_from_triangles(m._vertex, shs), bg_color=kw["bg_color"])
+    if refine:
+        keep = D.visible_triangle_mask(cams, m._vertex, shs)
+        vertices, faces, color = D.mesh_from_triangles(m._vertex[keep], shs[keep])
+        color = D.bake_face_colors(cams, vertices, faces, color, twin_period=int(keep.sum()))
+        res["refined"] = dict(D.evaluate_mesh(cams, vertices, faces, color, bg_color=kw["bg_color"]), kept=int(keep.sum()), triangles=int(keep.numel()))
+    return res
 
 
 # ---- image-parallel: the same training over N processes (diff_recon_hip/multirank.py) ------------------------------------------------------
@@ -336,7 +348,12 @@ if __name__ == "__main__":
     ap.add_argument("--exchange", default="dense", choices=["dense", "factored_sh"], help="--world: how the colour gradients travel between the ranks")
     ap.add_argument("--check-every", type=int, default=50, help="--world: iterations between two replica-guard checks (one is forced after every structural update)")
     ap.add_argument("--eval-mesh", action="store_true", help="after training, render the model as an opaque mesh (diff_recon_hip.MeshRenderer) from the training views and print PSNR / SSIM")
+    ap.add_argument("--refine-mesh", action="store_true", help="with --eval-mesh: drop the triangles that win no pixel from any view and give every face the mean colour of the "
+                                                               "pixels it wins (diff_recon_hip.MeshCensus), then print the triangles kept and the PSNR / SSIM of that mesh. The views "
+                                                               "are the training views, so the figure is a fit and not a generalisation")
     a = ap.parse_args()
+    if a.refine_mesh and not a.eval_mesh:
+        ap.error("--refine-mesh refines the mesh that --eval-mesh scores")
     if a.eval_mesh and a.world is not None:
         ap.error("--eval-mesh scores the model of the one-process loop (with --world the trained replicas live in the rank processes)")
     parallel = {} if a.world is None else dict(world=a.world, exchange=a.exchange, check_every=a.check_every,
@@ -347,7 +364,11 @@ if __name__ == "__main__":
         print("  update", row)
     print(f"{a.rasterizer}: loss {losses[0]:.5f} -> {losses[-1]:.5f} in {a.iters} iterations, {sec * 1e3:.2f} ms/iteration (incl. Python)")
     if a.eval_mesh:
-        res = mesh_scores(m, a.rasterizer, a.iters, a.triangles, views=a.views)
+        res = mesh_scores(m, a.rasterizer, a.iters, a.triangles, views=a.views, refine=a.refine_mesh)
         for v, (p_, s_) in enumerate(zip(res["psnr"], res["ssim"])):
             print(f"  opaque mesh, view {v}: PSNR {p_:.2f} dB  SSIM {s_:.4f}")
         print(f"opaque mesh of {m._vertex.shape[0]} triangles: mean PSNR {res['mean_psnr']:.2f} dB, mean SSIM {res['mean_ssim']:.4f} over {len(res['psnr'])} views")
+        if a.refine_mesh:
+            r = res["refined"]
+            print(f"refined mesh: {r['kept']} of {r['triangles']} triangles win a pixel from one of the {len(r['psnr'])} training views and are kept")
+            print(f"refined mesh, colours baked from those views: mean PSNR {r['mean_psnr']:.2f} dB, mean SSIM {r['mean_ssim']:.4f} (a fit to the training views)")

@@ -47,6 +47,7 @@ SOURCES = {
     "preprocess3d.hip": ["-ffp-contract=off"],
     "mesh_preprocess.hip": ["-ffp-contract=off"],  # the opaque mesh renderer (include/ts_mesh.h): per-face setup ...
     "mesh_resolve.hip": ["-ffp-contract=off"],     # ... and the per-pixel depth test (what is fused there is written as fmaf)
+    "mesh_census.hip": [],                         # the per-face census over face_idx (integer sums; nothing to contract)
     "shgrad.hip": ["-ffp-contract=off"],
     "photometric.hip": [],
     "depth_normal.hip": ["-ffp-contract=off"],

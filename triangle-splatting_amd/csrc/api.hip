@@ -1453,4 +1453,22 @@ int ts2d_mesh_render(const ts2d_camera *cam, int32_t F, const float *faces_color
 {
     return ts2d_mesh_render_counted(cam, F, faces_color, background, N, state, render, mask, depth, face_idx, nullptr, stream);
 }
+
+int ts2d_mesh_census_add(int32_t width, int32_t height, int32_t F, const int32_t *face_idx, const float *target, const float *pixel_mask,
+                         unsigned long long *census, void *stream)
+{
+    if (width < 1 || height < 1) return fail(TS2D_ERR_INVALID, "image size must be positive");
+    if ((int64_t)width * height > 0x7fffffffll) return fail(TS2D_ERR_INVALID, "image too large: the census sweeps at most 2^31 - 1 pixels");
+    if (F < 0) return fail(TS2D_ERR_INVALID, "F must be >= 0");
+    if (!face_idx) return fail(TS2D_ERR_INVALID, "face_idx is null");
+    if (F == 0) return TS2D_OK; // no row to add to
+    if (!census) return fail(TS2D_ERR_INVALID, "census is null");
+    hipStream_t s = (hipStream_t)stream;
+    {
+        ProfScope ps("mesh_census", s);
+        ts_launch_mesh_census(width, height, F, face_idx, target, pixel_mask, census, s);
+    }
+    TS_CHECK(0u, s, "mesh_census");
+    return TS2D_OK;
+}
 } // extern "C"

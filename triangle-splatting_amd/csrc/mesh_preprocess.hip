@@ -31,7 +31,15 @@ __global__ void __launch_bounds__(256) mesh_preprocess_kernel(MeshArgs a, Geomet
 #pragma unroll
     for (int i = 0; i < TS_REC_FLOATS; i++) rec[i] = 0.0f;
 
-    const int32_t i1 = a.faces[3 * (size_t)f], i2 = a.faces[3 * (size_t)f + 1], i3 = a.faces[3 * (size_t)f + 2];
+    // The record is built from the face's vertices in ASCENDING INDEX order, whatever order `faces` names them in: neither coverage nor depth
+    // depends on the winding (no back-face culling; mesh_resolve.hip orients the edges itself), and a reversed twin -- the back face saveGLB
+    // appends with the same three indices -- then gets its front face's record bit for bit.  Same coverage, same depth on every pixel: the
+    // tie goes to the smaller index and a twin never wins a pixel (include/ts_mesh.h).  A face that already names its vertices in ascending
+    // order, as every front face of an un-shared soup does, is untouched.
+    int32_t i1 = a.faces[3 * (size_t)f], i2 = a.faces[3 * (size_t)f + 1], i3 = a.faces[3 * (size_t)f + 2];
+    if (i1 > i2) { const int32_t t = i1; i1 = i2; i2 = t; }
+    if (i2 > i3) { const int32_t t = i2; i2 = i3; i3 = t; }
+    if (i1 > i2) { const int32_t t = i1; i1 = i2; i2 = t; }
     do
     {
         if ((uint32_t)i1 >= (uint32_t)a.V || (uint32_t)i2 >= (uint32_t)a.V || (uint32_t)i3 >= (uint32_t)a.V) break; // never read out of bounds

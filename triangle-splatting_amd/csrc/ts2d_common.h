@@ -324,6 +324,9 @@ void ts_launch_mesh_preprocess(const MeshArgs &a, const GeometryStateView &g, hi
 void ts_launch_mesh_resolve(const MeshArgs &a, const GeometryStateView &g, const BinningStateView &b, const ImageStateView &im,
                             const float *faces_color, const float *background, float *render, float *mask, float *depth, int32_t *face_idx,
                             unsigned long long *wave_visits, hipStream_t s);
+// per-face census over a face_idx image (mesh_census.hip): rows of {pixels, sum_r, sum_g, sum_b} in 64-bit integers; F > 0, W * H < 2^31
+void ts_launch_mesh_census(int W, int H, int F, const int32_t *face_idx, const float *target, const float *pixel_mask, unsigned long long *census,
+                           hipStream_t s);
 
 // ---- factored SH-gradient exchange (multi-GPU, shgrad.hip) ---------------------------------------------------------
 void ts_launch_sh_grad_expand(int P, int D, int M, int V, const float *vertex, const float *campos, const float *dL_dcolor,

@@ -30,6 +30,9 @@
     mesh_renderer.py      MeshRenderer (the opaque z-buffer look at an exported mesh: constructor, `render` signature and results of KaolinRenderer,
                           plus depth and face_idx) and mesh_from_triangles (the mesh saveGLB would write, on the device)
                           (reference: src/diff_recon/renderer/kaolin_renderer.py:8-72, src/diff_recon/models/raw_triangle.py:183-209)
+    mesh_census.py        MeshCensus (per-face pixel counts and fixed-point colour sums over the face_idx images of many views, in integers:
+                          bit-identical in any view order), bake_face_colors (every face takes the mean of the target pixels it wins) and
+                          visible_triangle_mask (multi-view visibility pruning of an exported mesh) -- no counterpart in the reference
     metrics.py            psnr, ssim (= 1 - SSIMLoss) and evaluate_mesh: PSNR / SSIM of a mesh's opaque render against each view's gt_image
                           (reference: src/diff_recon/trainers/trainer_utils.py:331-336, VanillaTS_trainer.py:156-190)
     graphed.py            GraphedStep: a whole training step (sync-free forward, loss, backward, optimizer) captured once into a HIP graph and
@@ -51,4 +54,5 @@ from .model_init import create_from_pcd, grid_sampling, grid_size_search, get_in
 from .multirank import (ImageParallelLoop, ReplicaGuard, ReplicaDivergence, state_digest, state_digest_reference, digest_segments,  # noqa: F401
                         replicated_state, MAX_DIGEST_SEGMENTS)
 from .mesh_renderer import MeshRenderer, mesh_from_triangles  # noqa: F401
+from .mesh_census import MeshCensus, bake_face_colors, visible_triangle_mask  # noqa: F401
 from .metrics import psnr, ssim, evaluate_mesh  # noqa: F401

@@ -85,6 +85,8 @@ class MeshRenderer:
     A face is drawn iff its three vertices have view-space depth > znear (kaolin_renderer.py:51; no clipping, no back-face culling).  A
     pixel is covered by a face when its centre (i + 0.5, j + 0.5) lies inside or on the projected triangle; the nearest covering face
     wins, ties go to the smaller face index, so the result is a pure function of the inputs (bit-identical from run to run).
+    Coverage and depth do not depend on the order in which a face names its vertices (its record is built in ascending index order), so
+    a reversed back twin of a face ties with it on every pixel and never wins one.
     The depth of a face at a pixel is the ray / plane intersection in view space (perspective-correct).  Whether Kaolin's backend
     interpolates z this way or linearly in screen space could not be checked (the library is not installable on this platform);
     `render` and `mask` depend on that choice only where triangles interpenetrate.

@@ -91,6 +91,22 @@ class RawTriangle:
     def shDegree(self):  # raw_triangle.py:52-54
         return int(np.sqrt(self.shs.shape[1] / 3) - 1)
 
+    def __getitem__(self, key):  # raw_triangle.py:58-63: numpy indexing of the three arrays; a boolean mask keeps the rows it marks
+        key = np.asarray(key.detach().cpu().numpy() if hasattr(key, "detach") else key)
+        if key.dtype == np.bool_ and key.shape != (len(self),):
+            raise IndexError(f"a boolean mask must have one entry per triangle ({len(self)}), not shape {key.shape}")
+        return RawTriangle(self.vertex[key], self.opacity[key], self.shs[key])
+
+    def with_face_colors(self, rgb):
+        """A copy whose DC coefficients are RGB2SH(rgb) (`rgb` (P, 3), e.g. diff_recon_hip.bake_face_colors' result for the front faces):
+        saveGLB then writes exactly these colours.  The higher SH coefficients are kept."""
+        rgb = np.asarray(rgb.detach().cpu().numpy() if hasattr(rgb, "detach") else rgb)
+        if rgb.shape != (len(self), 3):
+            raise ValueError(f"rgb must have dimensions ({len(self)}, 3)")
+        shs = np.array(self.shs, copy=True)
+        shs[:, :3] = RGB2SH(rgb.astype(shs.dtype))
+        return RawTriangle(np.array(self.vertex, copy=True), np.array(self.opacity, copy=True), shs)
+
     # ---- PLY ---------------------------------------------------------------------------------------------------------------
     def loadPLY(self, path):  # raw_triangle.py:124-154
         if not os.path.exists(path):

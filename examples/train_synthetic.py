@@ -21,6 +21,9 @@ A "ground truth" is rendered from a hidden set of triangles from several cameras
     python examples/train_synthetic.py --eval-mesh --refine-mesh
                                                         then census that mesh over the same views (diff_recon_hip.MeshCensus), drop the triangles
                                                         that win no pixel, bake every face's colour from the pixels it wins, and score it again
+    python examples/train_synthetic.py --eval-mesh --weld-mesh EPS
+                                                        then weld the front faces of that mesh (diff_recon_hip.weld_mesh), print V -> V', the faces
+                                                        dropped, the topology and the largest cluster, and score the welded mesh beside the soup
 """
 import argparse
 import math
@@ -192,12 +195,15 @@ def train(rasterizer="2D", iters=200, triangles=20000, width=256, height=192, se
     return [float(x) for x in torch.stack(losses).cpu()], m, sec
 
 
-def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, height=192, seed=0, views=2, refine=False):
+def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, height=192, seed=0, views=2, refine=False, weld=None):
     """PSNR / SSIM of the model's opaque mesh -- mesh_from_triangles: one colour per face from the DC coefficients, back faces as reversed
     twins, the soup saveGLB writes -- against the hidden targets of train() called with the same arguments (diff_recon_hip.evaluate_mesh).
     refine: the result also holds "refined", the same scores (plus "kept" and "triangles") of the mesh after a census over these views
     (diff_recon_hip.MeshCensus): the triangles that win no pixel from any view dropped (visible_triangle_mask), every remaining triangle
-    coloured with the mean of the target pixels it wins (bake_face_colors).  The views are the training views: a fit, not a generalisation."""
+    coloured with the mean of the target pixels it wins (bake_face_colors).  The views are the training views: a fit, not a generalisation.
+    weld = EPS: the result also holds "welded": the front faces of the mesh scored last (the refined one with `refine`) welded with
+    diff_recon_hip.weld_mesh(eps=EPS) -- its scores, the weld's "stats", the "topology" of the welded front faces and "soup", the scores of the
+    mesh it was welded from.  The renderer culls nothing, so the front faces alone draw what the soup with its back twins draws."""
     _, _, cams, gts, kw, _, _ = _setup(rasterizer, iters, triangles, width, height, seed, views, 0.0, False, False)
     for cam, gt in zip(cams, gts):
         cam.gt_image = gt
@@ -208,7 +214,28 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
         vertices, faces, color = D.mesh_from_triangles(m._vertex[keep], shs[keep])
         color = D.bake_face_colors(cams, vertices, faces, color, twin_period=int(keep.sum()))
         res["refined"] = dict(D.evaluate_mesh(cams, vertices, faces, color, bg_color=kw["bg_color"]), kept=int(keep.sum()), triangles=int(keep.numel()))
+    if weld is not None:
+        soup = res["refined"] if refine else res
+        if not refine:
+            vertices, faces, color = D.mesh_from_triangles(m._vertex, shs)
+        front = faces.shape[0] // 2  # mesh_from_triangles: the back twins follow the front faces
+        w = D.weld_mesh(vertices, faces[:front], color[:front], eps=weld)
+        res["welded"] = dict(D.evaluate_mesh(cams, w.vertices, w.faces, w.faces_color, bg_color=kw["bg_color"]), stats=w.stats,
+                             topology=D.mesh_topology(w.stats["num_vertices"], w.faces), eps=float(weld),
+                             soup={k: soup[k] for k in ("mean_psnr", "mean_ssim")})
     return res
+
+
+def weld_report(welded):
+    """The lines --weld-mesh prints for mesh_scores(...)["welded"]."""
+    s, t = welded["stats"], welded["topology"]
+    return [f"welded mesh, eps {welded['eps']:g}: vertices {s['num_vertices_in']} -> {s['num_vertices']}, "
+            f"{s['num_faces_in'] - s['num_faces']} of {s['num_faces_in']} faces dropped",
+            f"welded mesh topology: {t['edges']} edges ({t['boundary']} boundary, {t['manifold']} manifold, {t['nonmanifold']} non-manifold), "
+            f"{t['pieces']} pieces, Euler characteristic {t['euler']}",
+            f"welded mesh, largest cluster: {s['largest_cluster']} vertices, largest displacement {s['max_displacement']:.3g}",
+            f"welded mesh: mean PSNR {welded['mean_psnr']:.2f} dB, mean SSIM {welded['mean_ssim']:.4f} "
+            f"(the soup: {welded['soup']['mean_psnr']:.2f} dB, {welded['soup']['mean_ssim']:.4f})"]
 
 
 # ---- image-parallel: the same training over N processes (diff_recon_hip/multirank.py) ------------------------------------------------------
@@ -351,7 +378,12 @@ if __name__ == "__main__":
     ap.add_argument("--refine-mesh", action="store_true", help="with --eval-mesh: drop the triangles that win no pixel from any view and give every face the mean colour of the "
                                                                "pixels it wins (diff_recon_hip.MeshCensus), then print the triangles kept and the PSNR / SSIM of that mesh. The views "
                                                                "are the training views, so the figure is a fit and not a generalisation")
+    ap.add_argument("--weld-mesh", type=float, default=None, metavar="EPS", help="with --eval-mesh: weld the front faces of the mesh scored last (diff_recon_hip.weld_mesh: "
+                                                                                 "vertices within EPS of each other merge, transitively) and print V -> V', the faces dropped, "
+                                                                                 "the topology, the largest cluster and the welded mesh's PSNR / SSIM beside the soup's")
     a = ap.parse_args()
+    if a.weld_mesh is not None and not a.eval_mesh:
+        ap.error("--weld-mesh welds the mesh that --eval-mesh scores")
     if a.refine_mesh and not a.eval_mesh:
         ap.error("--refine-mesh refines the mesh that --eval-mesh scores")
     if a.eval_mesh and a.world is not None:
@@ -364,7 +396,7 @@ if __name__ == "__main__":
         print("  update", row)
     print(f"{a.rasterizer}: loss {losses[0]:.5f} -> {losses[-1]:.5f} in {a.iters} iterations, {sec * 1e3:.2f} ms/iteration (incl. Python)")
     if a.eval_mesh:
-        res = mesh_scores(m, a.rasterizer, a.iters, a.triangles, views=a.views, refine=a.refine_mesh)
+        res = mesh_scores(m, a.rasterizer, a.iters, a.triangles, views=a.views, refine=a.refine_mesh, weld=a.weld_mesh)
         for v, (p_, s_) in enumerate(zip(res["psnr"], res["ssim"])):
             print(f"  opaque mesh, view {v}: PSNR {p_:.2f} dB  SSIM {s_:.4f}")
         print(f"opaque mesh of {m._vertex.shape[0]} triangles: mean PSNR {res['mean_psnr']:.2f} dB, mean SSIM {res['mean_ssim']:.4f} over {len(res['psnr'])} views")
@@ -372,3 +404,6 @@ if __name__ == "__main__":
             r = res["refined"]
             print(f"refined mesh: {r['kept']} of {r['triangles']} triangles win a pixel from one of the {len(r['psnr'])} training views and are kept")
             print(f"refined mesh, colours baked from those views: mean PSNR {r['mean_psnr']:.2f} dB, mean SSIM {r['mean_ssim']:.4f} (a fit to the training views)")
+        if a.weld_mesh is not None:
+            for line in weld_report(res["welded"]):
+                print(line)

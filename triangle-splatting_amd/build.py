@@ -48,6 +48,7 @@ SOURCES = {
     "mesh_preprocess.hip": ["-ffp-contract=off"],  # the opaque mesh renderer (include/ts_mesh.h): per-face setup ...
     "mesh_resolve.hip": ["-ffp-contract=off"],     # ... and the per-pixel depth test (what is fused there is written as fmaf)
     "mesh_census.hip": [],                         # the per-face census over face_idx (integer sums; nothing to contract)
+    "mesh_weld.hip": ["-ffp-contract=off"],        # vertex welding and edge topology (include/ts_weld.h): the fp32 pair test rounds every operation
     "shgrad.hip": ["-ffp-contract=off"],
     "photometric.hip": [],
     "depth_normal.hip": ["-ffp-contract=off"],
@@ -73,12 +74,13 @@ LAB_SOURCES = {  # libts2d_lab.so only
 BIN_DIR = os.path.join(os.path.dirname(HERE), "tools", "bin")
 LAB_LIB = os.path.join(BIN_DIR, "libts2d_lab.so")
 LAB_SRC = os.path.join(os.path.dirname(HERE), "tools", "lab")  # lab_hooks.hip: the test hooks, outside the product's csrc/; it includes csrc's headers (-I)
-HEADERS = ["ts2d_common.h", "ts2d_lab.h", "ts2d_math.h", "ts2d_wave.h", "ts2d_group.h", "ts2d_support.h", "ts2d_sh.h", "ts2d_stage.h", "ts2d_preprocess_launch.h", "ts2d_imgops.h", "ts2d_select.h", "ts2d_tri.h", os.path.join("..", "..", "include", "ts2d.h"),
+HEADERS = ["ts2d_common.h", "ts_knn_front.h", "ts_weld_launch.h", "ts2d_lab.h", "ts2d_math.h", "ts2d_wave.h", "ts2d_group.h", "ts2d_support.h", "ts2d_sh.h", "ts2d_stage.h", "ts2d_preprocess_launch.h", "ts2d_imgops.h", "ts2d_select.h", "ts2d_tri.h", os.path.join("..", "..", "include", "ts2d.h"),
            os.path.join("..", "..", "include", "ts_loss.h"),
            os.path.join("..", "..", "include", "ts_knn.h"),
            os.path.join("..", "..", "include", "ts_model.h"),
            os.path.join("..", "..", "include", "ts_optim.h"),
-           os.path.join("..", "..", "include", "ts_mesh.h")]
+           os.path.join("..", "..", "include", "ts_mesh.h"),
+           os.path.join("..", "..", "include", "ts_weld.h")]
 
 
 def hipcc() -> str:

@@ -13,14 +13,17 @@
 #include "../../include/ts_model.h"
 #include "../../include/ts_optim.h"
 #include "../../include/ts_mesh.h"
+#include "../../include/ts_weld.h"
 #ifdef TS2D_LAB
 #include "ts2d_lab.h"
 #endif
 #pragma GCC visibility pop
 #include "ts2d_common.h"
+#include "ts_weld_launch.h"
 #include <atomic>
 #include <chrono>
 
+#include <cfloat>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -1469,6 +1472,96 @@ int ts2d_mesh_census_add(int32_t width, int32_t height, int32_t F, const int32_t
         ts_launch_mesh_census(width, height, F, face_idx, target, pixel_mask, census, s);
     }
     TS_CHECK(0u, s, "mesh_census");
+    return TS2D_OK;
+}
+
+// ---- include/ts_weld.h ------------------------------------------------------------------------------------------------
+#define TS_WELD_MAX_FACES 715827882 /* 3 F edge slots are addressed with 31 bits */
+
+size_t ts2d_weld_workspace_bytes(int32_t V, int32_t F) { return ts_weld_workspace_bytes(V, F); }
+
+static int weld_counts_ok(int32_t V, int32_t F)
+{
+    if (V < 0) return fail(TS2D_ERR_INVALID, "V must be >= 0");
+    if (F < 0) return fail(TS2D_ERR_INVALID, "F must be >= 0");
+    if (F > TS_WELD_MAX_FACES) return fail(TS2D_ERR_INVALID, "F must be at most %d", TS_WELD_MAX_FACES);
+    return TS2D_OK;
+}
+
+static int weld_workspace_ok(int32_t V, int32_t F, const void *workspace, size_t workspace_bytes)
+{
+    if (!workspace) return fail(TS2D_ERR_INVALID, "workspace is null");
+    if (workspace_bytes < ts_weld_workspace_bytes(V, F)) return fail(TS2D_ERR_INVALID, "weld workspace too small");
+    return TS2D_OK;
+}
+
+int ts2d_weld_labels_counted(int32_t V, const float *vertices, float eps, int32_t *label, unsigned long long *box_visits, void *workspace,
+                             size_t workspace_bytes, void *stream)
+{
+    if (int rc = weld_counts_ok(V, 0)) return rc;
+    if (!(eps >= 0.0f) || !(eps <= FLT_MAX)) return fail(TS2D_ERR_INVALID, "eps must be finite and >= 0");
+    if (V == 0) return TS2D_OK;
+    if (!vertices || !label) return fail(TS2D_ERR_INVALID, "null pointer");
+    if (int rc = weld_workspace_ok(V, 0, workspace, workspace_bytes)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps("weld_labels", s);
+    TS_HIP(ts_weld_labels(V, vertices, eps, (uint32_t *)label, box_visits, workspace, s));
+    return TS2D_OK;
+}
+
+int ts2d_weld_labels(int32_t V, const float *vertices, float eps, int32_t *label, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return ts2d_weld_labels_counted(V, vertices, eps, label, nullptr, workspace, workspace_bytes, stream);
+}
+
+int ts2d_weld_face_components(int32_t V, int32_t F, const int32_t *faces, const uint8_t *keep, int32_t *label, void *workspace,
+                              size_t workspace_bytes, void *stream)
+{
+    (void)workspace; (void)workspace_bytes; // the union-find works in `label` itself
+    if (int rc = weld_counts_ok(V, F)) return rc;
+    if (V == 0) return TS2D_OK;
+    if (!label || (F > 0 && !faces)) return fail(TS2D_ERR_INVALID, "null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps("weld_face_components", s);
+    TS_HIP(ts_weld_face_components(V, F, faces, keep, (uint32_t *)label, s));
+    return TS2D_OK;
+}
+
+int ts2d_weld_compact(int32_t V, const int32_t *label, const float *vertices, int32_t mode, int32_t *remap, float *out_vertices,
+                      int32_t *count, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (int rc = weld_counts_ok(V, 0)) return rc;
+    if (mode != TS2D_WELD_FIRST && mode != TS2D_WELD_MEAN) return fail(TS2D_ERR_INVALID, "mode must be TS2D_WELD_FIRST or TS2D_WELD_MEAN");
+    if (V == 0) return TS2D_OK;
+    if (!label || !vertices || !remap || !out_vertices || !count) return fail(TS2D_ERR_INVALID, "null pointer");
+    if (int rc = weld_workspace_ok(V, 0, workspace, workspace_bytes)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps("weld_compact", s);
+    TS_HIP(ts_weld_compact(V, (const uint32_t *)label, vertices, mode, remap, out_vertices, count, workspace, s));
+    return TS2D_OK;
+}
+
+int ts2d_weld_remap_faces(int32_t V, int32_t F, const int32_t *faces, const int32_t *remap, int32_t *out_faces, uint8_t *keep, void *stream)
+{
+    if (int rc = weld_counts_ok(V, F)) return rc;
+    if (F == 0) return TS2D_OK;
+    if (!faces || !out_faces || !keep || (V > 0 && !remap)) return fail(TS2D_ERR_INVALID, "null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps("weld_remap_faces", s);
+    TS_HIP(ts_weld_remap_faces(V, F, faces, remap, out_faces, keep, s));
+    return TS2D_OK;
+}
+
+int ts2d_weld_edge_census(int32_t V, int32_t F, const int32_t *faces, const uint8_t *keep, unsigned long long *counts, void *workspace,
+                          size_t workspace_bytes, void *stream)
+{
+    if (int rc = weld_counts_ok(V, F)) return rc;
+    if (F == 0) return TS2D_OK;
+    if (!faces || !counts) return fail(TS2D_ERR_INVALID, "null pointer");
+    if (int rc = weld_workspace_ok(V, F, workspace, workspace_bytes)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps("weld_edge_census", s);
+    TS_HIP(ts_weld_edge_census(V, F, faces, keep, counts, workspace, s));
     return TS2D_OK;
 }
 } // extern "C"

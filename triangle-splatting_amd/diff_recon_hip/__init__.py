@@ -33,12 +33,16 @@
     mesh_census.py        MeshCensus (per-face pixel counts and fixed-point colour sums over the face_idx images of many views, in integers:
                           bit-identical in any view order), bake_face_colors (every face takes the mean of the target pixels it wins) and
                           visible_triangle_mask (multi-view visibility pruning of an exported mesh) -- no counterpart in the reference
+    mesh_weld.py          weld_mesh (all vertices within eps of each other merged transitively: renumbered vertices, remapped faces, collapsed
+                          faces dropped; a pure function of the input) and mesh_topology (boundary / manifold / non-manifold edges, pieces, Euler
+                          characteristic) -- the counterpart of saveGLB(..., process=True)
+                          (reference: src/diff_recon/models/raw_triangle.py:183-207, trimesh's vertex merging)
     metrics.py            psnr, ssim (= 1 - SSIMLoss) and evaluate_mesh: PSNR / SSIM of a mesh's opaque render against each view's gt_image
                           (reference: src/diff_recon/trainers/trainer_utils.py:331-336, VanillaTS_trainer.py:156-190)
     graphed.py            GraphedStep: a whole training step (sync-free forward, loss, backward, optimizer) captured once into a HIP graph and
                           replayed with one launch -- no counterpart in the reference, whose forward reads num_rendered back every step
 
-Native code: libts2d.so (include/ts_loss.h, include/ts_model.h, include/ts_optim.h, include/ts2d.h, include/ts_mesh.h).  No CPU / eager fallback anywhere.
+Native code: libts2d.so (include/ts_loss.h, include/ts_model.h, include/ts_optim.h, include/ts2d.h, include/ts_mesh.h, include/ts_weld.h).  No CPU / eager fallback anywhere.
 """
 from .losses import L1, SSIMLoss, ssimLoss, PhotometricLoss, photometric_loss, DepthNormalLoss, DoGLoss, SmoothnessLoss, dogLoss, smoothnessLoss, downsample_bilinear, downsample_bilinear_many  # noqa: F401
 from .triangle_renderer import TriangleRenderer  # noqa: F401
@@ -55,4 +59,5 @@ from .multirank import (ImageParallelLoop, ReplicaGuard, ReplicaDivergence, stat
                         replicated_state, MAX_DIGEST_SEGMENTS)
 from .mesh_renderer import MeshRenderer, mesh_from_triangles  # noqa: F401
 from .mesh_census import MeshCensus, bake_face_colors, visible_triangle_mask  # noqa: F401
+from .mesh_weld import WeldedMesh, weld_mesh, mesh_topology  # noqa: F401
 from .metrics import psnr, ssim, evaluate_mesh  # noqa: F401

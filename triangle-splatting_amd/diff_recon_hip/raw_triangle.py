@@ -144,17 +144,26 @@ class RawTriangle:
             f.write(rows.tobytes())
 
     # ---- GLB ---------------------------------------------------------------------------------------------------------------
-    def saveGLB(self, path, save_empty=False, save_back=True, process=False):  # raw_triangle.py:183-209
+    def saveGLB(self, path, save_empty=False, save_back=True, process=False, weld_eps=0.0):  # raw_triangle.py:183-209
+        """process=False (the reference's default): every triangle keeps three private vertices, as described in the module text.
+        process=True: the counterpart of the reference's trimesh vertex merging -- the front faces are welded on the HIP device
+        (diff_recon_hip.mesh_weld.weld_mesh: all vertices within `weld_eps` of each other merge, transitively; a RuntimeError without a
+        device, there is no CPU fallback) and an INDEXED mesh is written: POSITION holds the V' welded vertices, the indices are the kept
+        front faces (plus their reversed twins with `save_back`), COLOR_0 is the per-vertex mean of the RGBA of the incident kept front
+        faces (summed on the host in float64 in face order; a vertex that no kept face names is written as zeros).  Like the rest of this
+        file the path is UNPINNED against trimesh.  `loadGLB` cannot recover per-triangle data from a welded file (it reads private
+        vertices), as in the reference; diff_recon_hip.mesh_renderer.load_glb_mesh reads both layouts."""
         if not save_empty and len(self) == 0:
             return
-        if process:
-            raise NotImplementedError("process=True (trimesh's vertex merging) has no counterpart here; the reference's default is False")
-        Path(path).parent.mkdir(parents=True, exist_ok=True)
         P = len(self)
-        pos = np.ascontiguousarray(self.vertex.reshape(-1, 3), dtype="<f4")
         rgba = np.concatenate([np.clip(SH2RGB(self.shs[:, :3]), 0, 1), 1 / (1 + np.exp(-self.opacity.reshape(-1, 1)))], axis=1)
-        col = np.ascontiguousarray(np.repeat(np.round(rgba * 255).astype(np.uint8), 3, axis=0))  # one colour per face -> its three vertices
-        faces = np.arange(P * 3, dtype="<u4").reshape(-1, 3)
+        if process:
+            pos, faces, col = self._welded(rgba, float(weld_eps))
+        else:
+            pos = np.ascontiguousarray(self.vertex.reshape(-1, 3), dtype="<f4")
+            col = np.ascontiguousarray(np.repeat(np.round(rgba * 255).astype(np.uint8), 3, axis=0))  # one colour per face -> its three vertices
+            faces = np.arange(P * 3, dtype="<u4").reshape(-1, 3)
+        Path(path).parent.mkdir(parents=True, exist_ok=True)
         if save_back:
             faces = np.concatenate([faces, faces[:, ::-1]], axis=0)
         idx = np.ascontiguousarray(faces.reshape(-1), dtype="<u4")
@@ -184,6 +193,25 @@ class RawTriangle:
             f.write(struct.pack("<4sII", b"glTF", 2, 12 + 8 + len(js) + 8 + len(binary)))
             f.write(struct.pack("<I4s", len(js), b"JSON") + js)
             f.write(struct.pack("<I4s", len(binary), b"BIN\x00") + binary)
+
+    def _welded(self, rgba, weld_eps):
+        """(positions (V', 3) <f4, kept front faces (F', 3) <u4, per-vertex colours (V', 4) uint8) of saveGLB(process=True)."""
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("saveGLB(process=True) (MI355X build) welds the vertices on a HIP device; there is no CPU fallback")
+        from .mesh_weld import weld_mesh
+        device = torch.device("cuda", torch.cuda.current_device())
+        soup = torch.from_numpy(np.ascontiguousarray(self.vertex.reshape(-1, 3), dtype=np.float32)).to(device)
+        tri = torch.arange(soup.shape[0], device=device, dtype=torch.int32).reshape(-1, 3)
+        welded = weld_mesh(soup, tri, None, eps=weld_eps, position="first")
+        pos = np.ascontiguousarray(welded.vertices.cpu().numpy(), dtype="<f4")
+        faces = welded.faces.cpu().numpy().astype("<u4")
+        face_rgba = np.asarray(rgba, dtype=np.float64)[welded.face_keep.cpu().numpy()]
+        sums, count = np.zeros((len(pos), 4), np.float64), np.zeros((len(pos), 1), np.float64)
+        np.add.at(sums, faces.reshape(-1), np.repeat(face_rgba, 3, axis=0))  # unbuffered: in face order
+        np.add.at(count, faces.reshape(-1), 1.0)
+        col = np.ascontiguousarray(np.round(sums / np.maximum(count, 1.0) * 255).astype(np.uint8))
+        return pos, faces, col
 
     def loadGLB(self, path):  # raw_triangle.py:211-223
         if not os.path.exists(path):

@@ -216,8 +216,7 @@ __global__ void __launch_bounds__(256) aux_smooth_sum_kernel(int C, int H, int W
     const int HW = H * W;
     for (int k = blockIdx.x * 256 + threadIdx.x; k < HW; k += gridDim.x * 256)
     {
-        const float m = mask[k];
-        if (m == 0.0f) continue;
+        const float m = mask[k]; // (nrm * mask).mean(), trainer_utils.py:200: masked-out pixels are NOT skipped, a non-finite norm times 0 is NaN
         const int i = k / W, j = k - i * W;
         float q = 0.0f;
         for (int c = 0; c < C; c++)
@@ -246,7 +245,7 @@ __global__ void __launch_bounds__(256) aux_smooth_adj_kernel(int C, int H, int W
         scharr_sym(img + (size_t)c * HW, i, j, H, W, gx[c], gy[c]);
         q += gx[c] * gx[c] + gy[c] * gy[c];
     }
-    const float nrm = sqrtf(q), w = (m != 0.0f && nrm > 0.0f) ? go * m / ((float)HW * nrm) : 0.0f;
+    const float nrm = sqrtf(q), w = nrm == 0.0f ? 0.0f : go * m / ((float)HW * nrm); // (a NaN norm gives a NaN weight, masked out or not)
     for (int c = 0; c < C; c++)
     {
         adj[(size_t)(2 * c) * HW + k] = w * gx[c];

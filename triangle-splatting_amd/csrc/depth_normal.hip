@@ -79,14 +79,14 @@ __global__ void __launch_bounds__(256) dn_fullres_kernel(Dims m, const float *__
     fullres_normal(m, nraw, y, x, Nx, Ny, Nz);
     const float inv = 1.0f / sqrtf(Nx * Nx + Ny * Ny + Nz * Nz);
     const float nx = normal[k], ny = normal[HW + k], nz = normal[2 * HW + k];
-    const float nn = fmaxf(sqrtf(nx * nx + ny * ny + nz * nz), 1e-8f); // F.normalize(p = 2, dim = 0, eps = 1e-8)
+    const float len = sqrtf(nx * nx + ny * ny + nz * nz), nn = len < 1e-8f ? 1e-8f : len; // F.normalize(p = 2, dim = 0, eps = 1e-8); not fmaxf, which drops a NaN
     const float dot = (nx * Nx + ny * Ny + nz * Nz) * inv / nn;
     float g;
     if (m.h == m.H && m.w == m.W) g = gnorm[k];
     else g = bilerp(gnorm, m.w, tap_of(y, m.r_up_y, m.h), tap_of(x, m.r_up_x, m.w));
     G[k] = g;
     my_key = __float_as_uint(g);
-    Gkey[k] = my_key; // G >= 0: the bit pattern is monotone
+    Gkey[k] = my_key; // G >= 0: the bit pattern is monotone (a NaN is caught by the select's neighbour pass and makes the threshold NaN)
     t[k] = 1.0f - dot;
     }
     // (the select's first histogram pass was fused in here and taken out again: one key per thread means 256 global adds per 256 keys on the same 256
@@ -103,7 +103,12 @@ __global__ void __launch_bounds__(256) dn_sum_kernel(int HW, const float *__rest
     if (blockIdx.x == 0 && threadIdx.x == 0) *thr = th;
     double s = 0.0;
     for (int k = blockIdx.x * 256 + threadIdx.x; k < HW; k += gridDim.x * 256)
-        if (G[k] < th) s += (double)t[k];
+    {
+        // ((1 - dot) * mask).mean(): a masked-out pixel adds t * 0, which is 0 unless t is non-finite -- a NaN normal under the mask, or anywhere
+        // once the threshold itself is NaN, must reach the loss (trainer_utils.py:257)
+        const float tk = t[k];
+        s += (double)(G[k] < th ? tk : tk * 0.0f);
+    }
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
@@ -135,7 +140,7 @@ __global__ void __launch_bounds__(256) dn_bwd_fullres_kernel(Dims m, const float
     const float inv = 1.0f / sqrtf(Nx * Nx + Ny * Ny + Nz * Nz);
     const float Dx = Nx * inv, Dy = Ny * inv, Dz = Nz * inv;
     const float nx = normal[k], ny = normal[HW + k], nz = normal[2 * HW + k];
-    const float len = sqrtf(nx * nx + ny * ny + nz * nz), nn = fmaxf(len, 1e-8f);
+    const float len = sqrtf(nx * nx + ny * ny + nz * nz), nn = len < 1e-8f ? 1e-8f : len; // clamp_min keeps a NaN, fmaxf would hand back eps and a finite gradient
     const float hx = nx / nn, hy = ny / nn, hz = nz / nn;
     if (dN)
     {

@@ -8,6 +8,7 @@
 // EVERY block of the next launch for itself from the 256 totals (no single-block step, no host round trip).  One more pass counts the keys <= that
 // value and takes the minimum of the larger ones: the value of rank + 1 is the same value when it has duplicates, that minimum otherwise.
 // Exact by construction (integers only until the final lerp, which is at::lerp's expression as before).  Five streaming launches over 4 n bytes.
+// A NaN among the values makes the quantile NaN, as torch.quantile does: the neighbour pass, which reads every key anyway, raises SelState::has_nan.
 #include "ts2d_common.h"
 
 #include "ts2d_select.h"
@@ -34,6 +35,7 @@ __global__ void __launch_bounds__(SEL_BLOCK) sel_neighbour_kernel(const uint32_t
     sel_resolve(st, 4, rank, value, rem);
     unsigned long long le = 0;
     uint32_t mn = 0xffffffffu;
+    bool nan = false;
     const size_t base = (size_t)blockIdx.x * (SEL_BLOCK * SEL_ITEMS);
 #pragma unroll
     for (int i = 0; i < SEL_ITEMS; i++)
@@ -44,6 +46,7 @@ __global__ void __launch_bounds__(SEL_BLOCK) sel_neighbour_kernel(const uint32_t
             const uint32_t v = keys[k];
             le += v <= value ? 1u : 0u;
             mn = v > value ? min(mn, v) : mn;
+            nan |= (v & 0x7fffffffu) > 0x7f800000u;
         }
     }
 #pragma unroll
@@ -64,6 +67,7 @@ __global__ void __launch_bounds__(SEL_BLOCK) sel_neighbour_kernel(const uint32_t
         if (le) atomicAdd(&st->count_le, le);
         if (mn != 0xffffffffu) atomicMax(&st->max_not_gt, ~mn);
     }
+    if (__any(nan) && (threadIdx.x & 63) == 0) atomicOr(&st->has_nan, 1u); // never on a finite image: no cost where there is nothing to report
 }
 
 __global__ void __launch_bounds__(SEL_BLOCK) sel_threshold_kernel(size_t n, float q, const SelState *st, float *__restrict__ thr)

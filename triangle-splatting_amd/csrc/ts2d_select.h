@@ -12,7 +12,7 @@ struct SelState
     uint32_t hist[4][256]; // digit totals of pass p (most significant first), among the keys that match passes 0 .. p - 1
     unsigned long long count_le; // keys <= the selected value
     uint32_t max_not_gt;         // ~(smallest key > the selected value), kept complemented so that the all-zero state means "none"
-    uint32_t pad;
+    uint32_t has_nan;            // nonzero when a key is the bit pattern of a NaN: torch.quantile is then NaN (raised by the neighbour pass)
 };
 
 // (prefix, remaining rank) after `passes` passes, recomputed from the histograms by whoever needs it (256 threads, one block-wide scan per pass)
@@ -88,6 +88,8 @@ __device__ __forceinline__ float sel_threshold_value(const SelState *st, size_t 
     uint32_t value;
     unsigned long long rem;
     sel_resolve(st, 4, lo, value, rem);
+    // A NaN orders above +inf as a bit pattern and would leave a finite value at the rank; torch.quantile returns NaN as soon as one input is NaN
+    if (st->has_nan) return __uint_as_float(0x7fc00000u);
     const float rank = q * (float)(n - 1);
     unsigned long long hi = (unsigned long long)ceilf(rank);
     if (hi > n - 1) hi = n - 1;

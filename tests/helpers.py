@@ -111,23 +111,12 @@ def lab_library():
             raise RuntimeError(f"{LAB_LIB} not found: build it with `python triangle-splatting_amd/build.py --lab`")
         # the package first: the lab library carries the soname libts2d.so too, and the extension binds the first library of that name loaded
         from diff_triangle_rasterization_2D import _C as product
-        L = C.CDLL(LAB_LIB)
-        L.ts2d_last_error.restype = C.c_char_p
-        L.ts2d_debug_read_state.restype = C.c_int
-        L.ts2d_debug_read_state.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.ts2d_test_sort_pairs.restype = C.c_int
-        L.ts2d_test_sort_pairs.argtypes = [C.c_void_p] * 4 + [C.c_size_t, C.c_int32, C.c_int32, C.c_void_p]
-        L.ts2d_test_quantile_scratch_bytes.restype = C.c_size_t
-        L.ts2d_test_quantile.restype = C.c_int
-        L.ts2d_test_quantile.argtypes = [C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.ts2d_test_inclusive_scan_rocprim.restype = C.c_int
-        L.ts2d_test_inclusive_scan_rocprim.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.ts2d_lab_force_ticket_passes.argtypes = [C.c_int]
+        from diff_triangle_rasterization_2D import _abi
+        L = _abi.bind(C.CDLL(LAB_LIB))  # the product's signatures and those of csrc/ts2d_lab.h
         # same layout code as the product library?  (a lab library left over from before a change of csrc/ts2d_common.h decodes other offsets)
         for f, args in (("ts2d_geometry_state_bytes", (C.c_int32(12345),)), ("ts2d_binning_state_bytes", (C.c_int64(54321), C.c_int32(640), C.c_int32(480))),
                         ("ts2d_binning_state_bytes", (C.c_int64(7654321), C.c_int32(1920), C.c_int32(1080))), ("ts2d_image_state_bytes", (C.c_int32(640), C.c_int32(480)))):
             mine, theirs = getattr(L, f), getattr(product._lib, f)
-            mine.restype = theirs.restype = C.c_size_t
             if mine(*args) != theirs(*args):
                 raise RuntimeError(f"{LAB_LIB} is stale ({f} differs from the product library's): rebuild it with `python triangle-splatting_amd/build.py --lab`")
         _lab = L
@@ -158,10 +147,7 @@ def debug_read_state(name, P, num_rendered, W, H, geometryBuffer, binningBuffer,
     field, dtype, shape = _field_spec()[name]
     T = ((W + 15) // 16) * ((H + 15) // 16)
     out = torch.empty(shape(P, num_rendered, T, (H, W)), dtype=dtype)
-
-    class State(C.Structure):  # ts2d_state, include/ts2d.h
-        _fields_ = [("geometry", C.c_void_p), ("geometry_bytes", C.c_size_t), ("binning", C.c_void_p), ("binning_bytes", C.c_size_t),
-                    ("image", C.c_void_p), ("image_bytes", C.c_size_t)]
+    from diff_triangle_rasterization_2D._abi import _State as State
     ptr = lambda t: t.data_ptr() if t.numel() else None
     st = State(ptr(geometryBuffer), geometryBuffer.numel(), ptr(binningBuffer), binningBuffer.numel(), ptr(imageBuffer), imageBuffer.numel())
     with torch.cuda.device(geometryBuffer.device):

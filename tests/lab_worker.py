@@ -27,7 +27,6 @@ if os.environ.get("LAB_DEPTH_ORDER") == "1":
     # passes (reached through ts2d_lab_force_depth_pass4) and the hierarchical ticket passes (ts2d_lab_force_ticket_passes): the depth permutation,
     # the instance offsets (= block sums + scan), the instance count and the sorted instance list must be IDENTICAL.
     from diff_triangle_rasterization_2D import _C
-    _C._lib.ts2d_lab_force_depth_pass4.argtypes = [__import__("ctypes").c_int]
     # (round 6: the one-launch form is used up to 9 216 triangles, the sampled-splitter form above: the sizes straddle both switch-overs)
     for P, culled in [(1, False), (63, False), (64, False), (65, False), (1023, False), (9215, False), (9216, False), (9217, False), (12288, False), (12289, False), (700, True), (9216, True)]:
         s = synthetic.scene(P, 160, 96, 1, seed=500 + P)
@@ -60,9 +59,7 @@ if os.environ.get("LAB_DEPTH_SPLIT") == "1":
     # must be IDENTICAL, on scenes that bend the buckets: a third of the triangles culled (key 0), half of them at ONE depth (a bucket of equal
     # keys larger than the registers: the copy), depths quantised to 40 values (oversize buckets of few distinct keys), a far background (the
     # splitters follow the sample, not the key range), depths that cross several powers of four (the fourth LSD pass is not skipped).
-    import ctypes
     from diff_triangle_rasterization_2D import _C
-    _C._lib.ts2d_lab_depth_split.argtypes = [ctypes.c_int, ctypes.c_int]
 
     def bend(s, kind):
         v = s["vertex"]

@@ -14,7 +14,8 @@ HEADERS = [os.path.join(ROOT, "include", n) for n in sorted(os.listdir(os.path.j
 
 @pytest.fixture(scope="module")
 def lib(hip_lib_built):
-    return ctypes.CDLL(hip_lib_built)
+    from diff_triangle_rasterization_2D import _abi  # every signature is declared there, once; bound here on a CDLL of this module's own
+    return _abi.bind(ctypes.CDLL(hip_lib_built))
 
 
 def _declared_functions():
@@ -72,10 +73,6 @@ def test_product_library_exports_only_the_declared_c_abi(hip_lib_built):
 
 def test_binning_capacity_inverts_the_size_query(lib):
     """The layout of a binning buffer follows from its size: capacity(bytes(N)) >= N, bytes(capacity(b)) <= b, monotone."""
-    lib.ts2d_binning_state_bytes.restype = ctypes.c_size_t
-    lib.ts2d_binning_state_bytes.argtypes = [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]
-    lib.ts2d_binning_capacity.restype = ctypes.c_int64
-    lib.ts2d_binning_capacity.argtypes = [ctypes.c_size_t, ctypes.c_int32, ctypes.c_int32]
     last = -1
     for n in (0, 1, 63, 4096, 4097, 262_145, 4_610_735, 50_000_000):
         b = lib.ts2d_binning_state_bytes(n, 1920, 1080)
@@ -88,12 +85,6 @@ def test_binning_capacity_inverts_the_size_query(lib):
 
 
 def test_state_size_queries_are_monotone_and_aligned(lib):
-    lib.ts2d_geometry_state_bytes.restype = ctypes.c_size_t
-    lib.ts2d_geometry_state_bytes.argtypes = [ctypes.c_int32]
-    lib.ts2d_image_state_bytes.restype = ctypes.c_size_t
-    lib.ts2d_image_state_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32]
-    lib.ts2d_backward_scratch_bytes.restype = ctypes.c_size_t
-    lib.ts2d_backward_scratch_bytes.argtypes = [ctypes.c_int32]
     a, b = lib.ts2d_geometry_state_bytes(1000), lib.ts2d_geometry_state_bytes(2000)
     assert 1000 * 64 <= a < b  # at least the 64-byte render record per triangle
     assert lib.ts2d_image_state_bytes(1920, 1080) >= 1920 * 1080 * 8 + 120 * 68 * 8
@@ -102,8 +93,6 @@ def test_state_size_queries_are_monotone_and_aligned(lib):
 
 
 def test_null_arguments_are_rejected_not_crashed(lib):
-    lib.ts2d_forward_bin.restype = ctypes.c_int
-    lib.ts2d_last_error.restype = ctypes.c_char_p
     rc = lib.ts2d_forward_bin(None, None, 0, None, None, None, None)
     assert rc == 1 and b"null" in lib.ts2d_last_error()
 
@@ -112,8 +101,6 @@ def test_triangle_count_beyond_the_id_bits_is_refused(lib):
     """The instance lists keep four bits of each value for the quadrant mask (csrc/ts2d_support.h): 2^28 triangles are a capacity error of the
     argument check, before any memory is touched."""
     from diff_triangle_rasterization_2D import _C
-    lib.ts2d_forward_bin.restype = ctypes.c_int
-    lib.ts2d_last_error.restype = ctypes.c_char_p
     cam, geom = _C._Camera(), _C._Geometry()
     cam.width, cam.height = 64, 64
     geom.P, geom.C, geom.M, geom.gamma = 1 << 28, 3, 0, 1.0
@@ -275,15 +262,23 @@ def test_a_library_without_the_soname_is_refused(tmp_path, hip_lib_built):
     assert r.returncode != 0 and "lacks the soname libts2d.so" in r.stderr and "triangle-splatting_amd/build.py" in r.stderr
 
 
+def _struct_mirrors():
+    """C struct name -> its ctypes mirror, under the names the product modules use them by."""
+    from diff_triangle_rasterization_2D import _C
+    from diff_recon_hip import optim
+    return {"ts2d_camera": _C._Camera, "ts2d_geometry": _C._Geometry, "ts2d_forward_out": _C._ForwardOut, "ts2d_loss_grads": _C._LossGrads,
+            "ts2d_backward_out": _C._BackwardOut, "ts2d_state": _C._State, "tso_adam_slice": optim._Slice, "tso_row_slice": optim._RowSlice,
+            "tso_sh_factored_step": optim._ShFactoredStep}
+
+
 def test_ctypes_structures_match_the_c_headers(tmp_path, hip_lib_built):
-    """The ctypes mirrors of the C ABI's structs (diff_triangle_rasterization_2D/_C.py, diff_recon_hip/optim.py) against the headers themselves:
+    """The ctypes mirrors of the C ABI's structs (diff_triangle_rasterization_2D/_abi.py) against the headers themselves:
     a probe compiled with gcc from include/*.h prints sizeof / offsetof of every field; a field added to a header but not to its mirror (or
     the other way round) fails here, without a GPU."""
     import subprocess
     from diff_triangle_rasterization_2D import _C
     from diff_recon_hip import optim
-    mirrors = {"ts2d_camera": _C._Camera, "ts2d_geometry": _C._Geometry, "ts2d_forward_out": _C._ForwardOut, "ts2d_loss_grads": _C._LossGrads,
-               "ts2d_backward_out": _C._BackwardOut, "ts2d_state": _C._State, "tso_adam_slice": optim._Slice}
+    mirrors = _struct_mirrors()
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "ts2d.h"', '#include "ts_optim.h"', 'int main(void) {']
     for cname, mirror in mirrors.items():
         lines.append(f'printf("{cname} size %zu\\n", sizeof({cname}));')
@@ -312,10 +307,6 @@ def test_binning_state_bytes_grow_with_the_capacity_and_invert(lib):
     """The forward and the backward both carve the binning state from the BUFFER'S SIZE (ts2d_binning_capacity inverts ts2d_binning_state_bytes by
     bisection), so the bytes must never shrink when the capacity grows -- also across the capacities at which the instance sort changes its chunk
     length (csrc/ts2d_common.h: ts_instance_chunk; the tables are sized for the shortest chunks at every capacity for exactly this reason)."""
-    lib.ts2d_binning_state_bytes.restype = ctypes.c_size_t
-    lib.ts2d_binning_state_bytes.argtypes = [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]
-    lib.ts2d_binning_capacity.restype = ctypes.c_int64
-    lib.ts2d_binning_capacity.argtypes = [ctypes.c_size_t, ctypes.c_int32, ctypes.c_int32]
     for W, H in ((1920, 1080), (256, 256), (37, 5)):
         caps = sorted(set(list(range(0, 70000, 997)) + list(range(2_499_000, 2_501_001, 125)) + [1 << k for k in range(4, 27)] +
                           [(1 << k) + 1 for k in range(4, 27)] + [4_610_000, 12_600_000, 23_000_000]))
@@ -328,3 +319,110 @@ def test_binning_state_bytes_grow_with_the_capacity_and_invert(lib):
             b = lib.ts2d_binning_state_bytes(n, W, H)
             cap = lib.ts2d_binning_capacity(b, W, H)
             assert cap >= n and lib.ts2d_binning_state_bytes(cap, W, H) <= b, (n, b, cap)  # the largest capacity whose carving fits the buffer
+
+
+# ---- every ctypes signature against its prototype ---------------------------------------------------------------------------------------
+LAB_HEADER = os.path.join(ROOT, "triangle-splatting_amd", "csrc", "ts2d_lab.h")
+_C_SCALARS = {"int": ("signed", ctypes.sizeof(ctypes.c_int)), "int32_t": ("signed", 4), "int64_t": ("signed", 8), "uint8_t": ("unsigned", 1),
+              "uint32_t": ("unsigned", 4), "uint64_t": ("unsigned", 8), "size_t": ("unsigned", ctypes.sizeof(ctypes.c_size_t)),
+              "unsigned long long": ("unsigned", ctypes.sizeof(ctypes.c_ulonglong)), "float": ("floating", 4), "double": ("floating", 8)}
+
+
+def _c_type(decl, named):
+    """(base type without qualifiers, number of `*`) of one C99 declarator: a return type (named = False) or a parameter with its name."""
+    stars = decl.count("*")
+    words = [w for w in decl.replace("*", " ").split() if w != "const"]
+    if named and len(words) > 1:
+        words = words[:-1]  # the parameter's name
+    return " ".join(words), stars
+
+
+def _prototypes(path):
+    """name -> (return type, [parameter types]) of every ts2d_ / tsl_ / tsk_ / tsm_ / tso_ prototype of a header, comments and directives stripped."""
+    text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    text = re.sub(r"^[ \t]*#[^\n]*$", "", text, flags=re.M)
+    found = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w \t\n*]*?)\b((?:ts2d|tsl|tsk|tsm|tso)_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        params = [" ".join(p.split()) for p in params.split(",")]
+        assert name not in found, name
+        found[name] = (_c_type(" ".join(ret.split()), False), [] if params == ["void"] else [_c_type(p, True) for p in params])
+    return found
+
+
+def _scalar_kind(ct):
+    code = getattr(ct, "_type_", None)
+    if not isinstance(code, str) or code not in "bhilqBHILQfd":
+        return None
+    return ("floating" if code in "fd" else "signed" if code.islower() else "unsigned", ctypes.sizeof(ct))
+
+
+def _mismatch(c, ct, mirrors):
+    """Why the ctypes type `ct` does not stand for the C type c = (base, stars), or None when it does.  c_int32 IS c_int here, so scalars are
+    compared by kind and size; a typed pointer must point at the mirror of that very C type."""
+    base, stars = c
+    if stars == 0:
+        if base == "void":
+            return None if ct is None else f"void, got {ct}"
+        return None if ct is not None and _scalar_kind(ct) == _C_SCALARS[base] else f"{base} is {_C_SCALARS[base]}, got {ct}"
+    if ct is ctypes.c_void_p:
+        return None
+    if ct is ctypes.c_char_p:
+        return None if (base, stars) == ("char", 1) else f"c_char_p for {base} {'*' * stars}"
+    pointee = getattr(ct, "_type_", None)
+    if not isinstance(ct, type) or not issubclass(ct, ctypes._Pointer):
+        return f"{base} {'*' * stars} needs a pointer, got {ct}"
+    if stars > 1:
+        return None if pointee is ctypes.c_void_p else f"an array of pointers is POINTER(c_void_p), got POINTER({pointee})"
+    if base in mirrors:
+        return None if pointee is mirrors[base] else f"{base} * points at {mirrors[base].__name__}, got POINTER({pointee.__name__})"
+    if base in _C_SCALARS:
+        return None if _scalar_kind(pointee) == _C_SCALARS[base] else f"{base} * points at {_C_SCALARS[base]}, got POINTER({pointee})"
+    return f"no typed pointer stands for {base} *"
+
+
+def _signature_problems(proto, signature, mirrors):
+    (c_ret, c_params), (restype, argtypes) = proto, signature
+    problems = []
+    why = _mismatch(c_ret, restype, mirrors)
+    if why:
+        problems.append(f"restype: {why}")
+    if len(c_params) != len(argtypes):
+        return problems + [f"arity: the header has {len(c_params)} parameters, the table {len(argtypes)}"]
+    for i, (c, ct) in enumerate(zip(c_params, argtypes)):
+        why = _mismatch(c, ct, mirrors)
+        if why:
+            problems.append(f"argument {i}: {why}")
+    return problems
+
+
+def test_ctypes_signatures_match_the_c_headers(lib):
+    """diff_triangle_rasterization_2D/_abi.py declares restype / argtypes of the whole C ABI once; here every entry is held against its
+    prototype in include/*.h (and csrc/ts2d_lab.h): the same set of names, the same arity, every scalar of the same kind and size, every typed
+    pointer at the mirror of that very C type.  A float where the header says double, or one pointer too few, would be a wild kernel argument."""
+    from diff_triangle_rasterization_2D import _abi
+    mirrors = _struct_mirrors()
+    product = {}
+    for h in HEADERS:
+        protos = _prototypes(h)
+        assert not set(protos) & set(product), sorted(set(protos) & set(product))
+        product.update(protos)
+    lab = _prototypes(LAB_HEADER)
+    assert set(product) == set(_declared_functions()) and len(product) == 76, len(product)  # the parser skipped no prototype
+    assert set(product) == set(_abi.SIGNATURES), sorted(set(product) ^ set(_abi.SIGNATURES))
+    assert set(lab) == set(_abi.LAB_SIGNATURES), sorted(set(lab) ^ set(_abi.LAB_SIGNATURES))
+    for protos, table in ((product, _abi.SIGNATURES), (lab, _abi.LAB_SIGNATURES)):
+        for name, proto in protos.items():
+            assert _signature_problems(proto, table[name], mirrors) == [], name
+    for name, (restype, argtypes) in _abi.SIGNATURES.items():  # and bind() sets both attributes, explicitly, on every function
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+    # the comparator itself: three corruptions of one entry, each must be reported
+    restype, argtypes = _abi.SIGNATURES["tso_adam_step"]
+    proto = product["tso_adam_step"]
+    assert _signature_problems(proto, (restype, argtypes), mirrors) == []
+    as_float = [ctypes.c_float if a is ctypes.c_double else a for a in argtypes]
+    assert as_float != list(argtypes) and any("double" in p for p in _signature_problems(proto, (restype, as_float), mirrors))
+    assert any("arity" in p for p in _signature_problems(proto, (restype, list(argtypes)[:-1]), mirrors))
+    wrong_struct = [ctypes.POINTER(mirrors["ts2d_camera"])] + list(argtypes)[1:]
+    assert any("tso_adam_slice" in p for p in _signature_problems(proto, (restype, wrong_struct), mirrors))

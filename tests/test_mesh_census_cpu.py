@@ -17,12 +17,8 @@ OK, INVALID = 0, 1
 
 @pytest.fixture(scope="module")
 def lib(hip_lib_built):
-    lib = ctypes.CDLL(hip_lib_built)
-    vp = ctypes.c_void_p
-    lib.ts2d_last_error.restype = ctypes.c_char_p
-    lib.ts2d_mesh_census_add.restype = ctypes.c_int
-    lib.ts2d_mesh_census_add.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp]
-    return lib
+    from diff_triangle_rasterization_2D import _abi  # the one table of signatures, on a CDLL of this module's own
+    return _abi.bind(ctypes.CDLL(hip_lib_built))
 
 
 def test_census_entry_point_is_declared_and_exported(lib):

@@ -104,29 +104,10 @@ def test_znear_inside_scene_a_leaves_straddlers_and_stays_under_the_cap():
 
 
 # ---- C ABI ------------------------------------------------------------------------------------------------------------------------
-class _Camera(ctypes.Structure):
-    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("tan_fovx", ctypes.c_float), ("tan_fovy", ctypes.c_float),
-                ("viewmatrix", ctypes.c_void_p), ("projmatrix", ctypes.c_void_p), ("campos", ctypes.c_void_p)]
-
-
-class _State(ctypes.Structure):
-    _fields_ = [("geometry", ctypes.c_void_p), ("geometry_bytes", ctypes.c_size_t), ("binning", ctypes.c_void_p), ("binning_bytes", ctypes.c_size_t),
-                ("image", ctypes.c_void_p), ("image_bytes", ctypes.c_size_t)]
-
-
 @pytest.fixture(scope="module")
 def lib(hip_lib_built):
-    lib = ctypes.CDLL(hip_lib_built)
-    vp = ctypes.c_void_p
-    lib.ts2d_last_error.restype = ctypes.c_char_p
-    lib.ts2d_mesh_geometry_state_bytes.restype = ctypes.c_size_t
-    lib.ts2d_mesh_geometry_state_bytes.argtypes = [ctypes.c_int32]
-    lib.ts2d_geometry_state_bytes.restype = ctypes.c_size_t
-    lib.ts2d_geometry_state_bytes.argtypes = [ctypes.c_int32]
-    lib.ts2d_mesh_bin.argtypes = [ctypes.POINTER(_Camera), ctypes.c_float, ctypes.c_int32, vp, ctypes.c_int32, vp, ctypes.POINTER(_State),
-                                  ctypes.POINTER(ctypes.c_int64), vp]
-    lib.ts2d_mesh_render.argtypes = [ctypes.POINTER(_Camera), ctypes.c_int32, vp, vp, ctypes.c_int64, ctypes.POINTER(_State), vp, vp, vp, vp, vp]
-    return lib
+    from diff_triangle_rasterization_2D import _abi  # the one table of signatures, on a CDLL of this module's own
+    return _abi.bind(ctypes.CDLL(hip_lib_built))
 
 
 def test_mesh_entry_points_are_declared_and_exported(lib):
@@ -138,6 +119,7 @@ def test_mesh_entry_points_are_declared_and_exported(lib):
 
 
 def test_mesh_argument_validation_touches_no_device(lib):
+    from diff_triangle_rasterization_2D._abi import _Camera, _State
     INVALID, CAPACITY = 1, 3
     fake = ctypes.c_void_p(0x1000)  # never dereferenced: every call below is refused before anything is queued
     n = ctypes.c_int64(-7)

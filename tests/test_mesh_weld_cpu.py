@@ -68,20 +68,8 @@ def test_reference_jittered_grid_counts():
 # ---- the C ABI's argument checks, without a device --------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def lib(hip_lib_built):
-    lib = ctypes.CDLL(hip_lib_built)
-    p, i32, sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_size_t
-    lib.ts2d_last_error.restype = ctypes.c_char_p
-    lib.ts2d_weld_workspace_bytes.restype = sz
-    lib.ts2d_weld_workspace_bytes.argtypes = [i32, i32]
-    for name, args in (("ts2d_weld_labels", [i32, p, ctypes.c_float, p, p, sz, p]),
-                       ("ts2d_weld_labels_counted", [i32, p, ctypes.c_float, p, p, p, sz, p]),
-                       ("ts2d_weld_face_components", [i32, i32, p, p, p, p, sz, p]),
-                       ("ts2d_weld_compact", [i32, p, p, i32, p, p, p, p, sz, p]),
-                       ("ts2d_weld_remap_faces", [i32, i32, p, p, p, p, p]),
-                       ("ts2d_weld_edge_census", [i32, i32, p, p, p, p, sz, p])):
-        getattr(lib, name).restype = ctypes.c_int
-        getattr(lib, name).argtypes = args
-    return lib
+    from diff_triangle_rasterization_2D import _abi  # the one table of signatures, on a CDLL of this module's own
+    return _abi.bind(ctypes.CDLL(hip_lib_built))
 
 
 X = 0x1000  # stands for a non-null device pointer: every call below is refused (or is a no-op) before anything is dereferenced or enqueued

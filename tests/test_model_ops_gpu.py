@@ -421,7 +421,8 @@ def _tie_triangles():
 
 def test_split_vertex_follows_argmax_first_maximum_on_tied_sides():
     import torch
-    from diff_recon_hip.model_update import _lib, _stream
+    from diff_recon_hip.model_update import _lib
+    from diff_triangle_rasterization_2D._C import stream as _stream
     v = _tie_triangles()
     n = v.shape[0]
     sides, _ = _mean_side(v)
@@ -436,7 +437,8 @@ def test_split_vertex_follows_argmax_first_maximum_on_tied_sides():
 
 def _update_mask(mode, opacity, vertex, max_radii, a, b=0.0):
     import torch
-    from diff_recon_hip.model_update import _lib, _stream
+    from diff_recon_hip.model_update import _lib
+    from diff_triangle_rasterization_2D._C import stream as _stream
     out = torch.empty((vertex.shape[0],), device="cuda", dtype=torch.uint8)
     assert _lib.tsm_update_mask(vertex.shape[0], mode, opacity.data_ptr(), vertex.data_ptr(), max_radii.data_ptr(), float(a), float(b),
                                 out.data_ptr(), _stream()) == 0
@@ -486,7 +488,8 @@ def test_mean_side_and_longest_side_of_inexact_triangles_follow_torch():
     moved by inexact amounts, whose three sides nearly tie.  The kernels form side lengths and mean as torch's GPU norm and mean do, so mode 3
     agrees with torch with the threshold on a row's own mean side and one ulp either side, and split_vertex picks torch.argmax's side."""
     import torch
-    from diff_recon_hip.model_update import _lib, _stream
+    from diff_recon_hip.model_update import _lib
+    from diff_triangle_rasterization_2D._C import stream as _stream
     P = 1_000_003
     g = torch.Generator(device="cuda").manual_seed(77)
     half = P // 2
@@ -517,7 +520,8 @@ def test_grow_classify_on_and_around_its_thresholds():
     one ulp either side, gradient_denom on and one ulp either side of min_view_count, and the mean side on and one ulp either side of the
     split threshold; the selected rows' accumulators are reset."""
     import torch
-    from diff_recon_hip.model_update import _lib, _stream
+    from diff_recon_hip.model_update import _lib
+    from diff_triangle_rasterization_2D._C import stream as _stream
     v = _tie_triangles()
     _, scaling = _mean_side(v)
     mvc = 4.0
@@ -552,7 +556,8 @@ def test_training_statistic_equals_the_sequential_float64_rule(V, rich):
     zeros, rows invisible in every view (untouched bit for bit), one NaN center2D gradient that must reach gradient_accum like the
     reference's `+=`.  gradient_accum to rtol 1e-6, everything else exact; without rich_info contrib_sum / contrib_max stay as they were."""
     import torch
-    from diff_recon_hip.model_update import _lib, _stream
+    from diff_recon_hip.model_update import _lib
+    from diff_triangle_rasterization_2D._C import stream as _stream
     P = 1_000_003
     g = torch.Generator(device="cuda").manual_seed(31 * V + rich)
     radii = torch.randint(0, 6, (V, P), device="cuda", generator=g, dtype=torch.int32)

@@ -41,7 +41,7 @@ EXT = os.path.join(HERE, "bindings", "_ts2d_torch_C.so")
 ARCH = "gfx950"
 
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function",
-          "-Wno-unused-result", "-DNDEBUG", "-fvisibility=hidden"]  # exports = what include/*.h declares (api.hip), nothing else
+          "-Wno-unused-result", "-DNDEBUG", "-fvisibility=hidden"]  # exports = what include/*.h declares (api*.hip), nothing else
 SOURCES = {
     "preprocess.hip": ["-ffp-contract=off"],
     "preprocess3d.hip": ["-ffp-contract=off"],
@@ -65,7 +65,10 @@ SOURCES = {
     "render_group.hip@fwd": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None", "-fno-slp-vectorize", "-DTSG_PART=1", "-mllvm", "-amdgpu-sched-strategy=max-ilp"],
     "render_group.hip@bwd": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None", "-fno-slp-vectorize", "-DTSG_PART=2"],
     "render3d_group.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None", "-fno-slp-vectorize"],
-    "api.hip": [],
+    "api.hip": [],       # the C ABI, one file per group of public headers (csrc/ts2d_api.h is what they share): include/ts2d.h ...
+    "api_loss.hip": [],  # ... ts_loss.h ...
+    "api_model.hip": [], # ... ts_model.h, ts_optim.h, ts_knn.h ...
+    "api_mesh.hip": [],  # ... ts_mesh.h, ts_weld.h
 }
 LAB_SOURCES = {  # libts2d_lab.so only
     "lab_hooks.hip": [],  # sort / scan test hooks + their rocPRIM comparators (csrc/ts2d_lab.h)
@@ -74,7 +77,7 @@ LAB_SOURCES = {  # libts2d_lab.so only
 BIN_DIR = os.path.join(os.path.dirname(HERE), "tools", "bin")
 LAB_LIB = os.path.join(BIN_DIR, "libts2d_lab.so")
 LAB_SRC = os.path.join(os.path.dirname(HERE), "tools", "lab")  # lab_hooks.hip: the test hooks, outside the product's csrc/; it includes csrc's headers (-I)
-HEADERS = ["ts2d_common.h", "ts_knn_front.h", "ts_weld_launch.h", "ts2d_lab.h", "ts2d_math.h", "ts2d_wave.h", "ts2d_group.h", "ts2d_support.h", "ts2d_sh.h", "ts2d_stage.h", "ts2d_preprocess_launch.h", "ts2d_imgops.h", "ts2d_select.h", "ts2d_tri.h", os.path.join("..", "..", "include", "ts2d.h"),
+HEADERS = ["ts2d_common.h", "ts2d_api.h", "ts_knn_front.h", "ts_weld_launch.h", "ts2d_lab.h", "ts2d_math.h", "ts2d_wave.h", "ts2d_group.h", "ts2d_support.h", "ts2d_sh.h", "ts2d_stage.h", "ts2d_preprocess_launch.h", "ts2d_imgops.h", "ts2d_select.h", "ts2d_tri.h", os.path.join("..", "..", "include", "ts2d.h"),
            os.path.join("..", "..", "include", "ts_loss.h"),
            os.path.join("..", "..", "include", "ts_knn.h"),
            os.path.join("..", "..", "include", "ts_model.h"),

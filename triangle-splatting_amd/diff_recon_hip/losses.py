@@ -22,15 +22,6 @@ from torch import nn
 from diff_triangle_rasterization_2D import _C as _native
 
 _lib = _native._lib
-_fp = C.c_void_p
-_lib.tsl_workspace_bytes.restype = C.c_size_t
-_lib.tsl_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-_lib.tsl_photometric_forward.restype = C.c_int
-_lib.tsl_photometric_forward.argtypes = [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32, _fp,
-                                         C.c_size_t, _fp, _fp]
-_lib.tsl_photometric_backward.restype = C.c_int
-_lib.tsl_photometric_backward.argtypes = [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _fp, C.c_size_t,
-                                          _fp, _fp, _fp]
 
 
 def _chw(img1: torch.Tensor, img2: torch.Tensor):
@@ -49,8 +40,7 @@ def _chw(img1: torch.Tensor, img2: torch.Tensor):
 
 
 def _check_inputs(image: torch.Tensor, gt: torch.Tensor):
-    if not image.is_cuda or not gt.is_cuda:
-        raise RuntimeError("the photometric loss (MI355X build) needs tensors on a HIP device; there is no CPU fallback")
+    _native.require_device("the photometric loss", image, gt)
     if image.dtype != torch.float32 or gt.dtype != torch.float32:
         raise RuntimeError("expected scalar type Float")
 
@@ -75,7 +65,7 @@ class _Photometric(torch.autograd.Function):
             out = torch.empty((3,), device=dev, dtype=torch.float32)
             _native._check(_lib.tsl_photometric_forward(image_c.data_ptr(), gt_c.data_ptr(), c, h, w, float(w_l1), float(w_ssim),
                                                         int(need_grad), ws.data_ptr(), nbytes, out.data_ptr(),
-                                                        torch.cuda.current_stream().cuda_stream), "photometric_loss")
+                                                        _native.stream()), "photometric_loss")
         ctx.dims = (c, h, w)
         ctx.weights = (float(w_l1), float(w_ssim))
         ctx.save_for_backward(image_c, gt_c, ws)
@@ -92,7 +82,7 @@ class _Photometric(torch.autograd.Function):
             go = grad_out.contiguous().to(torch.float32)
             _native._check(_lib.tsl_photometric_backward(image.data_ptr(), gt.data_ptr(), c, h, w, w_l1, w_ssim, ws.data_ptr(),
                                                          ws.numel(), go.data_ptr(), g.data_ptr(),
-                                                         torch.cuda.current_stream().cuda_stream), "photometric_loss backward")
+                                                         _native.stream()), "photometric_loss backward")
         return (g if ctx.needs_input_grad[0] else None), (-g if ctx.needs_input_grad[1] else None), None, None
 
 
@@ -126,19 +116,12 @@ class PhotometricLoss(nn.Module):
 
 
 # ---- depth / normal consistency loss (trainer_utils.py:204-257) -------------------------------------------------------------------
-_lib.tsl_depth_normal_workspace_bytes.restype = C.c_size_t
-_lib.tsl_depth_normal_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_double]
-_lib.tsl_depth_normal_forward.restype = C.c_int
-_lib.tsl_depth_normal_forward.argtypes = [_fp, _fp, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_double, C.c_float, _fp, C.c_size_t, _fp, _fp]
-_lib.tsl_depth_normal_backward.restype = C.c_int
-_lib.tsl_depth_normal_backward.argtypes = [_fp, _fp, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_double, _fp, C.c_size_t, _fp, _fp, _fp, _fp]
 
 
 class _DepthNormal(torch.autograd.Function):
     @staticmethod
     def forward(ctx, depth, normal, tan_fovx, tan_fovy, scale_factor, quantile):
-        if not depth.is_cuda or not normal.is_cuda:
-            raise RuntimeError("DepthNormalLoss (MI355X build) needs tensors on a HIP device; there is no CPU fallback")
+        _native.require_device("DepthNormalLoss", depth, normal)
         if depth.dtype != torch.float32 or normal.dtype != torch.float32:
             raise RuntimeError("expected scalar type Float")
         if depth.dim() != 2 or normal.dim() != 3 or normal.shape[0] != 3 or tuple(normal.shape[1:]) != tuple(depth.shape):
@@ -151,7 +134,7 @@ class _DepthNormal(torch.autograd.Function):
             ws = torch.empty((nbytes,), device=depth.device, dtype=torch.uint8)
             out = torch.empty((1,), device=depth.device, dtype=torch.float32)
             _native._check(_lib.tsl_depth_normal_forward(d.data_ptr(), n.data_ptr(), H, W, float(tan_fovx), float(tan_fovy), scale, float(quantile),
-                                                         ws.data_ptr(), nbytes, out.data_ptr(), torch.cuda.current_stream().cuda_stream),
+                                                         ws.data_ptr(), nbytes, out.data_ptr(), _native.stream()),
                            "depth_normal_loss")
         ctx.args = (H, W, float(tan_fovx), float(tan_fovy), scale)
         ctx.save_for_backward(d, n, ws)
@@ -167,7 +150,7 @@ class _DepthNormal(torch.autograd.Function):
             go = grad_out.contiguous().to(torch.float32)
             _native._check(_lib.tsl_depth_normal_backward(d.data_ptr(), n.data_ptr(), H, W, tx, ty, scale, ws.data_ptr(), ws.numel(), go.data_ptr(),
                                                           gd.data_ptr() if gd is not None else None, gn.data_ptr() if gn is not None else None,
-                                                          torch.cuda.current_stream().cuda_stream), "depth_normal_loss backward")
+                                                          _native.stream()), "depth_normal_loss backward")
         return gd, gn, None, None, None, None
 
 
@@ -192,20 +175,6 @@ class DepthNormalLoss(nn.Module):
 
 
 # ---- DoGLoss / SmoothnessLoss (round 5; csrc/aux_losses.hip) -------------------------------------------------------------------------
-_lib.tsl_aux_loss_workspace_bytes.restype = C.c_size_t
-_lib.tsl_aux_loss_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_double]
-_lib.tsl_dog_mask.restype = C.c_int
-_lib.tsl_dog_mask.argtypes = [_fp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_double, _fp, C.c_size_t, _fp, _fp]
-_lib.tsl_smoothness_mask.restype = C.c_int
-_lib.tsl_smoothness_mask.argtypes = [_fp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_float, _fp, C.c_size_t, _fp, _fp]
-_lib.tsl_masked_l1_forward.restype = C.c_int
-_lib.tsl_masked_l1_forward.argtypes = [_fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, C.c_size_t, _fp, _fp]
-_lib.tsl_masked_l1_backward.restype = C.c_int
-_lib.tsl_masked_l1_backward.argtypes = [_fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp]
-_lib.tsl_scharr_smoothness_forward.restype = C.c_int
-_lib.tsl_scharr_smoothness_forward.argtypes = [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, C.c_size_t, _fp, _fp]
-_lib.tsl_scharr_smoothness_backward.restype = C.c_int
-_lib.tsl_scharr_smoothness_backward.argtypes = [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, C.c_size_t, _fp, _fp, _fp]
 
 
 def _aux_prepare(img: torch.Tensor, img_gt: torch.Tensor, what: str):
@@ -224,7 +193,7 @@ class _MaskedL1(torch.autograd.Function):
         out = torch.empty((1,), device=img.device, dtype=torch.float32)
         with torch.cuda.device(img.device):
             _native._check(_lib.tsl_masked_l1_forward(img.data_ptr(), gt.data_ptr(), mask.data_ptr(), c, h, w, ws.data_ptr(), ws.numel(), out.data_ptr(),
-                                                      torch.cuda.current_stream().cuda_stream), "DoGLoss")
+                                                      _native.stream()), "DoGLoss")
         ctx.shape = (c, h, w)
         ctx.save_for_backward(img, gt, mask)
         return out[0].clone()
@@ -237,7 +206,7 @@ class _MaskedL1(torch.autograd.Function):
         go = grad_out.contiguous().to(torch.float32)
         with torch.cuda.device(img.device):
             _native._check(_lib.tsl_masked_l1_backward(img.data_ptr(), gt.data_ptr(), mask.data_ptr(), c, h, w, go.data_ptr(), g.data_ptr(),
-                                                       torch.cuda.current_stream().cuda_stream), "DoGLoss backward")
+                                                       _native.stream()), "DoGLoss backward")
         return g, None, None, None, None, None, None
 
 
@@ -247,7 +216,7 @@ class _ScharrSmoothness(torch.autograd.Function):
         out = torch.empty((1,), device=img.device, dtype=torch.float32)
         with torch.cuda.device(img.device):
             _native._check(_lib.tsl_scharr_smoothness_forward(img.data_ptr(), mask.data_ptr(), c, h, w, ws.data_ptr(), ws.numel(), out.data_ptr(),
-                                                              torch.cuda.current_stream().cuda_stream), "SmoothnessLoss")
+                                                              _native.stream()), "SmoothnessLoss")
         ctx.shape = (c, h, w)
         ctx.save_for_backward(img, mask, ws)
         return out[0].clone()
@@ -260,7 +229,7 @@ class _ScharrSmoothness(torch.autograd.Function):
         go = grad_out.contiguous().to(torch.float32)
         with torch.cuda.device(img.device):
             _native._check(_lib.tsl_scharr_smoothness_backward(img.data_ptr(), mask.data_ptr(), c, h, w, ws.data_ptr(), ws.numel(), go.data_ptr(), g.data_ptr(),
-                                                               torch.cuda.current_stream().cuda_stream), "SmoothnessLoss backward")
+                                                               _native.stream()), "SmoothnessLoss backward")
         return g, None, None, None, None, None
 
 
@@ -292,7 +261,7 @@ class DoGLoss(nn.Module):
         m = torch.empty((h, w), device=gt.device, dtype=torch.float32)
         with torch.cuda.device(gt.device):
             _native._check(_lib.tsl_dog_mask(gt.data_ptr(), c, h, w, self.sigma1, self.kernel_size1, self.sigma2, self.kernel_size2, int(self.freq >= 50), scale,
-                                             ws.data_ptr(), ws.numel(), m.data_ptr(), torch.cuda.current_stream().cuda_stream), "DoGLoss mask")
+                                             ws.data_ptr(), ws.numel(), m.data_ptr(), _native.stream()), "DoGLoss mask")
         return m
 
     def forward(self, img: torch.Tensor, img_gt: torch.Tensor) -> torch.Tensor:
@@ -322,7 +291,7 @@ class SmoothnessLoss(nn.Module):
         m = torch.empty((h, w), device=gt.device, dtype=torch.float32)
         with torch.cuda.device(gt.device):
             _native._check(_lib.tsl_smoothness_mask(gt.data_ptr(), c, h, w, scale, float(self.quantile), ws.data_ptr(), ws.numel(), m.data_ptr(),
-                                                    torch.cuda.current_stream().cuda_stream), "SmoothnessLoss mask")
+                                                    _native.stream()), "SmoothnessLoss mask")
         return m
 
     def forward(self, img: torch.Tensor, img_gt: torch.Tensor) -> torch.Tensor:
@@ -336,13 +305,6 @@ smoothnessLoss = SmoothnessLoss()
 
 
 # ---- the down-sampler of render_up_scale (include/ts_loss.h: tsl_downsample_*; csrc/resample.hip) ----------------------------------------
-_lib.tsl_downsample_forward.restype = C.c_int
-_lib.tsl_downsample_forward.argtypes = [_fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp, _fp]
-_lib.tsl_downsample_backward.restype = C.c_int
-_lib.tsl_downsample_backward.argtypes = [_fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp, _fp]
-for _name in ("tsl_downsample_forward_planes", "tsl_downsample_backward_planes"):
-    getattr(_lib, _name).restype = C.c_int
-    getattr(_lib, _name).argtypes = [C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), _fp]
 
 
 class _Downsample(torch.autograd.Function):
@@ -355,7 +317,7 @@ class _Downsample(torch.autograd.Function):
             c *= int(d)
         out = torch.empty(tuple(lead) + (h, w), device=x.device, dtype=torch.float32)
         with torch.cuda.device(x.device):
-            _native._check(_lib.tsl_downsample_forward(xc.data_ptr(), c, H, W, h, w, out.data_ptr(), torch.cuda.current_stream().cuda_stream), "downsample_bilinear")
+            _native._check(_lib.tsl_downsample_forward(xc.data_ptr(), c, H, W, h, w, out.data_ptr(), _native.stream()), "downsample_bilinear")
         ctx.dims = (c, H, W, h, w, tuple(xc.shape))
         return out
 
@@ -365,7 +327,7 @@ class _Downsample(torch.autograd.Function):
         gc = g.contiguous()
         gin = torch.empty(shape, device=g.device, dtype=torch.float32)
         with torch.cuda.device(g.device):
-            _native._check(_lib.tsl_downsample_backward(gc.data_ptr(), c, H, W, h, w, gin.data_ptr(), torch.cuda.current_stream().cuda_stream), "downsample_bilinear backward")
+            _native._check(_lib.tsl_downsample_backward(gc.data_ptr(), c, H, W, h, w, gin.data_ptr(), _native.stream()), "downsample_bilinear backward")
         return gin, None, None
 
 
@@ -387,7 +349,7 @@ class _DownsampleMany(torch.autograd.Function):
         n = len(src)
         with torch.cuda.device(xs[0].device):
             _native._check(_lib.tsl_downsample_forward_planes(n, (C.c_void_p * n)(*src), H, W, h, w, (C.c_void_p * n)(*dst),
-                                                              torch.cuda.current_stream().cuda_stream), "downsample_bilinear")
+                                                              _native.stream()), "downsample_bilinear")
         ctx.dims = (H, W, h, w, [tuple(x.shape) for x in xs])
         ctx.set_materialize_grads(False)  # an output nobody differentiates (depth / normal without the geometry loss) hands its input no gradient
         return tuple(outs)
@@ -406,7 +368,7 @@ class _DownsampleMany(torch.autograd.Function):
             n = len(src)
             with torch.cuda.device(dev):
                 _native._check(_lib.tsl_downsample_backward_planes(n, (C.c_void_p * n)(*src), H, W, h, w, (C.c_void_p * n)(*dst),
-                                                                   torch.cuda.current_stream().cuda_stream), "downsample_bilinear backward")
+                                                                   _native.stream()), "downsample_bilinear backward")
         return (None, None) + tuple(gins)
 
 

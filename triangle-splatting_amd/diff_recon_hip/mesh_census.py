@@ -16,7 +16,6 @@ TRIANGLE: `fold_twins` adds rows f and f + P (which also covers a mesh whose twi
 triangle keeps both faces, and both faces get the same baked colour -- which is also all a GLB file can hold (one colour per triangle)."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, Iterable, Optional
 
 import torch
@@ -26,9 +25,6 @@ from diff_triangle_rasterization_2D import _C as _native
 from .mesh_renderer import MeshRenderer, mesh_from_triangles
 
 _lib = _native._lib
-_fp = C.c_void_p
-_lib.ts2d_mesh_census_add.restype = C.c_int
-_lib.ts2d_mesh_census_add.argtypes = [C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp]
 
 Q16 = 65536.0
 
@@ -68,7 +64,7 @@ class MeshCensus:
             face_idx = face_idx.contiguous()
             target = target.detach().contiguous() if target is not None else None
             pixel_mask = pixel_mask.detach().contiguous() if pixel_mask is not None else None
-            stream = torch.cuda.current_stream().cuda_stream
+            stream = _native.stream()
             _native._check(_lib.ts2d_mesh_census_add(W, H, self.num_faces, face_idx.data_ptr(), _native._ptr(target), _native._ptr(pixel_mask),
                                                      _native._ptr(self.acc) if self.num_faces else None, stream), "MeshCensus.add")
         return self

@@ -19,17 +19,6 @@ from diff_triangle_rasterization_2D import _C as _native
 from .raw_triangle import C0, _accessor, read_glb
 
 _lib = _native._lib
-_fp = C.c_void_p
-_lib.ts2d_mesh_geometry_state_bytes.restype = C.c_size_t
-_lib.ts2d_mesh_geometry_state_bytes.argtypes = [C.c_int32]
-_lib.ts2d_mesh_bin.restype = C.c_int
-_lib.ts2d_mesh_bin.argtypes = [C.POINTER(_native._Camera), C.c_float, C.c_int32, _fp, C.c_int32, _fp, C.POINTER(_native._State),
-                               C.POINTER(C.c_int64), _fp]
-_lib.ts2d_mesh_render.restype = C.c_int
-_lib.ts2d_mesh_render.argtypes = [C.POINTER(_native._Camera), C.c_int32, _fp, _fp, C.c_int64, C.POINTER(_native._State), _fp, _fp, _fp, _fp, _fp]
-_lib.ts2d_mesh_render_counted.restype = C.c_int
-_lib.ts2d_mesh_render_counted.argtypes = [C.POINTER(_native._Camera), C.c_int32, _fp, _fp, C.c_int64, C.POINTER(_native._State), _fp, _fp, _fp,
-                                          _fp, _fp, _fp]
 
 
 def mesh_from_triangles(vertex: torch.Tensor, shs: torch.Tensor, save_back: bool = True) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -147,7 +136,7 @@ class MeshRenderer:
             view = cam.world_view_transform.to(device=device, dtype=torch.float32).contiguous()
             bg = self.bg_color.to(device=device, dtype=torch.float32).contiguous()
             gbuf, ibuf = self._state(F, W, H, device)
-            stream = torch.cuda.current_stream().cuda_stream
+            stream = _native.stream()
             ccam = _native._Camera(W, H, float(cam.tan_fovx), float(cam.tan_fovy), view.data_ptr(), None, None)
             bbuf = self._binning if (self._binning is not None and self._binning.device == device) else None
             st = _native._State(gbuf.data_ptr(), gbuf.numel(), _native._ptr(bbuf), 0 if bbuf is None else bbuf.numel(), ibuf.data_ptr(), ibuf.numel())

@@ -22,7 +22,6 @@ Native code: libts2d.so (include/ts_weld.h, csrc/mesh_weld.hip), bound with ctyp
 is quadratic when most vertices lie within `eps` of each other (see the header): `eps` is meant to be far below the mesh's extent."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Dict, NamedTuple, Optional
 
@@ -31,21 +30,6 @@ import torch
 from diff_triangle_rasterization_2D import _C as _native
 
 _lib = _native._lib
-_fp = C.c_void_p
-_lib.ts2d_weld_workspace_bytes.restype = C.c_size_t
-_lib.ts2d_weld_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
-_lib.ts2d_weld_labels.restype = C.c_int
-_lib.ts2d_weld_labels.argtypes = [C.c_int32, _fp, C.c_float, _fp, _fp, C.c_size_t, _fp]
-_lib.ts2d_weld_labels_counted.restype = C.c_int
-_lib.ts2d_weld_labels_counted.argtypes = [C.c_int32, _fp, C.c_float, _fp, _fp, _fp, C.c_size_t, _fp]
-_lib.ts2d_weld_face_components.restype = C.c_int
-_lib.ts2d_weld_face_components.argtypes = [C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, C.c_size_t, _fp]
-_lib.ts2d_weld_compact.restype = C.c_int
-_lib.ts2d_weld_compact.argtypes = [C.c_int32, _fp, _fp, C.c_int32, _fp, _fp, _fp, _fp, C.c_size_t, _fp]
-_lib.ts2d_weld_remap_faces.restype = C.c_int
-_lib.ts2d_weld_remap_faces.argtypes = [C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp]
-_lib.ts2d_weld_edge_census.restype = C.c_int
-_lib.ts2d_weld_edge_census.argtypes = [C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, C.c_size_t, _fp]
 
 POSITION_MODES = {"first": 0, "mean": 1}  # TS2D_WELD_FIRST / TS2D_WELD_MEAN
 
@@ -93,10 +77,6 @@ def _workspace(V: int, F: int, device) -> torch.Tensor:
     return torch.empty((_lib.ts2d_weld_workspace_bytes(V, F),), device=device, dtype=torch.uint8)
 
 
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
 def _check_eps(eps: float) -> float:
     eps = float(eps)
     if not (math.isfinite(eps) and eps >= 0.0):
@@ -116,7 +96,7 @@ def weld_labels(vertices: torch.Tensor, eps: float, box_visits: Optional[torch.T
         if V:
             ws = _workspace(V, 0, device)
             _native._check(_lib.ts2d_weld_labels_counted(V, v.data_ptr(), eps, label.data_ptr(), _native._ptr(box_visits), ws.data_ptr(), ws.numel(),
-                                                         _stream()), "weld_labels")
+                                                         _native.stream()), "weld_labels")
     return label
 
 
@@ -131,7 +111,7 @@ def face_components(num_vertices: int, faces: torch.Tensor, keep: Optional[torch
     with torch.cuda.device(device):
         label = torch.empty((V,), device=device, dtype=torch.int32)
         if V:
-            _native._check(_lib.ts2d_weld_face_components(V, F, _native._ptr(f) if F else None, _native._ptr(k), label.data_ptr(), None, 0, _stream()),
+            _native._check(_lib.ts2d_weld_face_components(V, F, _native._ptr(f) if F else None, _native._ptr(k), label.data_ptr(), None, 0, _native.stream()),
                            "face_components")
     return label
 
@@ -153,7 +133,7 @@ def compact_labels(label: torch.Tensor, vertices: torch.Tensor, position: str = 
         if V:
             ws = _workspace(V, 0, device)
             _native._check(_lib.ts2d_weld_compact(V, label.data_ptr(), v.data_ptr(), POSITION_MODES[position], remap.data_ptr(), out.data_ptr(),
-                                                  count.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "compact_labels")
+                                                  count.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream()), "compact_labels")
         n = int(count.item())
     return remap, out[:n].contiguous(), n
 
@@ -172,7 +152,7 @@ def remap_faces(num_vertices: int, faces: torch.Tensor, remap: torch.Tensor):
         keep = torch.zeros((F,), device=device, dtype=torch.bool)
         if F:
             _native._check(_lib.ts2d_weld_remap_faces(V, F, f.data_ptr(), _native._ptr(remap) if V else None, out.data_ptr(), keep.data_ptr(),
-                                                      _stream()), "remap_faces")
+                                                      _native.stream()), "remap_faces")
     return out, keep
 
 
@@ -188,7 +168,7 @@ def edge_census(num_vertices: int, faces: torch.Tensor, keep: Optional[torch.Ten
         counts = torch.zeros((4,), device=device, dtype=torch.int64)
         if F:
             ws = _workspace(V, F, device)
-            _native._check(_lib.ts2d_weld_edge_census(V, F, f.data_ptr(), _native._ptr(k), counts.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+            _native._check(_lib.ts2d_weld_edge_census(V, F, f.data_ptr(), _native._ptr(k), counts.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream()),
                            "edge_census")
     return counts
 

@@ -15,7 +15,6 @@ scope) and performs, in the reference's order:
 from __future__ import annotations
 
 import copy
-import ctypes
 import math
 from typing import Dict, Optional
 
@@ -49,8 +48,6 @@ def ste_opacity(opacity: torch.Tensor, threshold: float) -> torch.Tensor:
 
 
 _lib = _native._lib
-_lib.tsm_max_vertex_distance.restype = ctypes.c_int
-_lib.tsm_max_vertex_distance.argtypes = [ctypes.c_int32] + [ctypes.c_void_p] * 4
 
 
 def background_depth(vertex: torch.Tensor, camera_center: torch.Tensor) -> torch.Tensor:

@@ -20,27 +20,8 @@ import torch.nn.functional as F
 from diff_triangle_rasterization_2D import _C as _native
 
 _lib = _native._lib
-_fp = C.c_void_p
-_lib.tsm_training_statistic.restype = C.c_int
-_lib.tsm_training_statistic.argtypes = [C.c_int32, C.c_int32] + [_fp] * 11
+_stream = _native.stream  # under this name tests/test_model_ops_gpu.py calls the entry points directly
 
-_lib.tsm_select_scratch_bytes.restype = C.c_size_t
-_lib.tsm_select_scratch_bytes.argtypes = [C.c_int32]
-_lib.tsm_select_rows.restype = C.c_int
-_lib.tsm_select_rows.argtypes = [C.c_int32, _fp, C.c_int32, _fp, _fp, C.c_size_t, C.POINTER(C.c_uint32), _fp]
-for _name in ("tsm_scatter_rows", "tsm_gather_rows"):
-    getattr(_lib, _name).restype = C.c_int
-    getattr(_lib, _name).argtypes = [C.c_int64, C.c_int32, _fp, _fp, _fp, C.c_int64, _fp]
-_lib.tsm_grow_classify.restype = C.c_int
-_lib.tsm_grow_classify.argtypes = [C.c_int32, _fp, _fp, _fp, C.c_float, C.c_float, C.c_float, _fp, _fp]
-_lib.tsm_split_vertex.restype = C.c_int
-_lib.tsm_split_vertex.argtypes = [C.c_int32, _fp, _fp, _fp, _fp, _fp]
-_lib.tsm_update_mask.restype = C.c_int
-_lib.tsm_update_mask.argtypes = [C.c_int32, C.c_int32, _fp, _fp, _fp, C.c_float, C.c_float, _fp, _fp]
-_lib.tsm_clip.restype = C.c_int
-_lib.tsm_clip.argtypes = [C.c_int32, C.c_int32, _fp, C.c_float, _fp, _fp, _fp, _fp]
-_lib.tsm_opacity_reset.restype = C.c_int
-_lib.tsm_opacity_reset.argtypes = [C.c_int32, C.c_float, _fp, _fp, _fp, _fp]
 
 _STATE = ("gradient_accum", "gradient_denom", "max_radii2D", "contrib_sum", "contrib_max", "contrib_denom")
 
@@ -58,8 +39,7 @@ class DensificationStats:
         """VanillaTS_model.py:347-363 for the view(s) in `render_pkg` ("radii", "center2D" with .grad populated, and --
         when rendered with rich_info -- "contrib_sum", "contrib_max")."""
         radii = render_pkg["radii"]
-        if not radii.is_cuda:
-            raise RuntimeError("DensificationStats (MI355X build) needs tensors on a HIP device; there is no CPU fallback")
+        _native.require_device("DensificationStats", radii)
         grad = render_pkg["center2D"].grad
         if grad is None:
             raise RuntimeError("center2D.grad is not populated: call update() after loss.backward()")
@@ -86,7 +66,7 @@ class DensificationStats:
                 P, V, radii.data_ptr(), grad.data_ptr(), csum.data_ptr() if rich else None, cmax.data_ptr() if rich else None,
                 self.gradient_accum.data_ptr(), self.gradient_denom.data_ptr(), self.max_radii2D.data_ptr(),
                 self.contrib_sum.data_ptr(), self.contrib_max.data_ptr(), self.contrib_denom.data_ptr(),
-                torch.cuda.current_stream().cuda_stream), "training_statistic")
+                _stream()), "training_statistic")
 
     def prune(self, prune_mask: torch.Tensor):
         """VanillaTS_model.py:228-234: drop the rows of pruned triangles."""
@@ -113,22 +93,13 @@ class DensificationStats:
 _PARAM_GROUPS = ("vertex", "opacity", "f_dc", "f_rest", "shs")
 
 
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _need_device(t: torch.Tensor):
-    if not t.is_cuda:
-        raise RuntimeError("model-update operators (MI355X build) need tensors on a HIP device; there is no CPU fallback")
-
-
 def _row_bytes(t: torch.Tensor) -> int:
     return (t.numel() // max(t.shape[0], 1)) * t.element_size() if t.shape[0] > 0 else (int(torch.Size(t.shape[1:]).numel()) * t.element_size())
 
 
 def select_rows(mask: torch.Tensor, match: int = 1):
     """(pos, count): stable compaction plan of the rows with mask == match (tsm_select_rows)."""
-    _need_device(mask)
+    _native.require_device("model-update operators", mask, verb="need")
     m8 = mask.contiguous().view(torch.uint8) if mask.dtype == torch.bool else mask.contiguous()
     P = m8.shape[0]
     pos = torch.empty((P,), device=mask.device, dtype=torch.int32)
@@ -210,7 +181,7 @@ def densification(m, iteration: int):
         return None
     grad_threshold = float(m.grad_threshold_scheduler(iteration - args.start_iter))
     vertex = m._vertex.data
-    _need_device(vertex)
+    _native.require_device("model-update operators", vertex, verb="need")
     P = vertex.shape[0]
     code = torch.empty((P,), device=vertex.device, dtype=torch.uint8)
     with torch.cuda.device(vertex.device):
@@ -249,7 +220,7 @@ def densification(m, iteration: int):
 
 def _mask(m, mode: int, a: float, b: float = 0.0) -> torch.Tensor:
     vertex, opacity = m._vertex.data.contiguous(), m._opacity.data.contiguous()
-    _need_device(vertex)
+    _native.require_device("model-update operators", vertex, verb="need")
     P = vertex.shape[0]
     out = torch.empty((P,), device=vertex.device, dtype=torch.uint8)
     with torch.cuda.device(vertex.device):

@@ -30,8 +30,6 @@ from diff_triangle_rasterization_2D.parallel import (FactoredShExchange, GradBuc
 from .model_update import _PARAM_GROUPS, _STATE, run_model_update
 
 _lib = _native._lib
-_lib.tsm_state_digest.restype = C.c_int
-_lib.tsm_state_digest.argtypes = [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p]
 
 MAX_DIGEST_SEGMENTS = 32  # TSM_DIGEST_MAX_SEGMENTS, include/ts_model.h
 
@@ -58,8 +56,7 @@ def digest_segments(tensors: Sequence[torch.Tensor], names: Optional[Sequence[st
     dev = tensors[0].device
     words = []
     for name, t in zip(names, tensors):
-        if not t.is_cuda:
-            raise RuntimeError("state_digest (MI355X build) needs tensors on a HIP device; there is no CPU fallback")
+        _native.require_device("state_digest", t)
         if t.device != dev:
             raise ValueError(f"state digest: {name!r} lives on {t.device}, the others on {dev}")
         words.append(_words_or_raise(name, t))
@@ -67,7 +64,7 @@ def digest_segments(tensors: Sequence[torch.Tensor], names: Optional[Sequence[st
     ptrs = (C.c_void_p * n)(*[t.data_ptr() if w else None for t, w in zip(tensors, words)])
     counts = (C.c_uint64 * n)(*words)
     with torch.cuda.device(dev):
-        _native._check(_lib.tsm_state_digest(n, ptrs, counts, out.data_ptr(), torch.cuda.current_stream().cuda_stream), "state_digest")
+        _native._check(_lib.tsm_state_digest(n, ptrs, counts, out.data_ptr(), _native.stream()), "state_digest")
     return out
 
 

@@ -24,40 +24,10 @@ import torch
 import torch.distributed as dist
 
 from diff_triangle_rasterization_2D import _C as _native
+from diff_triangle_rasterization_2D._abi import SH_ROW_SLICES, _RowSlice, _ShFactoredStep, _Slice  # noqa: F401  (the mirrors of include/ts_optim.h)
 
 _lib = _native._lib
-_fp = C.c_void_p
 MAX_SLICES = 16  # TSO_MAX_SLICES
-
-
-class _Slice(C.Structure):  # tso_adam_slice, include/ts_optim.h
-    _fields_ = [("param", _fp), ("grad", _fp), ("exp_avg", _fp), ("exp_avg_sq", _fp), ("count", C.c_int64), ("step_size", C.c_float),
-                ("bias2_sqrt", C.c_float), ("grad_scale", C.c_float), ("step_size_tail", C.c_float), ("index0", C.c_int64),
-                ("period", C.c_int32), ("split", C.c_int32)]
-
-
-_lib.tso_adam_step.restype = C.c_int
-_lib.tso_adam_step.argtypes = [C.POINTER(_Slice), C.c_int32, C.c_double, C.c_double, C.c_double, _fp]
-
-
-class _RowSlice(C.Structure):  # tso_row_slice, include/ts_optim.h
-    _fields_ = [("param", _fp), ("grad", _fp), ("exp_avg", _fp), ("exp_avg_sq", _fp), ("floats_per_row", C.c_int32), ("step_size", C.c_float),
-                ("bias2_sqrt", C.c_float), ("grad_scale", C.c_float)]
-
-
-SH_ROW_SLICES = 2  # TSO_SH_ROW_SLICES
-
-
-class _ShFactoredStep(C.Structure):  # tso_sh_factored_step, include/ts_optim.h
-    _fields_ = [("P", C.c_int32), ("M", C.c_int32), ("sh_degree", C.c_int32), ("V", C.c_int32), ("vertex", _fp), ("campos", _fp), ("dL_dcolor", _fp),
-                ("param_dc", _fp), ("exp_avg_dc", _fp), ("exp_avg_sq_dc", _fp), ("param_rest", _fp), ("exp_avg_rest", _fp), ("exp_avg_sq_rest", _fp),
-                ("dc_stride", C.c_int64), ("rest_stride", C.c_int64), ("step_size_dc", C.c_float), ("bias2_sqrt_dc", C.c_float),
-                ("step_size_rest", C.c_float), ("bias2_sqrt_rest", C.c_float), ("grad_scale", C.c_float), ("num_rows", C.c_int32),
-                ("rows", _RowSlice * SH_ROW_SLICES)]
-
-
-_lib.tso_adam_step_sh_factored.restype = C.c_int
-_lib.tso_adam_step_sh_factored.argtypes = [C.POINTER(_ShFactoredStep), C.c_double, C.c_double, C.c_double, _fp]
 
 
 class ShFactors:
@@ -101,7 +71,7 @@ def adam_step_slices(slices: Sequence[dict], beta1: float, beta2: float, eps: fl
         rows.append(_Slice(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), s["step_size"], s["bias2_sqrt"],
                            s.get("grad_scale", 1.0), s.get("step_size_tail", 0.0), s.get("index0", 0), s.get("period", 0), s.get("split", 0)))
     with torch.cuda.device(device):
-        stream = torch.cuda.current_stream().cuda_stream
+        stream = _native.stream()
         for i in range(0, len(rows), MAX_SLICES):
             chunk = rows[i:i + MAX_SLICES]
             arr = (_Slice * len(chunk))(*chunk)
@@ -204,7 +174,7 @@ class FusedAdam(torch.optim.Optimizer):
         for k, (_, rs) in enumerate(fused):
             row.rows[k] = rs
         with torch.cuda.device(dev):
-            _native._check(_lib.tso_adam_step_sh_factored(C.byref(row), betas[0], betas[1], eps, torch.cuda.current_stream().cuda_stream),
+            _native._check(_lib.tso_adam_step_sh_factored(C.byref(row), betas[0], betas[1], eps, _native.stream()),
                            "adam_step_sh_factored")
         sink.clear()
         return [q for q, _ in fused]

@@ -14,7 +14,6 @@ No CPU / eager fallback: every call needs float32 tensors on the HIP device.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Callable, Dict, Optional, Tuple
 
 import torch
@@ -25,38 +24,12 @@ from diff_triangle_rasterization_2D import _C as _native
 from .schedulers import exponential_scheduler
 
 _lib = _native._lib
-_fp = C.c_void_p
-_lib.tsl_reg_workspace_bytes.restype = C.c_size_t
-_lib.tsl_reg_workspace_bytes.argtypes = []
-_lib.tsl_reg_prepared_bytes.restype = C.c_size_t
-_lib.tsl_reg_prepared_bytes.argtypes = [C.c_int32]
-_lib.tsl_reg_prepare.restype = C.c_int
-_lib.tsl_reg_prepare.argtypes = [C.c_int32, _fp, _fp, C.c_size_t, _fp]
-_lib.tsl_reg_forward.restype = C.c_int
-_lib.tsl_reg_forward.argtypes = [C.c_int32, _fp, _fp, _fp, C.c_float, C.c_float, C.c_int32, C.c_float, _fp, C.c_size_t, _fp, _fp]
-_lib.tsl_reg_backward.restype = C.c_int
-_lib.tsl_reg_backward.argtypes = [C.c_int32, _fp, _fp, _fp, _fp, C.c_size_t, C.c_float, C.c_float, C.c_int32, C.c_float, _fp, _fp, _fp, _fp]
-_lib.tsl_color_affine_forward.restype = C.c_int
-_lib.tsl_color_affine_forward.argtypes = [_fp, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp]
-_lib.tsl_color_affine_backward.restype = C.c_int
-_lib.tsl_color_affine_backward.argtypes = [_fp, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, C.c_size_t, _fp, _fp, _fp, _fp]
-_lib.tsl_aux_loss_workspace_bytes.restype = C.c_size_t
-_lib.tsl_aux_loss_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_double]
-_lib.tsl_masked_l1_forward.restype = C.c_int
-_lib.tsl_masked_l1_forward.argtypes = [_fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, C.c_size_t, _fp, _fp]
-_lib.tsl_masked_l1_backward.restype = C.c_int
-_lib.tsl_masked_l1_backward.argtypes = [_fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp]
 
 OPACITY_MODES = {"none": 0, "quad": 1, "linear": 2}  # TSL_REG_OPACITY_NONE / _QUAD / _LINEAR
 
 
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
 def _f32_cuda(t: torch.Tensor, what: str) -> torch.Tensor:
-    if not t.is_cuda:
-        raise RuntimeError(f"{what} (MI355X build) needs tensors on a HIP device; there is no CPU fallback")
+    _native.require_device(what, t)
     if t.dtype != torch.float32:
         raise RuntimeError(f"{what}: expected scalar type Float")
     return t.contiguous()
@@ -86,7 +59,7 @@ class PreparedNearest:
         with torch.cuda.device(self.nearest.device):
             nbytes = _lib.tsl_reg_prepared_bytes(self.P)
             self.buffer = torch.empty((nbytes,), device=self.nearest.device, dtype=torch.uint8)
-            _native._check(_lib.tsl_reg_prepare(self.P, self.nearest.data_ptr(), self.buffer.data_ptr(), nbytes, _stream()), "prepare_nearest")
+            _native._check(_lib.tsl_reg_prepare(self.P, self.nearest.data_ptr(), self.buffer.data_ptr(), nbytes, _native.stream()), "prepare_nearest")
 
 
 def prepare_nearest(nearest: torch.Tensor) -> PreparedNearest:
@@ -104,7 +77,7 @@ class _TriangleReg(torch.autograd.Function):
             out = torch.empty((4,), device=dev, dtype=torch.float32)
             _native._check(_lib.tsl_reg_forward(P, vertex.data_ptr(), opacity.data_ptr() if opacity is not None else None,
                                                 nearest.data_ptr() if nearest is not None else None, w_s, w_o, mode, w_v, ws.data_ptr(), nbytes,
-                                                out.data_ptr(), _stream()), "triangle_regularization")
+                                                out.data_ptr(), _native.stream()), "triangle_regularization")
         ctx.args = (P, w_s, w_o, mode, w_v, prepared)
         ctx.shapes = (vertex.shape, opacity.shape if opacity is not None else None)
         ctx.save_for_backward(vertex, opacity, nearest)
@@ -125,7 +98,7 @@ class _TriangleReg(torch.autograd.Function):
             _native._check(_lib.tsl_reg_backward(P, vertex.data_ptr(), opacity.data_ptr() if opacity is not None else None,
                                                  nearest.data_ptr() if nearest is not None else None, buf.data_ptr() if buf is not None else None,
                                                  buf.numel() if buf is not None else 0, w_s, w_o, mode, w_v, go.data_ptr(), dv.data_ptr(),
-                                                 do.data_ptr(), _stream()), "triangle_regularization backward")
+                                                 do.data_ptr(), _native.stream()), "triangle_regularization backward")
         vshape, oshape = ctx.shapes
         return (dv.view(vshape) if ctx.needs_input_grad[0] else None, do.view(oshape) if ctx.needs_input_grad[1] else None,
                 None, None, None, None, None, None)
@@ -176,7 +149,7 @@ class _AffineL1(torch.autograd.Function):
         out = torch.empty((1,), device=x.device, dtype=torch.float32)
         with torch.cuda.device(x.device):
             _native._check(_lib.tsl_masked_l1_forward(x.data_ptr(), y.data_ptr(), mask.data_ptr(), c, h, w, ws.data_ptr(), ws.numel(), out.data_ptr(),
-                                                      _stream()), "affine_reg")
+                                                      _native.stream()), "affine_reg")
         ctx.save_for_backward(x, y, mask)
         return out[0].clone()
 
@@ -187,7 +160,7 @@ class _AffineL1(torch.autograd.Function):
         g = torch.empty_like(x)
         go = grad_out.contiguous().to(torch.float32)
         with torch.cuda.device(x.device):
-            _native._check(_lib.tsl_masked_l1_backward(x.data_ptr(), y.data_ptr(), mask.data_ptr(), c, h, w, go.data_ptr(), g.data_ptr(), _stream()),
+            _native._check(_lib.tsl_masked_l1_backward(x.data_ptr(), y.data_ptr(), mask.data_ptr(), c, h, w, go.data_ptr(), g.data_ptr(), _native.stream()),
                            "affine_reg backward")
         return (g if ctx.needs_input_grad[0] else None), (-g if ctx.needs_input_grad[1] else None), None, None
 
@@ -233,7 +206,7 @@ class _ColorAffine(torch.autograd.Function):
         out = torch.empty_like(image)
         with torch.cuda.device(image.device):
             _native._check(_lib.tsl_color_affine_forward(image.data_ptr(), h, w, weight[uid].data_ptr(), bias[uid].data_ptr(), out.data_ptr(),
-                                                         _stream()), "ColorAffine")
+                                                         _native.stream()), "ColorAffine")
         ctx.uid = uid
         ctx.save_for_backward(image, weight, bias)
         return out
@@ -252,7 +225,7 @@ class _ColorAffine(torch.autograd.Function):
             nbytes = _lib.tsl_reg_workspace_bytes()
             ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
             _native._check(_lib.tsl_color_affine_backward(image.data_ptr(), h, w, weight[uid].data_ptr(), bias[uid].data_ptr(), g.data_ptr(),
-                                                          ws.data_ptr(), nbytes, gx.data_ptr(), gw[uid].data_ptr(), gb[uid].data_ptr(), _stream()),
+                                                          ws.data_ptr(), nbytes, gx.data_ptr(), gw[uid].data_ptr(), gb[uid].data_ptr(), _native.stream()),
                            "ColorAffine backward")
         return (gx if ctx.needs_input_grad[0] else None), (gw if ctx.needs_input_grad[1] else None), (gb if ctx.needs_input_grad[2] else None), None
 

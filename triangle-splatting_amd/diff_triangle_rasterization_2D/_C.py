@@ -58,84 +58,10 @@ if C.cast(C.CDLL("libts2d.so", mode=os.RTLD_NOLOAD).ts2d_version, C.c_void_p).va
 
 FLAG_BACK_CULLING, FLAG_RICH_INFO, FLAG_DEBUG, FLAG_USE_SHS, FLAG_3D, FLAG_SH_FACTORED = 1, 2, 4, 8, 16, 32
 
-_fp = C.c_void_p
+# Every struct mirror and every function signature of the C ABI is declared once, in _abi.py; the names stay importable from here.
+from ._abi import _BackwardOut, _Camera, _ForwardOut, _Geometry, _LossGrads, _State, bind  # noqa: E402,F401
 
-
-class _Camera(C.Structure):
-    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("tan_fovx", C.c_float), ("tan_fovy", C.c_float),
-                ("viewmatrix", _fp), ("projmatrix", _fp), ("campos", _fp)]
-
-
-class _Geometry(C.Structure):
-    _fields_ = [("P", C.c_int32), ("sh_degree", C.c_int32), ("M", C.c_int32), ("C", C.c_int32),
-                ("gamma", C.c_float), ("scale_modifier", C.c_float), ("background_depth", C.c_float),
-                ("background", _fp), ("vertex", _fp), ("shs", _fp), ("feature", _fp), ("opacity", _fp), ("background_depth_dev", _fp)]
-
-
-class _ForwardOut(C.Structure):
-    _fields_ = [("out_feature", _fp), ("depth", _fp), ("normal", _fp), ("contrib_sum", _fp), ("contrib_max", _fp)]
-
-
-class _LossGrads(C.Structure):
-    _fields_ = [("dL_dout_feature", _fp), ("dL_dout_depth", _fp), ("dL_dout_normal", _fp)]
-
-
-class _BackwardOut(C.Structure):
-    _fields_ = [("dL_dvertex", _fp), ("dL_dcenter2D", _fp), ("dL_dshs", _fp), ("dL_dfeature", _fp),
-                ("dL_dopacity", _fp)]
-
-
-class _State(C.Structure):
-    _fields_ = [("geometry", _fp), ("geometry_bytes", C.c_size_t), ("binning", _fp), ("binning_bytes", C.c_size_t),
-                ("image", _fp), ("image_bytes", C.c_size_t)]
-
-
-_lib.ts2d_version.restype = C.c_char_p
-_lib.ts2d_last_error.restype = C.c_char_p
-_lib.ts2d_geometry_state_bytes.restype = C.c_size_t
-_lib.ts2d_geometry_state_bytes.argtypes = [C.c_int32]
-_lib.ts2d_binning_state_bytes.restype = C.c_size_t
-_lib.ts2d_binning_state_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
-_lib.ts2d_image_state_bytes.restype = C.c_size_t
-_lib.ts2d_image_state_bytes.argtypes = [C.c_int32, C.c_int32]
-_lib.ts2d_backward_scratch_bytes.restype = C.c_size_t
-_lib.ts2d_backward_scratch_bytes.argtypes = [C.c_int32]
-_lib.ts2d_forward_bin.restype = C.c_int
-_lib.ts2d_forward_bin.argtypes = [C.POINTER(_Camera), C.POINTER(_Geometry), C.c_uint32, _fp, C.POINTER(_State),
-                                  C.POINTER(C.c_int64), _fp]
-_lib.ts2d_forward_render.restype = C.c_int
-_lib.ts2d_forward_render.argtypes = [C.POINTER(_Camera), C.POINTER(_Geometry), C.c_uint32, C.c_int64,
-                                     C.POINTER(_State), C.POINTER(_ForwardOut), _fp]
-_lib.ts2d_forward.restype = C.c_int
-_lib.ts2d_forward.argtypes = [C.POINTER(_Camera), C.POINTER(_Geometry), C.c_uint32, _fp, C.POINTER(_State), C.c_int64,
-                              C.POINTER(_ForwardOut), _fp]
-_lib.ts2d_forward_status.restype = C.c_int
-_lib.ts2d_forward_status.argtypes = [C.POINTER(_State), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64), _fp]
-_lib.ts2d_backward.restype = C.c_int
-_lib.ts2d_backward.argtypes = [C.POINTER(_Camera), C.POINTER(_Geometry), C.c_uint32, C.c_int64, _fp,
-                               C.POINTER(_State), C.POINTER(_LossGrads), _fp, C.c_size_t, C.POINTER(_BackwardOut), _fp]
-_lib.ts2d_backward_ranged.restype = C.c_int
-_lib.ts2d_backward_ranged.argtypes = [C.POINTER(_Camera), C.POINTER(_Geometry), C.c_uint32, C.c_int64, _fp,
-                                      C.POINTER(_State), C.POINTER(_LossGrads), _fp, C.c_size_t, C.POINTER(_BackwardOut), C.c_int32, C.POINTER(_fp), _fp]
-_lib.ts2d_backward_range_rows.restype = C.c_int32
-_lib.ts2d_backward_range_rows.argtypes = [C.c_int32, C.c_int32]
-_lib.ts2d_sh_grad_expand.restype = C.c_int
-_lib.ts2d_sh_grad_expand.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp]
-_lib.ts2d_binning_capacity.restype = C.c_int64
-_lib.ts2d_binning_capacity.argtypes = [C.c_size_t, C.c_int32, C.c_int32]
-_lib.ts2d_instance_capacity_hint.restype = C.c_int64
-_lib.ts2d_instance_capacity_hint.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_uint32]
-_lib.ts2d_set_capacity_hint_key.restype = None
-_lib.ts2d_set_capacity_hint_key.argtypes = [C.c_uint64]
-_lib.ts2d_speculative_overflow_count.restype = C.c_uint64
-_lib.ts2d_speculative_overflow_count.argtypes = []
-_lib.ts2d_forward_speculative.restype = C.c_int
-_lib.ts2d_forward_speculative.argtypes = [C.POINTER(_Camera), C.POINTER(_Geometry), C.c_uint32, _fp, C.POINTER(_State), C.POINTER(_ForwardOut),
-                                          C.POINTER(C.c_int64), _fp]
-_lib.ts2d_profile_enable.argtypes = [C.c_int]
-_lib.ts2d_profile_only.argtypes = [C.c_char_p]
-_lib.ts2d_profile_read.restype = C.c_int
-_lib.ts2d_profile_read.argtypes = [C.c_int32, C.c_char_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+bind(_lib)
 
 
 def set_capacity_hint_key(key: int) -> None:
@@ -169,11 +95,15 @@ def _ptr(t):
     return t.data_ptr()
 
 
-def _require_device(vertex: torch.Tensor):
-    if not vertex.is_cuda:
-        raise RuntimeError(
-            "diff_triangle_rasterization_2D (MI355X build) needs tensors on a HIP device; there is no CPU fallback"
-        )
+def stream() -> int:
+    """The current stream of the current device, as the `void *stream` of the C ABI."""
+    return torch.cuda.current_stream().cuda_stream
+
+
+def require_device(what: str, *tensors, verb: str = "needs"):
+    """There is no CPU or eager fallback anywhere in the package: component `what` refuses tensors that are not on a HIP device."""
+    if not all(t.is_cuda for t in tensors):
+        raise RuntimeError(f"{what} (MI355X build) {verb} tensors on a HIP device; there is no CPU fallback")
 
 
 def _contiguous_or_raise(*tensors):
@@ -236,7 +166,7 @@ def forward_status(P, W, H, geometryBuffer, imageBuffer):
     st = _State(_ptr(geometryBuffer), geometryBuffer.numel(), None, 0, _ptr(imageBuffer), imageBuffer.numel())
     over, n = C.c_int32(0), C.c_int64(0)
     with torch.cuda.device(imageBuffer.device):
-        _check(_lib.ts2d_forward_status(C.byref(st), int(P), int(W), int(H), C.byref(over), C.byref(n), torch.cuda.current_stream().cuda_stream),
+        _check(_lib.ts2d_forward_status(C.byref(st), int(P), int(W), int(H), C.byref(over), C.byref(n), stream()),
                "forward_status")
     return bool(over.value), int(n.value)
 
@@ -244,7 +174,7 @@ def forward_status(P, W, H, geometryBuffer, imageBuffer):
 def sh_grad_expand(vertex, campos, dL_dcolor, sh_degree, M, out=None):
     """dL_dshs (P, M, 3) = sum over views v of basis(normalize(centroid - campos[v])) x dL_dcolor[v]  (ts2d_sh_grad_expand).
     vertex (P,3,3), campos (V,3), dL_dcolor (V,P,3): contiguous float32 on one HIP device."""
-    _require_device(vertex)
+    require_device("diff_triangle_rasterization_2D", vertex)
     _contiguous_or_raise(vertex, campos, dL_dcolor, out)
     _f32_or_raise(vertex, campos, dL_dcolor, out)
     P, V = vertex.size(0), campos.size(0)
@@ -253,8 +183,8 @@ def sh_grad_expand(vertex, campos, dL_dcolor, sh_degree, M, out=None):
     with torch.cuda.device(vertex.device):
         if out is None:
             out = (torch.zeros if P == 0 else torch.empty)((P, int(M), 3), device=vertex.device, dtype=torch.float32)
-        _check(_lib.ts2d_sh_grad_expand(P, int(sh_degree), int(M), V, _ptr(vertex), _ptr(campos), _ptr(dL_dcolor), _ptr(out),
-                                        torch.cuda.current_stream().cuda_stream), "sh_grad_expand")
+        _check(_lib.ts2d_sh_grad_expand(P, int(sh_degree), int(M), V, _ptr(vertex), _ptr(campos), _ptr(dL_dcolor), _ptr(out), stream()),
+               "sh_grad_expand")
     return out
 
 

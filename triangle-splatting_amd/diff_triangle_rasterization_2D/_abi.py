@@ -1,0 +1,182 @@
+"""The C ABI of libts2d.so as ctypes sees it, declared once: the mirrors of the structs of include/*.h and the signature of every function
+they declare (and of the lab library's additions, csrc/ts2d_lab.h).  Pure ctypes: no torch, no library is loaded here -- `_C.py` binds the
+library the package loads, the CPU tests bind a CDLL of their own.  tests/test_cabi_cpu.py holds both tables against the headers: the structs
+by sizeof / offsetof, the functions prototype by prototype.
+
+Pointers to device memory and opaque handles (streams, workspaces) are c_void_p; a pointer the HOST dereferences is typed by what it points
+at: POINTER(mirror) for a struct, POINTER(scalar) for a value the callee returns through it, POINTER(c_void_p) for an array of pointers.
+"""
+import ctypes as C
+
+_vp = C.c_void_p
+
+
+class _Camera(C.Structure):  # ts2d_camera
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("tan_fovx", C.c_float), ("tan_fovy", C.c_float),
+                ("viewmatrix", _vp), ("projmatrix", _vp), ("campos", _vp)]
+
+
+class _Geometry(C.Structure):  # ts2d_geometry
+    _fields_ = [("P", C.c_int32), ("sh_degree", C.c_int32), ("M", C.c_int32), ("C", C.c_int32),
+                ("gamma", C.c_float), ("scale_modifier", C.c_float), ("background_depth", C.c_float),
+                ("background", _vp), ("vertex", _vp), ("shs", _vp), ("feature", _vp), ("opacity", _vp), ("background_depth_dev", _vp)]
+
+
+class _ForwardOut(C.Structure):  # ts2d_forward_out
+    _fields_ = [("out_feature", _vp), ("depth", _vp), ("normal", _vp), ("contrib_sum", _vp), ("contrib_max", _vp)]
+
+
+class _LossGrads(C.Structure):  # ts2d_loss_grads
+    _fields_ = [("dL_dout_feature", _vp), ("dL_dout_depth", _vp), ("dL_dout_normal", _vp)]
+
+
+class _BackwardOut(C.Structure):  # ts2d_backward_out
+    _fields_ = [("dL_dvertex", _vp), ("dL_dcenter2D", _vp), ("dL_dshs", _vp), ("dL_dfeature", _vp),
+                ("dL_dopacity", _vp)]
+
+
+class _State(C.Structure):  # ts2d_state
+    _fields_ = [("geometry", _vp), ("geometry_bytes", C.c_size_t), ("binning", _vp), ("binning_bytes", C.c_size_t),
+                ("image", _vp), ("image_bytes", C.c_size_t)]
+
+
+class _Slice(C.Structure):  # tso_adam_slice, include/ts_optim.h
+    _fields_ = [("param", _vp), ("grad", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp), ("count", C.c_int64), ("step_size", C.c_float),
+                ("bias2_sqrt", C.c_float), ("grad_scale", C.c_float), ("step_size_tail", C.c_float), ("index0", C.c_int64),
+                ("period", C.c_int32), ("split", C.c_int32)]
+
+
+class _RowSlice(C.Structure):  # tso_row_slice, include/ts_optim.h
+    _fields_ = [("param", _vp), ("grad", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp), ("floats_per_row", C.c_int32), ("step_size", C.c_float),
+                ("bias2_sqrt", C.c_float), ("grad_scale", C.c_float)]
+
+
+SH_ROW_SLICES = 2  # TSO_SH_ROW_SLICES
+
+
+class _ShFactoredStep(C.Structure):  # tso_sh_factored_step, include/ts_optim.h
+    _fields_ = [("P", C.c_int32), ("M", C.c_int32), ("sh_degree", C.c_int32), ("V", C.c_int32), ("vertex", _vp), ("campos", _vp), ("dL_dcolor", _vp),
+                ("param_dc", _vp), ("exp_avg_dc", _vp), ("exp_avg_sq_dc", _vp), ("param_rest", _vp), ("exp_avg_rest", _vp), ("exp_avg_sq_rest", _vp),
+                ("dc_stride", C.c_int64), ("rest_stride", C.c_int64), ("step_size_dc", C.c_float), ("bias2_sqrt_dc", C.c_float),
+                ("step_size_rest", C.c_float), ("bias2_sqrt_rest", C.c_float), ("grad_scale", C.c_float), ("num_rows", C.c_int32),
+                ("rows", _RowSlice * SH_ROW_SLICES)]
+
+
+# name -> (restype, argtypes), header by header in the headers' order
+SIGNATURES = {
+    # ---- include/ts2d.h
+    "ts2d_version": (C.c_char_p, []),
+    "ts2d_last_error": (C.c_char_p, []),
+    "ts2d_geometry_state_bytes": (C.c_size_t, [C.c_int32]),
+    "ts2d_binning_state_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "ts2d_image_state_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "ts2d_backward_scratch_bytes": (C.c_size_t, [C.c_int32]),
+    "ts2d_binning_capacity": (C.c_int64, [C.c_size_t, C.c_int32, C.c_int32]),
+    "ts2d_forward_bin": (C.c_int, [C.POINTER(_Camera), C.POINTER(_Geometry), C.c_uint32, _vp, C.POINTER(_State), C.POINTER(C.c_int64), _vp]),
+    "ts2d_forward_render": (C.c_int, [C.POINTER(_Camera), C.POINTER(_Geometry), C.c_uint32, C.c_int64, C.POINTER(_State), C.POINTER(_ForwardOut),
+                                      _vp]),
+    "ts2d_backward": (C.c_int, [C.POINTER(_Camera), C.POINTER(_Geometry), C.c_uint32, C.c_int64, _vp, C.POINTER(_State), C.POINTER(_LossGrads), _vp,
+                                C.c_size_t, C.POINTER(_BackwardOut), _vp]),
+    "ts2d_backward_ranged": (C.c_int, [C.POINTER(_Camera), C.POINTER(_Geometry), C.c_uint32, C.c_int64, _vp, C.POINTER(_State),
+                                       C.POINTER(_LossGrads), _vp, C.c_size_t, C.POINTER(_BackwardOut), C.c_int32, C.POINTER(_vp), _vp]),
+    "ts2d_backward_range_rows": (C.c_int32, [C.c_int32, C.c_int32]),
+    "ts2d_forward": (C.c_int, [C.POINTER(_Camera), C.POINTER(_Geometry), C.c_uint32, _vp, C.POINTER(_State), C.c_int64, C.POINTER(_ForwardOut), _vp]),
+    "ts2d_forward_speculative": (C.c_int, [C.POINTER(_Camera), C.POINTER(_Geometry), C.c_uint32, _vp, C.POINTER(_State), C.POINTER(_ForwardOut),
+                                           C.POINTER(C.c_int64), _vp]),
+    "ts2d_instance_capacity_hint": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_uint32]),
+    "ts2d_set_capacity_hint_key": (None, [C.c_uint64]),
+    "ts2d_speculative_overflow_count": (C.c_uint64, []),
+    "ts2d_forward_status": (C.c_int, [C.POINTER(_State), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64), _vp]),
+    "ts2d_sh_grad_expand": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "ts2d_profile_enable": (None, [C.c_int]),
+    "ts2d_profile_only": (None, [C.c_char_p]),
+    "ts2d_profile_reset": (None, []),
+    "ts2d_profile_read": (C.c_int, [C.c_int32, C.c_char_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    # ---- include/ts_loss.h
+    "tsl_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "tsl_photometric_forward": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32, _vp, C.c_size_t, _vp, _vp]),
+    "tsl_photometric_backward": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _vp, C.c_size_t, _vp, _vp, _vp]),
+    "tsl_depth_normal_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_double]),
+    "tsl_depth_normal_forward": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_double, C.c_float, _vp, C.c_size_t, _vp, _vp]),
+    "tsl_depth_normal_backward": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_double, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
+    "tsl_aux_loss_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_double]),
+    "tsl_dog_mask": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_double, _vp,
+                               C.c_size_t, _vp, _vp]),
+    "tsl_smoothness_mask": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_float, _vp, C.c_size_t, _vp, _vp]),
+    "tsl_masked_l1_forward": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_size_t, _vp, _vp]),
+    "tsl_masked_l1_backward": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    "tsl_scharr_smoothness_forward": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_size_t, _vp, _vp]),
+    "tsl_scharr_smoothness_backward": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_size_t, _vp, _vp, _vp]),
+    "tsl_downsample_forward": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
+    "tsl_downsample_backward": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
+    "tsl_downsample_forward_planes": (C.c_int, [C.c_int32, C.POINTER(_vp), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_vp), _vp]),
+    "tsl_downsample_backward_planes": (C.c_int, [C.c_int32, C.POINTER(_vp), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_vp), _vp]),
+    "tsl_reg_workspace_bytes": (C.c_size_t, []),
+    "tsl_reg_prepared_bytes": (C.c_size_t, [C.c_int32]),
+    "tsl_reg_prepare": (C.c_int, [C.c_int32, _vp, _vp, C.c_size_t, _vp]),
+    "tsl_reg_forward": (C.c_int, [C.c_int32, _vp, _vp, _vp, C.c_float, C.c_float, C.c_int32, C.c_float, _vp, C.c_size_t, _vp, _vp]),
+    "tsl_reg_backward": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, C.c_float, C.c_int32, C.c_float, _vp, _vp, _vp, _vp]),
+    "tsl_color_affine_forward": (C.c_int, [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
+    "tsl_color_affine_backward": (C.c_int, [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
+    # ---- include/ts_knn.h
+    "tsk_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "tsk_mean_dist3": (C.c_int, [C.c_int32, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "tsk_nearest_other": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_size_t, _vp]),
+    # ---- include/ts_model.h
+    "tsm_training_statistic": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tsm_select_scratch_bytes": (C.c_size_t, [C.c_int32]),
+    "tsm_select_rows": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp, _vp, C.c_size_t, C.POINTER(C.c_uint32), _vp]),
+    "tsm_scatter_rows": (C.c_int, [C.c_int64, C.c_int32, _vp, _vp, _vp, C.c_int64, _vp]),
+    "tsm_gather_rows": (C.c_int, [C.c_int64, C.c_int32, _vp, _vp, _vp, C.c_int64, _vp]),
+    "tsm_grow_classify": (C.c_int, [C.c_int32, _vp, _vp, _vp, C.c_float, C.c_float, C.c_float, _vp, _vp]),
+    "tsm_split_vertex": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "tsm_update_mask": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_float, C.c_float, _vp, _vp]),
+    "tsm_clip": (C.c_int, [C.c_int32, C.c_int32, _vp, C.c_float, _vp, _vp, _vp, _vp]),
+    "tsm_opacity_reset": (C.c_int, [C.c_int32, C.c_float, _vp, _vp, _vp, _vp]),
+    "tsm_max_vertex_distance": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp]),
+    "tsm_state_digest": (C.c_int, [C.c_int32, C.POINTER(_vp), C.POINTER(C.c_uint64), _vp, _vp]),
+    # ---- include/ts_optim.h
+    "tso_adam_step": (C.c_int, [C.POINTER(_Slice), C.c_int32, C.c_double, C.c_double, C.c_double, _vp]),
+    "tso_adam_step_sh_factored": (C.c_int, [C.POINTER(_ShFactoredStep), C.c_double, C.c_double, C.c_double, _vp]),
+    # ---- include/ts_mesh.h
+    "ts2d_mesh_geometry_state_bytes": (C.c_size_t, [C.c_int32]),
+    "ts2d_mesh_bin": (C.c_int, [C.POINTER(_Camera), C.c_float, C.c_int32, _vp, C.c_int32, _vp, C.POINTER(_State), C.POINTER(C.c_int64), _vp]),
+    "ts2d_mesh_render": (C.c_int, [C.POINTER(_Camera), C.c_int32, _vp, _vp, C.c_int64, C.POINTER(_State), _vp, _vp, _vp, _vp, _vp]),
+    "ts2d_mesh_render_counted": (C.c_int, [C.POINTER(_Camera), C.c_int32, _vp, _vp, C.c_int64, C.POINTER(_State), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ts2d_mesh_census_add": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    # ---- include/ts_weld.h
+    "ts2d_weld_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "ts2d_weld_labels": (C.c_int, [C.c_int32, _vp, C.c_float, _vp, _vp, C.c_size_t, _vp]),
+    "ts2d_weld_labels_counted": (C.c_int, [C.c_int32, _vp, C.c_float, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "ts2d_weld_face_components": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "ts2d_weld_compact": (C.c_int, [C.c_int32, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "ts2d_weld_remap_faces": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "ts2d_weld_edge_census": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+}
+
+# what csrc/ts2d_lab.h adds in tools/bin/libts2d_lab.so (the test hooks: only in a library built with them)
+LAB_SIGNATURES = {
+    "ts2d_debug_read_state": (C.c_int, [C.POINTER(_State), C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_size_t, _vp]),
+    "ts2d_test_sort_pairs": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, C.c_int32, C.c_int32, _vp]),
+    "ts2d_test_inclusive_scan_rocprim": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),
+    "ts2d_lab_force_ticket_passes": (None, [C.c_int]),
+    "ts2d_lab_force_depth_pass4": (None, [C.c_int]),
+    "ts2d_test_quantile_scratch_bytes": (C.c_size_t, []),
+    "ts2d_test_quantile": (C.c_int, [_vp, C.c_size_t, C.c_float, _vp, _vp, _vp]),
+    "ts2d_lab_depth_split": (None, [C.c_int, C.c_int]),
+    "ts2d_lab_force_all_quadrants": (None, [C.c_int]),
+}
+
+
+def bind(lib):
+    """Sets restype and argtypes of every function of the C ABI on `lib` (a ctypes.CDLL of libts2d.so or of one of its lab / variant builds),
+    and of the lab entry points it has.  A library that lacks a product function is refused."""
+    missing = [name for name in SIGNATURES if not hasattr(lib, name)]
+    if missing:
+        raise ImportError(f"{getattr(lib, '_name', lib)} does not export {', '.join(missing)}: rebuild it with `python triangle-splatting_amd/build.py`")
+    for table in (SIGNATURES, LAB_SIGNATURES):
+        for name, (restype, argtypes) in table.items():
+            if table is SIGNATURES or hasattr(lib, name):
+                fn = getattr(lib, name)
+                fn.restype, fn.argtypes = restype, argtypes
+    return lib

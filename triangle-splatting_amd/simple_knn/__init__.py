@@ -9,25 +9,15 @@ CPU fallback.  Argument checks and messages follow submodules/simple-knn/interfa
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from diff_triangle_rasterization_2D import _C as _native
 
 _lib = _native._lib
-_fp = C.c_void_p
-_lib.tsk_workspace_bytes.restype = C.c_size_t
-_lib.tsk_workspace_bytes.argtypes = [C.c_int32]
-_lib.tsk_mean_dist3.restype = C.c_int
-_lib.tsk_mean_dist3.argtypes = [C.c_int32, _fp, _fp, _fp, C.c_size_t, _fp]
-_lib.tsk_nearest_other.restype = C.c_int
-_lib.tsk_nearest_other.argtypes = [C.c_int32, C.c_int32, _fp, _fp, _fp, C.c_size_t, _fp]
 
 
 def _prepare(points: torch.Tensor):
-    if not points.is_cuda:
-        raise RuntimeError("simple_knn (MI355X build) needs tensors on a HIP device; there is no CPU fallback")
+    _native.require_device("simple_knn", points)
     if points.dtype != torch.float32:
         raise RuntimeError("expected scalar type Float")
     return points.contiguous()  # interface.cu:21,46
@@ -45,7 +35,7 @@ def distCUDA2(points: torch.Tensor) -> torch.Tensor:
         nbytes = _lib.tsk_workspace_bytes(P)
         ws = torch.empty((nbytes,), device=pts.device, dtype=torch.uint8)
         _native._check(_lib.tsk_mean_dist3(P, pts.data_ptr(), means.data_ptr(), ws.data_ptr(), nbytes,
-                                           torch.cuda.current_stream().cuda_stream), "distCUDA2")
+                                           _native.stream()), "distCUDA2")
     return means
 
 
@@ -63,7 +53,7 @@ def nearestNeighbor(points: torch.Tensor, batch_size: int = 1) -> torch.Tensor:
             nbytes = _lib.tsk_workspace_bytes(P)
             ws = torch.empty((nbytes,), device=pts.device, dtype=torch.uint8)
             _native._check(_lib.tsk_nearest_other(P, int(batch_size), pts.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes,
-                                                  torch.cuda.current_stream().cuda_stream), "nearestNeighbor")
+                                                  _native.stream()), "nearestNeighbor")
     return out.view(torch.uint32)  # the reference returns kUInt32 (interface.cu:44)
 
 

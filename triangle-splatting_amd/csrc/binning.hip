@@ -32,6 +32,11 @@
 // The same rule removed the elected blocks from the scan (raw block sums, added up by the emission blocks) and from the census (published
 // by block 0 of the first scatter).  The round-1 rocPRIM calls (radix_sort_pairs, inclusive_scan) survive only as the comparators of
 // tests/test_binning_gpu.py.
+// Step 1 has three forms, chosen by depth_form(): these LSD passes; below ~9 k triangles the whole order in one launch
+// (depth_order_small_kernel); up to 500 k sampled splitters + per-bucket sorts in LDS (K0-K3 below).  Every form ranks with the same pieces,
+// each defined once at the top of the namespace: wave_match_rank (the 64-pair step), digit_exclusive_prefix / digit_run_starts (counts -> run
+// starts), lsd_rank_pass (a pass of a workgroup that holds its pairs in registers), DirectPrefix (the ticket-free prefixes), KeyCensus /
+// publish_instance_count (N and the fourth-pass verdict).
 #include "ts2d_common.h"
 #include "ts2d_wave.h"
 #include "ts2d_support.h"
@@ -53,6 +58,179 @@ __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v, int lane) //
     x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xC, 0xF, true); // row_bcast:31 -> rows 2 and 3
     return (uint32_t)x;
 }
+__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v) // on every lane
+{
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ void wave_min_max(uint32_t &lo, uint32_t &hi) // on every lane
+{
+    for (int o = 32; o > 0; o >>= 1)
+    {
+        lo = min(lo, (uint32_t)__shfl_xor((int)lo, o));
+        hi = max(hi, (uint32_t)__shfl_xor((int)hi, o));
+    }
+}
+
+// ---- the pieces every form of the stable radix ranking is made of ----------------------------------------------------------------------------------
+// Stable ranks of one step of 64 pairs: returns how many pairs with this lane's digit `d` (< 256; the caller decides which bits of its key that is)
+// the wave has ranked before -- in earlier steps (`cnt`, the wave's 256 LDS counters, advanced here) and in lower lanes of this one.  The lanes
+// holding equal digits find each other with one ballot per digit bit (wave64 match); ranks follow lane order, steps follow list order.
+__device__ __forceinline__ uint32_t wave_match_rank(uint32_t d, bool valid, uint32_t *cnt)
+{
+    // lanes whose digit differs from mine in some bit: (ballot of bit i) xor (my bit i, sign-extended), or-ed over the bits, in two 32-bit
+    // halves -- three instructions per bit and half (round 5; the select form `m &= one ? bb : ~bb` compiled to ~100 instructions per step,
+    // and a launch of a few resident workgroups per SIMD -- or ONE workgroup on one compute unit -- spends a good part of its time issuing exactly these)
+    const unsigned long long vm = ballot64(valid);
+    uint32_t mis_lo = ~(uint32_t)vm, mis_hi = ~(uint32_t)(vm >> 32);
+    // all eight bits, unrolled, however many the digit has (the bits above them are zero in every lane and cost a ballot that changes nothing): with
+    // the bit index a compile-time constant a bit is four instructions (v_bfe_i32, the compare behind the ballot, two fused xor-or); as a loop
+    // over a run-time bit count it was twelve (shift by an SGPR, select, loop control, two s_nop) -- 96 of the ~135 instructions of a 64-pair
+    // step, in kernels whose time IS this ranking (round 6: profiles/r06_rank_unroll.txt)
+#pragma unroll
+    for (int bit = 0; bit < 8; bit++)
+    {
+        const unsigned long long bb = ballot64((d >> bit) & 1u);
+        const uint32_t e = (uint32_t)__builtin_amdgcn_sbfe((int)d, bit, 1); // all ones when my bit is set
+        mis_lo |= (uint32_t)bb ^ e;
+        mis_hi |= (uint32_t)(bb >> 32) ^ e;
+    }
+    const uint32_t m_lo = ~mis_lo, m_hi = ~mis_hi; // the valid lanes that hold my digit
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi(m_hi, __builtin_amdgcn_mbcnt_lo(m_lo, 0u));
+    const uint32_t c = (uint32_t)(__popc(m_lo) + __popc(m_hi));
+    uint32_t seen = 0;
+    if (valid) seen = cnt[d];
+    wave_lds_order(); // every lane has read its digit's count before the group leaders advance it
+    if (valid && rank == c - 1u) cnt[d] = seen + c;
+    wave_lds_order();
+    return seen + rank;
+}
+
+// Exclusive prefix over the 256 digits of `total` in a workgroup of W waves (thread d < 256: digit d; the threads of waves 4 and up come along for
+// the barrier): wave64 DPP scan + the preceding waves' totals, which meet in wtot[4].
+template <int W>
+__device__ __forceinline__ uint32_t digit_exclusive_prefix(uint32_t total, uint32_t *wtot, int wave, int lane)
+{
+    const bool digit = W <= 4 || wave < NB / 64;
+    uint32_t inc = 0u;
+    if (digit)
+    {
+        inc = wave_inclusive_scan(total, lane);
+        if (lane == 63) wtot[wave] = inc;
+    }
+    __syncthreads();
+    uint32_t excl = inc - total;
+    if (digit)
+        for (int w = 0; w < wave; w++) excl += wtot[w];
+    return excl;
+}
+// The W waves' counts of digit t (wcnt[w][t], complete: barrier before) -> where the run of every (wave, digit) starts in (digit, wave) order, left in
+// wcnt (barrier after).  Returns the start of digit t's first run; `total` = the digit's count over the waves.
+template <int W>
+__device__ __forceinline__ uint32_t digit_run_starts(uint32_t (*wcnt)[NB], uint32_t *wtot, int wave, int lane, uint32_t &total)
+{
+    const int t = 64 * wave + lane;
+    const bool digit = W <= 4 || wave < NB / 64;
+    uint32_t c[W], tot = 0u;
+    if (digit)
+    {
+#pragma unroll
+        for (int w = 0; w < W; w++) { c[w] = wcnt[w][t]; tot += c[w]; }
+    }
+    const uint32_t start = digit_exclusive_prefix<W>(tot, wtot, wave, lane);
+    if (digit)
+    {
+        uint32_t run = start;
+#pragma unroll
+        for (int w = 0; w < W; w++) { wcnt[w][t] = run; run += c[w]; }
+    }
+    total = tot;
+    return start;
+}
+
+// One stable LSD pass, on digit (key >> shift) & 255, of a workgroup of W waves over the pairs it holds in registers (wave w: `mine` of the `per`
+// positions [w per, (w + 1) per) of the list, 64 consecutive ones per step).  Leaves in rk[] every pair's position in the list's (digit, wave,
+// step, lane) order -- the caller exchanges the pairs through LDS on it -- and in `digit_count` (thread d < 256) how many pairs hold digit d.
+template <int KBX, int W>
+__device__ __forceinline__ void lsd_rank_pass(const uint32_t (&key)[KBX], uint32_t (&rk)[KBX], int shift, int per, int mine, uint32_t (*wcnt)[NB],
+                                              uint32_t *wtot, uint32_t &digit_count)
+{
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    uint32_t *cnt = wcnt[wave];
+#pragma unroll
+    for (int k = 0; k < NB / 64; k++) cnt[lane + 64 * k] = 0u;
+    wave_lds_order();
+#pragma unroll
+    for (int b = 0; b < KBX; b++)
+    {
+        if (64 * b >= per) continue; // wave-uniform
+        rk[b] = wave_match_rank((key[b] >> shift) & 0xFFu, 64 * b + lane < mine, cnt);
+    }
+    __syncthreads();
+    digit_run_starts<W>(wcnt, wtot, wave, lane, digit_count);
+    __syncthreads();
+#pragma unroll
+    for (int b = 0; b < KBX; b++)
+        if (64 * b + lane < mine) rk[b] += cnt[(key[b] >> shift) & 0xFFu];
+}
+
+// The ticket-free ("DIRECT") prefixes of a scatter block: how many pairs of each digit sit in earlier chunks of its slab (`within`, from the raw table
+// rows), in earlier slabs (`before`) and in all slabs (`total`, both from the slabs' totals `acc`).
+constexpr int TS_DIRECT_MAX_SLABS = 48; // every scatter block reads the totals of all slabs: beyond this the hierarchical pass is cheaper
+struct DirectPrefix
+{
+    uint4 within = make_uint4(0u, 0u, 0u, 0u), before = make_uint4(0u, 0u, 0u, 0u), total = make_uint4(0u, 0u, 0u, 0u);
+    // Wave w takes every fourth row, lane l the digits 4l .. 4l + 3 (one dwordx4 per row: at most 16 + 12 loads per lane, all requested here -- the
+    // caller puts this behind its key loads and its ranking in front of park())
+    __device__ __forceinline__ void load(const RadixScratchView &r, const uint32_t *__restrict__ acc, int chunk, int wave, int lane)
+    {
+        const int slab = chunk >> 6, c0 = slab * 64;
+        const uint4 *tab4 = (const uint4 *)r.table + (size_t)c0 * (NB / 4) + lane;
+        const uint4 *acc4 = (const uint4 *)acc + lane;
+#pragma unroll 4
+        for (int k = 0; k < 16; k++)
+        {
+            const int c = wave + 4 * k;
+            if (c0 + c < chunk)
+            {
+                const uint4 v = tab4[(size_t)c * (NB / 4)];
+                within.x += v.x; within.y += v.y; within.z += v.z; within.w += v.w;
+            }
+        }
+#pragma unroll 4
+        for (int k = 0; k < TS_DIRECT_MAX_SLABS / 4; k++)
+        {
+            const int sl = wave + 4 * k;
+            if (sl < r.slabs)
+            {
+                const uint4 v = acc4[(size_t)sl * (NB / 4)];
+                total.x += v.x; total.y += v.y; total.z += v.z; total.w += v.w;
+                if (sl < slab) { before.x += v.x; before.y += v.y; before.z += v.z; before.w += v.w; }
+            }
+        }
+    }
+    // the four waves' partial sums meet in LDS: 8 x 256 words at `x` (within, before) and 4 x 256 at `xtotal`; barrier, then fold()
+    __device__ __forceinline__ void park(uint32_t *x, uint32_t *xtotal, int wave, int lane) const
+    {
+        *(uint4 *)(x + wave * NB + 4 * lane) = within;
+        *(uint4 *)(x + (4 + wave) * NB + 4 * lane) = before;
+        *(uint4 *)(xtotal + wave * NB + 4 * lane) = total;
+    }
+    // digit t: pairs in earlier chunks of the grid (within + before) and in the whole array
+    static __device__ __forceinline__ void fold(const uint32_t *x, const uint32_t *xtotal, int t, uint32_t &d_earlier, uint32_t &d_total)
+    {
+        uint32_t d_within = 0u, d_before = 0u;
+        d_total = 0u;
+#pragma unroll
+        for (int w = 0; w < 4; w++)
+        {
+            d_within += x[w * NB + t];
+            d_before += x[(4 + w) * NB + t];
+            d_total += xtotal[w * NB + t];
+        }
+        d_earlier = d_before + d_within;
+    }
+};
 
 // Elects the block that arrives last at `ticket` among `count` arrivals; the elected block resets the ticket for the next
 // launch and returns true on all of its threads.  Data handed to the elected block travels as write-through (sc0 sc1) stores and
@@ -134,6 +312,49 @@ struct DepthCensus
     uint32_t force_varying;        // lab library only (ts2d_lab_force_depth_pass4): key bits reported as varying whatever the scene holds
 };
 __device__ __forceinline__ bool pass_skipped(const uint32_t *skip_flag) { return skip_flag && peer_load(skip_flag) != 0u; }
+// What the depth sort's first pass takes stock of (see above): the sum of the tile counts and which key bits differ between VISIBLE keys.
+struct KeyCensus
+{
+    unsigned long long tiles = 0ull;
+    uint32_t kor = 0u, kand = 0xFFFFFFFFu;
+    __device__ __forceinline__ void add(uint32_t key, uint32_t tiles_touched)
+    {
+        tiles += tiles_touched;
+        if (key != 0u) { kor |= key; kand &= key; } // culled triangles (key 0) emit nothing wherever they land: they do not count
+    }
+    __device__ __forceinline__ void combine(unsigned long long s, uint32_t o, uint32_t a) { tiles += s; kor |= o; kand &= a; }
+    __device__ __forceinline__ void wave_fold() // on every lane
+    {
+        for (int d = 32; d > 0; d >>= 1) combine(__shfl_xor(tiles, d), __shfl_xor(kor, d), __shfl_xor(kand, d));
+    }
+    // The waves' folded censuses meet in three LDS arrays of the caller: park (barrier) gather
+    __device__ __forceinline__ void park(unsigned long long *s, uint32_t *o, uint32_t *a) const
+    {
+        if ((threadIdx.x & 63) == 0) { s[threadIdx.x >> 6] = tiles; o[threadIdx.x >> 6] = kor; a[threadIdx.x >> 6] = kand; }
+    }
+    template <int W>
+    static __device__ __forceinline__ KeyCensus gather(const unsigned long long *s, const uint32_t *o, const uint32_t *a)
+    {
+        KeyCensus c;
+#pragma unroll
+        for (int w = 0; w < W; w++) c.combine(s[w], o[w], a[w]);
+        return c;
+    }
+    // Depths are positive floats: when all visible keys share their top byte the fourth pass has nothing to order.  No visible triangle at all:
+    // or = 0, and = ~0 -> every bit varies -> false.  `force_varying`: DepthCensus
+    __device__ __forceinline__ bool top_byte_constant(uint32_t force_varying = 0u) const { return (((kor ^ kand) | force_varying) >> 24) == 0u; }
+};
+// N and the verdict on the fourth pass leave as soon as they are known.  `host_out`: a pinned, device-visible host word or null; the host reads it
+// after the event recorded behind the kernel (no copy kernel in between).  PEER: the ticket path's write-through store of the verdict.
+template <bool PEER = false>
+__device__ __forceinline__ void publish_instance_count(unsigned long long N, unsigned long long *n_out, uint32_t *top_const, bool verdict,
+                                                       unsigned long long *host_out)
+{
+    *n_out = N;
+    if (PEER) peer_store(top_const, verdict ? 1u : 0u);
+    else *top_const = verdict ? 1u : 0u;
+    if (host_out) __hip_atomic_store(host_out, N, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
 
 template <bool CENSUS, int CH>
 __global__ void __launch_bounds__(256) rs_hist_kernel(const uint32_t *__restrict__ keys, int64_t n, const unsigned long long *n_dev, int shift,
@@ -149,8 +370,7 @@ __global__ void __launch_bounds__(256) rs_hist_kernel(const uint32_t *__restrict
     bins[t] = 0u;
     __syncthreads();
     const int64_t base = (int64_t)chunk * CH;
-    unsigned long long tsum = 0;
-    uint32_t kor = 0u, kand = 0xFFFFFFFFu;
+    KeyCensus mine;
 #pragma unroll 4
     for (int b = 0; b < CH / 256; b++)
     {
@@ -159,30 +379,22 @@ __global__ void __launch_bounds__(256) rs_hist_kernel(const uint32_t *__restrict
         {
             const uint32_t k = keys[i];
             atomicAdd(&bins[(k >> shift) & mask], 1u);
-            if (CENSUS)
-            {
-                tsum += census.tiles_touched[i];
-                if (k != 0u) { kor |= k; kand &= k; }
-            }
+            if (CENSUS) mine.add(k, census.tiles_touched[i]);
         }
     }
     if (CENSUS)
     {
-        for (int o = 32; o > 0; o >>= 1)
-        {
-            tsum += __shfl_xor(tsum, o);
-            kor |= __shfl_xor(kor, o);
-            kand &= __shfl_xor(kand, o);
-        }
-        if ((t & 63) == 0) { csum[t >> 6] = tsum; cor[t >> 6] = kor; cand[t >> 6] = kand; }
+        mine.wave_fold();
+        mine.park(csum, cor, cand);
     }
     __syncthreads();
     peer_store(r.table + (size_t)chunk * NB + t, bins[t]);
     if (CENSUS && t == 0)
     {
-        peer_store(census.chunk_sum + chunk, csum[0] + csum[1] + csum[2] + csum[3]);
-        peer_store(census.chunk_or + chunk, cor[0] | cor[1] | cor[2] | cor[3]);
-        peer_store(census.chunk_and + chunk, cand[0] & cand[1] & cand[2] & cand[3]);
+        const KeyCensus c = KeyCensus::gather<4>(csum, cor, cand);
+        peer_store(census.chunk_sum + chunk, c.tiles);
+        peer_store(census.chunk_or + chunk, c.kor);
+        peer_store(census.chunk_and + chunk, c.kand);
     }
 
     const int slab = chunk >> 6, c0 = slab * 64, c1 = min(r.chunks, c0 + 64);
@@ -217,44 +429,21 @@ __global__ void __launch_bounds__(256) rs_hist_kernel(const uint32_t *__restrict
             total += v[k];
         }
     }
-    {
-        // exclusive prefix of the 256 digit totals: wave64 DPP scan + the preceding waves' totals
-        __shared__ uint32_t wtot[4];
-        const uint32_t inc = wave_inclusive_scan(total, t & 63);
-        if ((t & 63) == 63) wtot[t >> 6] = inc;
-        __syncthreads();
-        uint32_t before = 0;
-        for (int w = 0; w < (t >> 6); w++) before += wtot[w];
-        r.binbase[t] = before + inc - total;
-    }
+    __shared__ uint32_t wtot[4];
+    r.binbase[t] = digit_exclusive_prefix<4>(total, wtot, t >> 6, t & 63);
     if (CENSUS)
     {
         // this block arrived last of all: every chunk's census is visible (same hand-off as the digit counts)
-        unsigned long long sum = 0;
-        uint32_t o = 0u, a = 0xFFFFFFFFu;
-        for (int c = t; c < r.chunks; c += 256)
-        {
-            sum += peer_load(census.chunk_sum + c);
-            o |= peer_load(census.chunk_or + c);
-            a &= peer_load(census.chunk_and + c);
-        }
-        for (int d = 32; d > 0; d >>= 1)
-        {
-            sum += __shfl_xor(sum, d);
-            o |= __shfl_xor(o, d);
-            a &= __shfl_xor(a, d);
-        }
+        KeyCensus all;
+        for (int c = t; c < r.chunks; c += 256) all.combine(peer_load(census.chunk_sum + c), peer_load(census.chunk_or + c), peer_load(census.chunk_and + c));
+        all.wave_fold();
         __syncthreads();
-        if ((t & 63) == 0) { csum[t >> 6] = sum; cor[t >> 6] = o; cand[t >> 6] = a; }
+        all.park(csum, cor, cand);
         __syncthreads();
         if (t == 0)
         {
-            const unsigned long long N = csum[0] + csum[1] + csum[2] + csum[3];
-            const uint32_t varying = ((cor[0] | cor[1] | cor[2] | cor[3]) ^ (cand[0] & cand[1] & cand[2] & cand[3])) | census.force_varying;
-            *census.n_out = N;
-            peer_store(census.top_const, (varying >> 24) == 0u ? 1u : 0u); // no visible triangle at all: or = 0, and = ~0 -> varying = ~0 -> not set
-            // pinned, device-visible host word: the host reads it after the event recorded behind this kernel (no copy kernel in between)
-            if (census.host_out) __hip_atomic_store(census.host_out, N, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            all = KeyCensus::gather<4>(csum, cor, cand);
+            publish_instance_count<true>(all.tiles, census.n_out, census.top_const, all.top_byte_constant(census.force_varying), census.host_out);
         }
     }
 }
@@ -264,7 +453,6 @@ __global__ void __launch_bounds__(256) rs_hist_kernel(const uint32_t *__restrict
 // that chain IS the kernel (18 us for 4 MB of keys).  Here a block leaves its 256 counts as a table row and adds them to its slab's totals
 // with fire-and-forget atomics, and that is all; the scatter kernel that follows works out the three prefixes it needs from the rows
 // (<= 63 rows of its slab + the slabs' totals, loaded while its keys are on their way).
-constexpr int TS_DIRECT_MAX_SLABS = 48; // every scatter block reads the totals of all slabs: beyond this the hierarchical pass is cheaper
 template <int CH>
 __global__ void __launch_bounds__(256) rs_hist_direct_kernel(const uint32_t *__restrict__ keys, int64_t n, const unsigned long long *n_dev, int shift,
                                                               uint32_t mask, RadixScratchView r, uint32_t *__restrict__ acc, const uint32_t *skip_flag)
@@ -300,7 +488,7 @@ __global__ void __launch_bounds__(256) rs_hist_direct_kernel(const uint32_t *__r
 }
 
 // The depth sort's first histogram, ticket-free like the one above, with the census riding along: a block leaves its part of N and of the
-// key-bit OR / OR-of-complements as three per-chunk words; block 0 of the scatter kernel that follows adds them up and publishes N (device
+// key-bit OR / AND as three per-chunk words; block 0 of the scatter kernel that follows adds them up and publishes N (device
 // word + pinned host word) and the top-byte verdict (`top_const`).  No ticket at all: electing a publisher HERE costs one same-address
 // atomic per block, and 488 of those in a row take longer (17 us) than the histogram itself.  Large scenes (more than
 // TS_DIRECT_MAX_SLABS slabs) keep rs_hist_kernel<true>.
@@ -310,14 +498,13 @@ __global__ void __launch_bounds__(256) rs_hist_census_direct_kernel(const uint32
 {
     __shared__ uint32_t bins[NB];
     __shared__ unsigned long long csum[4];
-    __shared__ uint32_t cor[4], cnand[4];
+    __shared__ uint32_t cor[4], cand[4];
     const int t = threadIdx.x, chunk = rs_chunk_of_block(r.chunks);
     if (chunk < 0) return;
     bins[t] = 0u;
     __syncthreads();
     const int64_t base = (int64_t)chunk * CH;
-    unsigned long long tsum = 0;
-    uint32_t kor = 0u, knand = 0u;
+    KeyCensus mine;
 #pragma unroll
     for (int b = 0; b < CH / 256; b++)
     {
@@ -326,26 +513,21 @@ __global__ void __launch_bounds__(256) rs_hist_census_direct_kernel(const uint32
         {
             const uint32_t k = keys[i];
             atomicAdd(&bins[k & mask], 1u);
-            tsum += census.tiles_touched[i];
-            if (k != 0u) { kor |= k; knand |= ~k; }
+            mine.add(k, census.tiles_touched[i]);
         }
     }
-    for (int o = 32; o > 0; o >>= 1)
-    {
-        tsum += __shfl_xor(tsum, o);
-        kor |= __shfl_xor(kor, o);
-        knand |= __shfl_xor(knand, o);
-    }
-    if ((t & 63) == 0) { csum[t >> 6] = tsum; cor[t >> 6] = kor; cnand[t >> 6] = knand; }
+    mine.wave_fold();
+    mine.park(csum, cor, cand);
     __syncthreads();
     const uint32_t c = bins[t];
     r.table[(size_t)chunk * NB + t] = c;
     if (c) __hip_atomic_fetch_add(acc + (size_t)(chunk >> 6) * NB + t, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (t == 0)
     {
-        census.chunk_sum[chunk] = csum[0] + csum[1] + csum[2] + csum[3];
-        census.chunk_or[chunk] = cor[0] | cor[1] | cor[2] | cor[3];
-        census.chunk_and[chunk] = ~(cnand[0] | cnand[1] | cnand[2] | cnand[3]);
+        const KeyCensus all = KeyCensus::gather<4>(csum, cor, cand);
+        census.chunk_sum[chunk] = all.tiles;
+        census.chunk_or[chunk] = all.kor;
+        census.chunk_and[chunk] = all.kand;
     }
 }
 
@@ -354,38 +536,22 @@ __device__ __forceinline__ void publish_census(const DepthCensus &census, int ch
 {
     __shared__ unsigned long long psum[4];
     __shared__ uint32_t por[4], pand[4];
-    unsigned long long sum = 0;
-    uint32_t o = 0u, a = 0xFFFFFFFFu;
-    for (int c = t; c < chunks; c += 256)
-    {
-        sum += census.chunk_sum[c];
-        o |= census.chunk_or[c];
-        a &= census.chunk_and[c];
-    }
-    for (int d = 32; d > 0; d >>= 1)
-    {
-        sum += __shfl_xor(sum, d);
-        o |= __shfl_xor(o, d);
-        a &= __shfl_xor(a, d);
-    }
-    if ((t & 63) == 0) { psum[t >> 6] = sum; por[t >> 6] = o; pand[t >> 6] = a; }
+    KeyCensus all;
+    for (int c = t; c < chunks; c += 256) all.combine(census.chunk_sum[c], census.chunk_or[c], census.chunk_and[c]);
+    all.wave_fold();
+    all.park(psum, por, pand);
     __syncthreads();
     if (t == 0)
     {
-        const unsigned long long N = psum[0] + psum[1] + psum[2] + psum[3];
-        const uint32_t varying = ((por[0] | por[1] | por[2] | por[3]) ^ (pand[0] & pand[1] & pand[2] & pand[3])) | census.force_varying;
-        *census.n_out = N;
-        *census.top_const = (varying >> 24) == 0u ? 1u : 0u; // no visible triangle at all: or = 0, and = ~0 -> varying = ~0 -> not set
-        // pinned, device-visible host word: the host reads it after the event recorded behind this kernel (no copy kernel in between)
-        if (census.host_out) __hip_atomic_store(census.host_out, N, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        all = KeyCensus::gather<4>(psum, por, pand);
+        publish_instance_count(all.tiles, census.n_out, census.top_const, all.top_byte_constant(census.force_varying), census.host_out);
     }
 }
 
 // One workgroup = one chunk of CH pairs; wave w owns the w-th quarter (KB steps of 64 consecutive pairs, held in registers).
-//   1. wave-local stable ranks: per step the lanes holding equal digits find each other with `nbits` ballots (wave64 match),
-//      rank = v_mbcnt of the match mask on top of the digit's running count in the wave's LDS counters;
-//   2. thread d turns the four waves' counts of digit d into the chunk-local start of every (wave, digit) run (wave64 DPP scan
-//      + the three other waves' totals) and the distance from the chunk-local order to the digit's global run;
+//   1. wave-local stable ranks, step by step (wave_match_rank);
+//   2. thread d turns the four waves' counts of digit d into the chunk-local start of every (wave, digit) run (digit_run_starts) and the
+//      distance from the chunk-local order to the digit's global run;
 //   3. every pair is parked in LDS at its chunk-local sorted position, and the chunk leaves in that order: consecutive threads
 //      write consecutive addresses inside each digit's run (scattering straight from registers costs a 32-64 B fabric write
 //      per 4-byte store on this chip: measured 2x slower than rocPRIM; staged, the stores are coalesced runs).
@@ -434,113 +600,26 @@ __device__ __forceinline__ void rs_scatter_body(const uint32_t *__restrict__ kin
             if (!TWO_PHASE) val[b] = IDENTITY_VALUES ? (uint32_t)(base + i) : vin_w[i];
         }
     }
-    // DIRECT: how many pairs of each digit sit in earlier chunks of this slab, in earlier slabs, and in all slabs.  Wave w takes every
-    // fourth row, lane l the digits 4l .. 4l + 3 (one dwordx4 per row: at most 16 + 12 loads per lane, all requested here, behind the keys);
-    // the four waves' partial sums meet in LDS after the ranking (the staging arrays are still free then).
-    uint4 p_within = make_uint4(0u, 0u, 0u, 0u), p_before = p_within, p_total = p_within;
-    if (DIRECT)
-    {
-        const int slab = chunk >> 6, c0 = slab * 64;
-        const uint4 *tab4 = (const uint4 *)r.table + (size_t)c0 * (NB / 4) + lane;
-        const uint4 *acc4 = (const uint4 *)acc + lane;
-#pragma unroll 4
-        for (int k = 0; k < 16; k++)
-        {
-            const int c = wave + 4 * k;
-            if (c0 + c < chunk)
-            {
-                const uint4 v = tab4[(size_t)c * (NB / 4)];
-                p_within.x += v.x; p_within.y += v.y; p_within.z += v.z; p_within.w += v.w;
-            }
-        }
-#pragma unroll 4
-        for (int k = 0; k < TS_DIRECT_MAX_SLABS / 4; k++)
-        {
-            const int sl = wave + 4 * k;
-            if (sl < r.slabs)
-            {
-                const uint4 v = acc4[(size_t)sl * (NB / 4)];
-                p_total.x += v.x; p_total.y += v.y; p_total.z += v.z; p_total.w += v.w;
-                if (sl < slab) { p_before.x += v.x; p_before.y += v.y; p_before.z += v.z; p_before.w += v.w; }
-            }
-        }
-    }
+    // DIRECT: the loads of the prefixes are requested here, behind the keys; the four waves' partial sums meet in LDS after the ranking (the
+    // staging arrays are still free then)
+    DirectPrefix prefix;
+    if (DIRECT) prefix.load(r, acc, chunk, wave, lane);
 #pragma unroll
     for (int k = 0; k < NB / 64; k++) wcnt[wave][lane + 64 * k] = 0u;
     wave_lds_order();
     uint32_t *cnt = wcnt[wave];
 #pragma unroll
-    for (int b = 0; b < KB; b++)
-    {
-        const bool valid = 64 * b + lane < mine;
-        const uint32_t d = (key[b] >> shift) & mask;
-        // lanes whose digit differs from mine in some bit: (ballot of bit i) xor (my bit i, sign-extended), or-ed over the bits, in two 32-bit
-        // halves -- three instructions per bit and half (round 5; the select form `m &= one ? bb : ~bb` compiled to ~100 instructions per step,
-        // and a launch of a few resident workgroups per SIMD spends a good part of its time issuing exactly these)
-        const unsigned long long vm = ballot64(valid);
-        uint32_t mis_lo = ~(uint32_t)vm, mis_hi = ~(uint32_t)(vm >> 32);
-        // all eight bits, unrolled, whatever `nbits` is (the digit's bits above it are zero in every lane and cost a ballot that changes nothing): with
-        // the bit index a compile-time constant a bit is four instructions (v_bfe_i32, the compare behind the ballot, two fused xor-or); as a loop
-        // over the run-time `nbits` it was twelve (shift by an SGPR, select, loop control, two s_nop) -- 96 of the ~135 instructions of a 64-pair
-        // step, in kernels whose time IS this ranking (round 6: profiles/r06_rank_unroll.txt)
-#pragma unroll
-        for (int bit = 0; bit < 8; bit++)
-        {
-            const unsigned long long bb = ballot64((d >> bit) & 1u);
-            const uint32_t e = (uint32_t)__builtin_amdgcn_sbfe((int)d, bit, 1); // all ones when my bit is set
-            mis_lo |= (uint32_t)bb ^ e;
-            mis_hi |= (uint32_t)(bb >> 32) ^ e;
-        }
-        const uint32_t m_lo = ~mis_lo, m_hi = ~mis_hi; // the valid lanes that hold my digit
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi(m_hi, __builtin_amdgcn_mbcnt_lo(m_lo, 0u));
-        const uint32_t c = (uint32_t)(__popc(m_lo) + __popc(m_hi));
-        uint32_t seen = 0;
-        if (valid) seen = cnt[d];
-        wave_lds_order(); // every lane has read its digit's count before the group leaders advance it
-        if (valid && rank == c - 1u) cnt[d] = seen + c;
-        wave_lds_order();
-        rk[b] = seen + rank;
-    }
-    if (DIRECT)
-    {
-        *(uint4 *)(stage_k + wave * NB + 4 * lane) = p_within;
-        *(uint4 *)(stage_k + (4 + wave) * NB + 4 * lane) = p_before;
-        *(uint4 *)(xtotal + wave * NB + 4 * lane) = p_total;
-    }
+    for (int b = 0; b < KB; b++) rk[b] = wave_match_rank((key[b] >> shift) & mask, 64 * b + lane < mine, cnt);
+    if (DIRECT) prefix.park(stage_k, xtotal, wave, lane);
     __syncthreads();
     {
         // thread t = digit t
-        uint32_t d_within = 0u, d_before = 0u, d_total = 0u;
-        if (DIRECT)
-        {
-#pragma unroll
-            for (int w = 0; w < 4; w++)
-            {
-                d_within += stage_k[w * NB + t];
-                d_before += stage_k[(4 + w) * NB + t];
-                d_total += xtotal[w * NB + t];
-            }
-        }
-        const uint32_t c0 = wcnt[0][t], c1 = wcnt[1][t], c2 = wcnt[2][t], c3 = wcnt[3][t];
-        const uint32_t tot = c0 + c1 + c2 + c3;
-        const uint32_t inc = wave_inclusive_scan(tot, lane);
-        if (lane == 63) wtot[wave] = inc;
-        __syncthreads();
-        uint32_t dbase = inc - tot;
-        for (int w = 0; w < wave; w++) dbase += wtot[w];
-        wcnt[0][t] = dbase; wcnt[1][t] = dbase + c0; wcnt[2][t] = dbase + c0 + c1; wcnt[3][t] = dbase + c0 + c1 + c2;
-        uint32_t g;
-        if (DIRECT)
-        {
-            // exclusive prefix of the digit totals over the digits, the same way as the chunk-local one above
-            const uint32_t ginc = wave_inclusive_scan(d_total, lane);
-            if (lane == 63) gtot[wave] = ginc;
-            __syncthreads();
-            uint32_t gbase = ginc - d_total;
-            for (int w = 0; w < wave; w++) gbase += gtot[w];
-            g = gbase + d_before + d_within;
-        }
-        else g = r.binbase[t] + r.slabtot[(size_t)(chunk >> 6) * NB + t] + r.table[(size_t)chunk * NB + t];
+        uint32_t d_earlier = 0u, d_total = 0u, tot;
+        if (DIRECT) DirectPrefix::fold(stage_k, xtotal, t, d_earlier, d_total);
+        const uint32_t dbase = digit_run_starts<4>(wcnt, wtot, wave, lane, tot);
+        // global run start of the digit: the exclusive prefix of the digit totals over the digits + what earlier chunks hold of it
+        const uint32_t g = DIRECT ? digit_exclusive_prefix<4>(d_total, gtot, wave, lane) + d_earlier
+                                  : r.binbase[t] + r.slabtot[(size_t)(chunk >> 6) * NB + t] + r.table[(size_t)chunk * NB + t];
         gdelta[t] = (int32_t)(g - dbase);
     }
     __syncthreads();
@@ -983,9 +1062,9 @@ __global__ void zero_words_kernel(uint32_t *p, size_t n) // 64-bit count and ind
 // Up to TS_DEPTH_SMALL_MAX triangles the eight launches of the depth sort and the launch of the block sums order a few thousand keys in 4-9 us
 // each -- dependent launches, each one a load -> LDS -> barrier -> store chain with a handful of workgroups on the chip (BASELINE configs[0],
 // 10 k triangles: 47 + 7 of the step's 166 us).  Here ONE workgroup of 16 waves keeps the (key, id) pairs in registers (wave w: a contiguous
-// range of `per` <= 1024 positions, 64 consecutive pairs per step), ranks them with the same wave-local match as rs_scatter_body, exchanges
-// them through LDS after every pass, and then does what the census, publish_census and gather_blocksum_kernel do: N to the device word and
-// the pinned host word, tiles_sorted, the raw block sums.  Same passes (the fourth skipped under the same condition), same stable order,
+// range of `per` <= 1024 positions, 64 consecutive pairs per step), ranks them pass by pass (lsd_rank_pass), exchanges them through LDS after
+// every pass, and then does what the census, publish_census and gather_blocksum_kernel do: N to the device word and the pinned host word,
+// tiles_sorted, the raw block sums.  Same passes (the fourth skipped under the same condition), same stable order,
 // so sv[1] holds exactly the ids the multi-launch path leaves in sorted_ids(); top_const stays 0 (the order is always in sk[1] / sv[1]).
 constexpr int TS_DEPTH_SMALL_MAX = 12288; // the kernel's capacity (level with the LSD passes of 1024-pair chunks at ~12 k triangles: 34 us either way); used up to TS_DEPTH_SMALL_USE
 constexpr int DS_WAVES = 16, DS_KB = TS_DEPTH_SMALL_MAX / (64 * DS_WAVES);
@@ -1002,15 +1081,14 @@ __global__ void __launch_bounds__(64 * DS_WAVES) depth_order_small_kernel(int P,
     __shared__ uint32_t wcnt[DS_WAVES][NB]; // per-wave digit counts, then the start of the (wave, digit) run
     __shared__ uint32_t wtot[4];
     __shared__ unsigned long long csum[DS_WAVES], bsum[TS_DEPTH_SMALL_MAX / SB];
-    __shared__ uint32_t cor[DS_WAVES], cnand[DS_WAVES];
+    __shared__ uint32_t cor[DS_WAVES], cand[DS_WAVES];
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
     const int per = ((P + 64 * DS_WAVES - 1) / (64 * DS_WAVES)) * 64; // positions per wave
     const int base = wave * per;
     const int mine = P - base < per ? (P - base > 0 ? P - base : 0) : per;
     const uint32_t *keys = (const uint32_t *)g.depth;
     uint32_t key[DS_KB], val[DS_KB], rk[DS_KB];
-    unsigned long long tsum = 0;
-    uint32_t kor = 0u, knand = 0u;
+    KeyCensus census;
     if (t < TS_DEPTH_SMALL_MAX / SB) bsum[t] = 0ull;
 #pragma unroll
     for (int b = 0; b < DS_KB; b++) // branch-free: the register arrays stay scalars the compiler can place one by one
@@ -1021,88 +1099,22 @@ __global__ void __launch_bounds__(64 * DS_WAVES) depth_order_small_kernel(int P,
         const uint32_t k = keys[src], tt = g.tiles_touched[src];
         key[b] = in ? k : 0xFFFFFFFFu;
         val[b] = (uint32_t)src;
-        tsum += in ? tt : 0u;
-        const bool vis = in && k != 0u; // culled triangles (key 0) do not count: rs_hist_census_direct_kernel
-        kor |= vis ? k : 0u;
-        knand |= vis ? ~k : 0u;
+        census.add(in ? k : 0u, in ? tt : 0u);
     }
-    for (int o = 32; o > 0; o >>= 1)
-    {
-        tsum += __shfl_xor(tsum, o);
-        kor |= __shfl_xor(kor, o);
-        knand |= __shfl_xor(knand, o);
-    }
-    if (lane == 0) { csum[wave] = tsum; cor[wave] = kor; cnand[wave] = knand; }
+    census.wave_fold();
+    census.park(csum, cor, cand);
     __syncthreads();
-    unsigned long long N = 0;
-    uint32_t o_all = 0u, n_all = 0u;
-#pragma unroll
-    for (int w = 0; w < DS_WAVES; w++) { N += csum[w]; o_all |= cor[w]; n_all |= cnand[w]; }
-    const uint32_t varying = o_all ^ ~n_all;             // publish_census: or ^ and, and = ~(or of the complements)
-    const int passes = (varying >> 24) == 0u ? 3 : 4;    // no visible triangle: or = 0, and = ~0 -> four passes, like the flag there
-    uint32_t *cnt = wcnt[wave];
+    census = KeyCensus::gather<DS_WAVES>(csum, cor, cand);
+    const unsigned long long N = census.tiles;
+    const int passes = census.top_byte_constant() ? 3 : 4; // the passes of the multi-launch forms, the fourth under the same condition
 #pragma nounroll
     for (int pass = 0; pass < passes; pass++)
     {
-        const int shift = 8 * pass;
-#pragma unroll
-        for (int k = 0; k < NB / 64; k++) cnt[lane + 64 * k] = 0u;
-        wave_lds_order();
+        uint32_t unused;
+        lsd_rank_pass<DS_KB, DS_WAVES>(key, rk, 8 * pass, per, mine, wcnt, wtot, unused);
 #pragma unroll
         for (int b = 0; b < DS_KB; b++)
-        {
-            if (64 * b >= per) continue; // wave-uniform
-            const bool valid = 64 * b + lane < mine;
-            const uint32_t d = (key[b] >> shift) & 0xFFu;
-            // lanes whose digit differs from mine in some bit: (ballot of bit i) xor (my bit i, sign-extended), or-ed over the bits -- two
-            // 32-bit halves, three instructions per bit and half (the select form of rs_scatter_body costs ~100 instructions per step; this
-            // kernel runs on ONE compute unit and is bound by exactly these)
-            const unsigned long long vm = ballot64(valid);
-            uint32_t mis_lo = ~(uint32_t)vm, mis_hi = ~(uint32_t)(vm >> 32);
-#pragma unroll
-            for (int bit = 0; bit < 8; bit++)
-            {
-                const unsigned long long bb = ballot64((d >> bit) & 1u);
-                const uint32_t e = (uint32_t)__builtin_amdgcn_sbfe((int)d, bit, 1); // all ones when my bit is set
-                mis_lo |= (uint32_t)bb ^ e;
-                mis_hi |= (uint32_t)(bb >> 32) ^ e;
-            }
-            const uint32_t m_lo = ~mis_lo, m_hi = ~mis_hi; // valid lanes with my digit
-            const uint32_t rank = __builtin_amdgcn_mbcnt_hi(m_hi, __builtin_amdgcn_mbcnt_lo(m_lo, 0u));
-            const uint32_t c = (uint32_t)(__popc(m_lo) + __popc(m_hi));
-            uint32_t seen = 0;
-            if (valid) seen = cnt[d];
-            wave_lds_order(); // every lane has read its digit's count before the group leaders advance it
-            if (valid && rank == c - 1u) cnt[d] = seen + c;
-            wave_lds_order();
-            rk[b] = seen + rank;
-        }
-        __syncthreads();
-        uint32_t c[DS_WAVES], tot = 0u, inc = 0u;
-        if (t < NB) // thread d = digit d
-        {
-#pragma unroll
-            for (int w = 0; w < DS_WAVES; w++) { c[w] = wcnt[w][t]; tot += c[w]; }
-            inc = wave_inclusive_scan(tot, lane);
-            if (lane == 63) wtot[wave] = inc;
-        }
-        __syncthreads();
-        if (t < NB)
-        {
-            uint32_t run = inc - tot;
-            for (int w = 0; w < wave; w++) run += wtot[w];
-#pragma unroll
-            for (int w = 0; w < DS_WAVES; w++) { wcnt[w][t] = run; run += c[w]; }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int b = 0; b < DS_KB; b++)
-            if (64 * b + lane < mine)
-            {
-                const uint32_t p = cnt[(key[b] >> shift) & 0xFFu] + rk[b];
-                stage_k[p] = key[b];
-                stage_v[p] = val[b];
-            }
+            if (64 * b + lane < mine) { stage_k[rk[b]] = key[b]; stage_v[rk[b]] = val[b]; }
         __syncthreads();
 #pragma unroll
         for (int b = 0; b < DS_KB; b++) // (positions past `mine` hold stale pairs that nothing uses)
@@ -1126,18 +1138,13 @@ __global__ void __launch_bounds__(64 * DS_WAVES) depth_order_small_kernel(int P,
             g.tiles_sorted[i] = tt;
             tiles = tt;
         }
-        for (int o = 32; o > 0; o >>= 1) tiles += __shfl_xor(tiles, o);
+        tiles = wave_sum64(tiles);
         if (lane == 0 && tiles) atomicAdd(&bsum[(base + 64 * b) / SB], tiles);
     }
     __syncthreads();
     const int nblocks = (P + SB - 1) / SB;
     if (t < nblocks) g.blocksum[t] = bsum[t];
-    if (t == 0)
-    {
-        g.blocksum[nblocks] = N; // = DepthCensus::n_out
-        *g.top_const = 0u;
-        if (host_out) __hip_atomic_store(host_out, N, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    if (t == 0) publish_instance_count(N, (unsigned long long *)g.blocksum + nblocks, g.top_const, false, host_out); // (= DepthCensus::n_out)
 }
 
 // ---- mid-sized scenes: the depth order by SAMPLED SPLITTERS + per-bucket sorts in LDS (round 6) -------------------------------------------------
@@ -1151,11 +1158,11 @@ __global__ void __launch_bounds__(64 * DS_WAVES) depth_order_small_kernel(int P,
 //                                   would put most of the scene into a few of them.)
 //   K1  depth_split_hist_kernel     bucket(key) = number of splitters below the key (8-step search in LDS) -> a byte per key, the chunk's bucket
 //                                   counts (table + per-slab totals, like rs_hist_direct_kernel), the chunk's part of N
-//   K2  depth_split_scatter_kernel  the stable scatter of rs_scatter_body<IDENTITY, DIRECT> on those bytes: (key, id) pairs bucket by bucket in
-//                                   sk[0] / sv[0]; chunk 0 leaves the 256 bucket starts and publishes N (device word + pinned host word)
+//   K2  depth_split_scatter_kernel  a stable ticket-free scatter like rs_scatter_body's, with those bytes as the digit: (key, id) pairs bucket by
+//                                   bucket in sk[0] / sv[0]; chunk 0 leaves the 256 bucket starts and publishes N (device word + pinned host word)
 //   K3  depth_bucket_sort_kernel    one workgroup per bucket (4 waves below 300 k triangles, 16 above): its pairs in registers, a stable LSD sort in
-//                                   LDS on the bits of (key - smallest visible key of the bucket) that vary inside the bucket (13 of them = two
-//                                   passes, 8 + 5 ballots, where the full key needs three or four of 8), then what gather_blocksum_kernel did:
+//                                   LDS (lsd_rank_pass) on the bits of (key - smallest visible key of the bucket) that vary inside the bucket (13 of
+//                                   them = two passes where the full key needs three or four), then what gather_blocksum_kernel did:
 //                                   tiles_sorted and the raw block sums (64-bit atomics; the sums were cleared by K0).
 // bucket() is monotone in the key and K2 is stable, K3 is a stable sort by the full key inside a bucket: sk[1] / sv[1] hold exactly the (key, id)
 // order of the LSD passes -- checked form against form in tests/test_parity_gpu.py::test_split_depth_order_equals_the_multi_launch_forms.  A bucket
@@ -1302,7 +1309,7 @@ __global__ void __launch_bounds__(256) depth_split_hist_kernel(int64_t n, Geomet
     if (t == 0) ds.chunk_sum[chunk] = csum[0] + csum[1] + csum[2] + csum[3];
 }
 
-// rs_scatter_body<IDENTITY_VALUES, CH, DIRECT> with the digit read from K1's byte array (and parked in LDS beside the pair, for the way out)
+// The digit is K1's byte (parked in LDS beside the pair, for the way out); the values are the ids
 template <int CH>
 __global__ void __launch_bounds__(256) depth_split_scatter_kernel(int64_t n, GeometryStateView g, RadixScratchView r, const uint32_t *__restrict__ acc, DepthSplit ds,
                                                                    unsigned long long *host_out)
@@ -1330,86 +1337,21 @@ __global__ void __launch_bounds__(256) depth_split_scatter_kernel(int64_t n, Geo
         dg[b] = 0u;
         if (i < mine) { key[b] = kin[base + i]; dg[b] = ds.digit[base + i]; }
     }
-    uint4 p_within = make_uint4(0u, 0u, 0u, 0u), p_before = p_within, p_total = p_within;
-    {
-        const int slab = chunk >> 6, c0 = slab * 64;
-        const uint4 *tab4 = (const uint4 *)r.table + (size_t)c0 * (NB / 4) + lane;
-        const uint4 *acc4 = (const uint4 *)acc + lane;
-#pragma unroll 4
-        for (int k = 0; k < 16; k++)
-        {
-            const int c = wave + 4 * k;
-            if (c0 + c < chunk)
-            {
-                const uint4 v = tab4[(size_t)c * (NB / 4)];
-                p_within.x += v.x; p_within.y += v.y; p_within.z += v.z; p_within.w += v.w;
-            }
-        }
-#pragma unroll 4
-        for (int k = 0; k < TS_DIRECT_MAX_SLABS / 4; k++)
-        {
-            const int sl = wave + 4 * k;
-            if (sl < r.slabs)
-            {
-                const uint4 v = acc4[(size_t)sl * (NB / 4)];
-                p_total.x += v.x; p_total.y += v.y; p_total.z += v.z; p_total.w += v.w;
-                if (sl < slab) { p_before.x += v.x; p_before.y += v.y; p_before.z += v.z; p_before.w += v.w; }
-            }
-        }
-    }
+    DirectPrefix prefix;
+    prefix.load(r, acc, chunk, wave, lane);
 #pragma unroll
     for (int k = 0; k < NB / 64; k++) wcnt[wave][lane + 64 * k] = 0u;
     wave_lds_order();
-    uint32_t *cnt = wcnt[wave];
 #pragma unroll
-    for (int b = 0; b < KB; b++)
-    {
-        const bool valid = 64 * b + lane < mine;
-        const uint32_t d = dg[b];
-        const unsigned long long vm = ballot64(valid);
-        uint32_t mis_lo = ~(uint32_t)vm, mis_hi = ~(uint32_t)(vm >> 32);
-#pragma unroll
-        for (int bit = 0; bit < 8; bit++)
-        {
-            const unsigned long long bb = ballot64((d >> bit) & 1u);
-            const uint32_t e = (uint32_t)__builtin_amdgcn_sbfe((int)d, bit, 1);
-            mis_lo |= (uint32_t)bb ^ e;
-            mis_hi |= (uint32_t)(bb >> 32) ^ e;
-        }
-        const uint32_t m_lo = ~mis_lo, m_hi = ~mis_hi;
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi(m_hi, __builtin_amdgcn_mbcnt_lo(m_lo, 0u));
-        const uint32_t c = (uint32_t)(__popc(m_lo) + __popc(m_hi));
-        uint32_t seen = 0;
-        if (valid) seen = cnt[d];
-        wave_lds_order();
-        if (valid && rank == c - 1u) cnt[d] = seen + c;
-        wave_lds_order();
-        rk[b] = seen + rank;
-    }
-    *(uint4 *)(stage_k + wave * NB + 4 * lane) = p_within;
-    *(uint4 *)(stage_k + (4 + wave) * NB + 4 * lane) = p_before;
-    *(uint4 *)(stage_v + wave * NB + 4 * lane) = p_total;
+    for (int b = 0; b < KB; b++) rk[b] = wave_match_rank(dg[b], 64 * b + lane < mine, wcnt[wave]);
+    prefix.park(stage_k, stage_v, wave, lane);
     __syncthreads();
     {
-        uint32_t d_within = 0u, d_before = 0u, d_total = 0u; // thread t = bucket t
-#pragma unroll
-        for (int w = 0; w < 4; w++)
-        {
-            d_within += stage_k[w * NB + t];
-            d_before += stage_k[(4 + w) * NB + t];
-            d_total += stage_v[w * NB + t];
-        }
-        const uint32_t c0 = wcnt[0][t], c1 = wcnt[1][t], c2 = wcnt[2][t], c3 = wcnt[3][t];
-        const uint32_t tot = c0 + c1 + c2 + c3;
-        const uint32_t inc = wave_inclusive_scan(tot, lane);
-        if (lane == 63) wtot[wave] = inc;
-        const uint32_t ginc = wave_inclusive_scan(d_total, lane);
-        if (lane == 63) gtot[wave] = ginc;
-        __syncthreads();
-        uint32_t dbase = inc - tot, gbase = ginc - d_total;
-        for (int w = 0; w < wave; w++) { dbase += wtot[w]; gbase += gtot[w]; }
-        wcnt[0][t] = dbase; wcnt[1][t] = dbase + c0; wcnt[2][t] = dbase + c0 + c1; wcnt[3][t] = dbase + c0 + c1 + c2;
-        gdelta[t] = (int32_t)(gbase + d_before + d_within - dbase);
+        uint32_t d_earlier, d_total, tot; // thread t = bucket t
+        DirectPrefix::fold(stage_k, stage_v, t, d_earlier, d_total);
+        const uint32_t dbase = digit_run_starts<4>(wcnt, wtot, wave, lane, tot);
+        const uint32_t gbase = digit_exclusive_prefix<4>(d_total, gtot, wave, lane);
+        gdelta[t] = (int32_t)(gbase + d_earlier - dbase);
         if (chunk == 0) ds.bucket_start[t] = gbase; // where bucket t begins in sk[0] / sv[0]
     }
     __syncthreads();
@@ -1431,84 +1373,17 @@ __global__ void __launch_bounds__(256) depth_split_scatter_kernel(int64_t n, Geo
         g.sk[0][dst] = stage_k[p];
         g.sv[0][dst] = stage_v[p];
     }
-    if (chunk == 0) // N = the chunks' sums of K1: to the device word the scan reads and to the pinned host word (publish_census of the LSD form)
+    if (chunk == 0) // N = the chunks' sums of K1 (what publish_census does in the LSD form); the order is always in sk[1] / sv[1]: top_const = 0
     {
         __shared__ unsigned long long psum[4];
         unsigned long long sum = 0;
         for (int c = t; c < r.chunks; c += 256) sum += ds.chunk_sum[c];
-        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+        sum = wave_sum64(sum);
         if (lane == 0) psum[wave] = sum;
         __syncthreads();
-        if (t == 0)
-        {
-            const unsigned long long N = psum[0] + psum[1] + psum[2] + psum[3];
-            g.blocksum[((int)n + SB - 1) / SB] = N; // behind the block sums K3 adds up (= DepthCensus::n_out)
-            *g.top_const = 0u;                      // the order is always in sk[1] / sv[1]
-            if (host_out) __hip_atomic_store(host_out, N, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
+        // behind the block sums K3 adds up (= DepthCensus::n_out)
+        if (t == 0) publish_instance_count(psum[0] + psum[1] + psum[2] + psum[3], (unsigned long long *)g.blocksum + ((int)n + SB - 1) / SB, g.top_const, false, host_out);
     }
-}
-
-// One stable LSD pass of a 16-wave workgroup over the `mine` pairs each wave holds in registers (wave w: positions [w per, w per + mine) of the
-// tile, 64 consecutive ones per step), on digit (key - kmin) >> shift: the ranking of depth_order_small_kernel.  Leaves, for every pair, its
-// position among the tile's pairs in (digit, wave, step, lane) order in rk[], and the tile's digit counts in tile_cnt (thread d < 256: digit d).
-template <int KBX, int W>
-__device__ __forceinline__ void bucket_rank_pass(const uint32_t (&key)[KBX], uint32_t (&rk)[KBX], uint32_t kmin, int shift, int nbits, int per, int mine,
-                                                 uint32_t (*wcnt)[NB], uint32_t *wtot, uint32_t &tile_cnt)
-{
-    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
-    uint32_t *cnt = wcnt[wave];
-#pragma unroll
-    for (int k = 0; k < NB / 64; k++) cnt[lane + 64 * k] = 0u;
-    wave_lds_order();
-#pragma unroll
-    for (int b = 0; b < KBX; b++)
-    {
-        if (64 * b >= per) continue; // wave-uniform
-        const bool valid = 64 * b + lane < mine;
-        const uint32_t d = ((key[b] - kmin) >> shift) & 0xFFu;
-        const unsigned long long vm = ballot64(valid);
-        uint32_t mis_lo = ~(uint32_t)vm, mis_hi = ~(uint32_t)(vm >> 32);
-#pragma unroll
-        for (int bit = 0; bit < 8; bit++) // unrolled over all eight bits (see rs_scatter_body); `nbits` is not needed
-        {
-            const unsigned long long bb = ballot64((d >> bit) & 1u);
-            const uint32_t e = (uint32_t)__builtin_amdgcn_sbfe((int)d, bit, 1);
-            mis_lo |= (uint32_t)bb ^ e;
-            mis_hi |= (uint32_t)(bb >> 32) ^ e;
-        }
-        const uint32_t m_lo = ~mis_lo, m_hi = ~mis_hi;
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi(m_hi, __builtin_amdgcn_mbcnt_lo(m_lo, 0u));
-        const uint32_t c = (uint32_t)(__popc(m_lo) + __popc(m_hi));
-        uint32_t seen = 0;
-        if (valid) seen = cnt[d];
-        wave_lds_order();
-        if (valid && rank == c - 1u) cnt[d] = seen + c;
-        wave_lds_order();
-        rk[b] = seen + rank;
-    }
-    __syncthreads();
-    uint32_t c[W], tot = 0u, inc = 0u;
-    if (t < NB) // thread d = digit d
-    {
-#pragma unroll
-        for (int w = 0; w < W; w++) { c[w] = wcnt[w][t]; tot += c[w]; }
-        inc = wave_inclusive_scan(tot, lane);
-        if (lane == 63) wtot[wave] = inc;
-    }
-    __syncthreads();
-    if (t < NB)
-    {
-        uint32_t run = inc - tot;
-        for (int w = 0; w < wave; w++) run += wtot[w];
-#pragma unroll
-        for (int w = 0; w < W; w++) { wcnt[w][t] = run; run += c[w]; }
-    }
-    tile_cnt = tot;
-    __syncthreads();
-#pragma unroll
-    for (int b = 0; b < KBX; b++)
-        if (64 * b + lane < mine) rk[b] += cnt[((key[b] - kmin) >> shift) & 0xFFu];
 }
 
 // What gather_blocksum_kernel does, for 64 consecutive depth-order positions (first one `pos0`, this lane's `pos`): the tile counts in depth order
@@ -1591,7 +1466,7 @@ __global__ void __launch_bounds__(64 * W) depth_bucket_sort_kernel(int P, Geomet
             kmin = min(kmin, k ? k : 0xFFFFFFFFu);
             kmax = max(kmax, k);
         }
-    for (int o = 32; o > 0; o >>= 1) { kmin = min(kmin, (uint32_t)__shfl_xor((int)kmin, o)); kmax = max(kmax, (uint32_t)__shfl_xor((int)kmax, o)); }
+    wave_min_max(kmin, kmax);
     if (lane == 0) { rmin[wave] = kmin; rmax[wave] = kmax; }
     __syncthreads();
 #pragma unroll
@@ -1611,7 +1486,7 @@ __global__ void __launch_bounds__(64 * W) depth_bucket_sort_kernel(int P, Geomet
         for (int pass = 0; pass < passes; pass++)
         {
             uint32_t unused;
-            bucket_rank_pass<DB_KB, W>(key, rk, 0u, 8 * pass, min(8, kbits - 8 * pass), per, mine, wcnt, wtot, unused);
+            lsd_rank_pass<DB_KB, W>(key, rk, 8 * pass, per, mine, wcnt, wtot, unused);
 #pragma unroll
             for (int b = 0; b < DB_KB; b++)
                 if (64 * b + lane < mine) { stage_k[rk[b]] = key[b]; stage_v[rk[b]] = val[b]; }
@@ -1664,15 +1539,8 @@ __global__ void __launch_bounds__(64 * W) depth_bucket_sort_kernel(int P, Geomet
             for (int i = t; i < n; i += 64 * DB_WAVES) atomicAdd(&dstart[(depth_key_adjust(peer_load(kin + i), kmin) >> (8 * pass)) & 0xFFu], 1u);
             __syncthreads();
             {
-                uint32_t tot = 0u, inc = 0u;
-                if (t < NB) { tot = dstart[t]; inc = wave_inclusive_scan(tot, lane); if (lane == 63) wtot[wave] = inc; }
-                __syncthreads();
-                if (t < NB)
-                {
-                    uint32_t run = inc - tot;
-                    for (int w = 0; w < wave; w++) run += wtot[w];
-                    dstart[t] = run; // where digit t begins in the bucket
-                }
+                const uint32_t start = digit_exclusive_prefix<W>(t < NB ? dstart[t] : 0u, wtot, wave, lane);
+                if (t < NB) dstart[t] = start; // where digit t begins in the bucket
                 __syncthreads();
             }
             for (int t0 = 0; t0 < n; t0 += tile)
@@ -1690,7 +1558,7 @@ __global__ void __launch_bounds__(64 * W) depth_bucket_sort_kernel(int P, Geomet
                     val[b] = in ? peer_load(vin + t0 + tbase + i) : 0u;
                 }
                 uint32_t tile_cnt;
-                bucket_rank_pass<DB_KB, W>(key, rk, 0u, 8 * pass, min(8, kbits - 8 * pass), tper, tmine, wcnt, wtot, tile_cnt);
+                lsd_rank_pass<DB_KB, W>(key, rk, 8 * pass, tper, tmine, wcnt, wtot, tile_cnt);
                 // rk = position inside the tile's (digit, order) arrangement; the digit's pairs of this tile go behind the earlier tiles' ones:
                 // global position = dstart[d] + (rk - start of d inside the tile) = dstart[d] + rk - wcnt[0][d]
 #pragma unroll
@@ -1732,23 +1600,28 @@ __global__ void __launch_bounds__(64 * W) depth_bucket_sort_kernel(int P, Geomet
 #endif
 constexpr int TS_DEPTH_SMALL_USE = TS_DEPTH_SMALL_USE_VALUE;
 static_assert(TS_DEPTH_SMALL_USE <= TS_DEPTH_SMALL_MAX && TS_DEPTH_SMALL_USE >= 2048, "the split form's scratch needs 1024 + 2 chunks words of `offsets`");
-static bool depth_small_ok(int32_t P) { return P <= TS_DEPTH_SMALL_USE && !g_force_tickets && !g_force_pass4; }
-// The sampled-splitter form: every size between the one-launch form and TS_DEPTH_SPLIT_MAX whose scratch takes the ticket-free passes; never under the
-// lab library's switches that ask for the LSD forms.
-static bool depth_split_ok(int32_t P, const RadixScratchView &r)
+// Which form orders a scene of P triangles: the one-launch form up to TS_DEPTH_SMALL_USE, the sampled-splitter form from there to TS_DEPTH_SPLIT_MAX when
+// the scratch takes the ticket-free passes, the LSD passes (ticket-free or, for the largest sorts, with tickets) beyond.  The lab library's switches
+// that ask for the LSD forms (forced tickets, forced fourth pass, split mode 1) get them at every size.
+enum class DepthForm { OneLaunch, Split, LsdDirect, LsdTickets };
+static DepthForm depth_form(int32_t P, const RadixScratchView &r)
 {
-    return P > TS_DEPTH_SMALL_USE && P <= (g_depth_split_mode == 2 ? TS_DEPTH_SPLIT_HARD_MAX : TS_DEPTH_SPLIT_MAX) && g_depth_split_mode != 1 && !g_force_tickets &&
-           !g_force_pass4 && radix_direct_ok(r);
+    const bool lsd_forced = g_force_tickets || g_force_pass4;
+    if (P <= TS_DEPTH_SMALL_USE && !lsd_forced) return DepthForm::OneLaunch;
+    if (!radix_direct_ok(r)) return DepthForm::LsdTickets;
+    const bool split = P > TS_DEPTH_SMALL_USE && P <= (g_depth_split_mode == 2 ? TS_DEPTH_SPLIT_HARD_MAX : TS_DEPTH_SPLIT_MAX) && g_depth_split_mode != 1;
+    return split && !lsd_forced ? DepthForm::Split : DepthForm::LsdDirect;
 }
 void ts_sort_by_depth_begin(const GeometryStateView &g, int32_t P, unsigned long long *host_out, hipStream_t s)
 {
     if (P <= 0) return;
-    if (depth_small_ok(P))
+    const DepthForm form = depth_form(P, g.rs);
+    if (form == DepthForm::OneLaunch)
     {
         hipLaunchKernelGGL(depth_order_small_kernel, dim3(1), dim3(64 * DS_WAVES), 0, s, P, g, host_out);
         return;
     }
-    if (depth_split_ok(P, g.rs))
+    if (form == DepthForm::Split)
     {
         const DepthSplit ds = depth_split_of(g);
         const dim3 grid((unsigned)g.rs.chunks);
@@ -1768,7 +1641,7 @@ void ts_sort_by_depth_begin(const GeometryStateView &g, int32_t P, unsigned long
     c.host_out = host_out;
     c.top_const = g.top_const;
     c.force_varying = g_force_pass4 ? 0xFF000000u : 0u;
-    if (!radix_direct_ok(g.rs))
+    if (form == DepthForm::LsdTickets)
     {
         radix_hist((const uint32_t *)g.depth, P, nullptr, 0, 8, g.rs, s, &c);
         return;
@@ -1786,26 +1659,28 @@ void ts_sort_by_depth_begin(const GeometryStateView &g, int32_t P, unsigned long
 }
 void ts_sort_by_depth_finish(const GeometryStateView &g, int32_t P, hipStream_t s)
 {
-    if (P <= 0 || depth_small_ok(P)) return;
-    if (depth_split_ok(P, g.rs))
+    if (P <= 0) return;
+    switch (depth_form(P, g.rs))
     {
+    case DepthForm::OneLaunch: return;
+    case DepthForm::Split:
         if (P < DB_SMALL_BELOW)
             hipLaunchKernelGGL(depth_bucket_sort_kernel<DB_SMALL_WAVES>, dim3(NB), dim3(64 * DB_SMALL_WAVES), 0, s, P, g, depth_split_of(g),
                                min(g_depth_bucket_cap, 64 * DB_SMALL_WAVES * DB_KB));
         else hipLaunchKernelGGL(depth_bucket_sort_kernel<DB_WAVES>, dim3(NB), dim3(64 * DB_WAVES), 0, s, P, g, depth_split_of(g), g_depth_bucket_cap);
         return;
-    }
-    if (!radix_direct_ok(g.rs))
-    {
+    case DepthForm::LsdTickets:
         radix_scatter((const uint32_t *)g.depth, nullptr, g.sk[0], g.sv[0], P, nullptr, 0, 8, g.rs, s);
         radix_pass(g.sk[0], g.sv[0], g.sk[1], g.sv[1], P, nullptr, 8, 8, g.rs, s);
         radix_pass(g.sk[1], g.sv[1], g.sk[0], g.sv[0], P, nullptr, 16, 8, g.rs, s);
         radix_pass(g.sk[0], g.sv[0], g.sk[1], g.sv[1], P, nullptr, 24, 8, g.rs, s, g.top_const);
         return;
+    case DepthForm::LsdDirect:
+        radix_pass_direct(g.sk[0], g.sv[0], g.sk[1], g.sv[1], P, nullptr, 8, 8, g.rs, 1, s);
+        radix_pass_direct(g.sk[1], g.sv[1], g.sk[0], g.sv[0], P, nullptr, 16, 8, g.rs, 0, s);
+        radix_pass_direct(g.sk[0], g.sv[0], g.sk[1], g.sv[1], P, nullptr, 24, 8, g.rs, 1, s, g.top_const);
+        return;
     }
-    radix_pass_direct(g.sk[0], g.sv[0], g.sk[1], g.sv[1], P, nullptr, 8, 8, g.rs, 1, s);
-    radix_pass_direct(g.sk[1], g.sv[1], g.sk[0], g.sv[0], P, nullptr, 16, 8, g.rs, 0, s);
-    radix_pass_direct(g.sk[0], g.sv[0], g.sk[1], g.sv[1], P, nullptr, 24, 8, g.rs, 1, s, g.top_const);
 }
 
 // Step 2: tiles_sorted = tiles_touched[perm], raw block sums (+ their groups' sums above 2048 blocks, or always under the lab library's
@@ -1813,7 +1688,14 @@ void ts_sort_by_depth_finish(const GeometryStateView &g, int32_t P, hipStream_t 
 static bool scan_two_level(int32_t P) { return g_force_tickets || (P + SB - 1) / SB > 2048; }
 void ts_scan_offsets(const GeometryStateView &g, int32_t P, hipStream_t s)
 {
-    if (P <= 0 || depth_small_ok(P) || depth_split_ok(P, g.rs)) return; // depth_order_small_kernel / depth_bucket_sort_kernel left tiles_sorted and the block sums behind
+    if (P <= 0) return;
+    switch (depth_form(P, g.rs))
+    {
+    case DepthForm::OneLaunch:
+    case DepthForm::Split: return; // depth_order_small_kernel / depth_bucket_sort_kernel left tiles_sorted and the block sums behind
+    case DepthForm::LsdDirect:
+    case DepthForm::LsdTickets: break;
+    }
     hipLaunchKernelGGL(gather_blocksum_kernel, dim3((unsigned)((P + SB - 1) / SB)), dim3(256), 0, s, P, g, scan_two_level(P));
 }
 

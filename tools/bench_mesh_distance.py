@@ -1,0 +1,123 @@
+"""Times the geometric mesh scores (diff_recon_hip.mesh_distance over csrc/mesh_distance.hip) part by part, next to
+simple_knn.nearestNeighbor(points, 1) on as many points -- the search of one set against itself that shares the front half (Morton codes,
+radix sort, gathered points, 1024-point boxes; csrc/ts_knn_front.h) and the candidate loop, and so the honest yardstick for the cross search:
+
+    python tools/bench_mesh_distance.py [--points 1000000 --faces 1000000 --blocks 10 --iters 5 --warmup 3 --out profiles/mesh_distance.json]
+
+Timed with device events, in alternating blocks after a warm-up, each through its public wrapper (workspace allocation from torch's caching
+allocator included):
+
+    cross_volume     nearest_points, Q = R = --points, both sets uniform in one volume
+    cross_surface    nearest_points between two --points-sample surface sets of nearby meshes (a bumpy height field and the same field
+                     displaced by a fraction of its cell)
+    sample           sample_mesh_surface, --points samples of a height-field mesh of about --faces faces (includes the face areas and the
+                     blocking read of the total area)
+    nearest_other    simple_knn.nearestNeighbor(points, 1) on the volume's query set: the yardstick
+
+and reads each search's (workgroup, ref box) visits from the library's counter in a run of its own.  Writes, and prints as one JSON line,
+the median block time of every part with the slowest and fastest block, the visits and the ratios to the yardstick.  Needs a HIP device;
+there is no fallback."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "triangle-splatting_amd")]
+import torch
+
+
+def height_field(n, amplitude, phase, dev):
+    """(vertices, faces) of an n x n grid over the unit square, z = amplitude * sin * cos bumps: 2 (n - 1)^2 faces."""
+    g = torch.linspace(0.0, 1.0, n, device=dev)
+    x, y = torch.meshgrid(g, g, indexing="ij")
+    z = amplitude * torch.sin(12.0 * x + phase) * torch.cos(9.0 * y - phase)
+    vertices = torch.stack([x, y, z], dim=-1).reshape(-1, 3).contiguous()
+    i = (torch.arange(n - 1, device=dev)[:, None] * n + torch.arange(n - 1, device=dev)[None, :]).reshape(-1)
+    faces = torch.cat([torch.stack([i, i + n, i + n + 1], dim=1), torch.stack([i, i + n + 1, i + 1], dim=1)]).to(torch.int32).contiguous()
+    return vertices, faces
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--points", type=int, default=1_000_000)
+    ap.add_argument("--faces", type=int, default=1_000_000)
+    ap.add_argument("--blocks", type=int, default=10, help="alternating blocks per part")
+    ap.add_argument("--iters", type=int, default=5, help="calls per block")
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mesh_distance.json"))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_mesh_distance.py needs a HIP device (the mesh scores have no CPU fallback)")
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    from diff_recon_hip.mesh_distance import nearest_points, sample_mesh_surface
+    from simple_knn import nearestNeighbor
+
+    P = args.points
+    g = torch.Generator(device=dev).manual_seed(42)
+    vol_q = torch.rand((P, 3), device=dev, generator=g) * 100
+    vol_r = torch.rand((P, 3), device=dev, generator=g) * 100
+    n = int(round((args.faces / 2) ** 0.5)) + 1
+    mesh_a, mesh_b = height_field(n, 0.05, 0.0, dev), height_field(n, 0.05, 0.02, dev)
+    F = mesh_a[1].shape[0]
+    surf_q, surf_r = sample_mesh_surface(*mesh_a, P, seed=0).points, sample_mesh_surface(*mesh_b, P, seed=1).points
+
+    def block(fn, k):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(k):
+            fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b) / k
+
+    def summary(v):
+        return {"ms": round(statistics.median(v), 4), "min_block_ms": round(min(v), 4), "max_block_ms": round(max(v), 4)}
+
+    parts = {
+        "cross_volume": lambda: nearest_points(vol_q, vol_r),
+        "cross_surface": lambda: nearest_points(surf_q, surf_r),
+        "sample": lambda: sample_mesh_surface(*mesh_a, P, seed=0),
+        "nearest_other": lambda: nearestNeighbor(vol_q, 1),
+    }
+    for _ in range(args.warmup):
+        for fn in parts.values():
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in parts}
+    for _ in range(args.blocks):
+        for k, fn in parts.items():
+            times[k].append(block(fn, args.iters))
+    out = {k: summary(v) for k, v in times.items()}
+    print(", ".join(f"{k} {v['ms']:.3f} ms" for k, v in out.items()), file=sys.stderr, flush=True)
+
+    nboxes = (P + 1023) // 1024
+    for name, (q, r) in (("cross_volume", (vol_q, vol_r)), ("cross_surface", (surf_q, surf_r))):
+        visits = torch.zeros(1, device=dev, dtype=torch.int64)
+        _, d2 = nearest_points(q, r, visits)
+        torch.cuda.synchronize()
+        out[name].update({"box_visits": int(visits.item()), "box_visits_per_workgroup": round(int(visits.item()) / nboxes, 2),
+                          "distance_evaluations_upper_bound": int(visits.item()) * 1024 * 1024,
+                          "mean_distance": float(d2.to(torch.float64).sqrt().mean().item()),
+                          "over_nearest_other": round(out[name]["ms"] / out["nearest_other"]["ms"], 3)})
+    result = {
+        "workload": f"cross_volume: Q = R = {P} points uniform in a 100^3 cube; cross_surface: {P} surface samples each of two {n} x {n} height fields "
+                    f"({F} faces) a phase of 0.02 apart; sample: {P} samples of one of them; nearest_other: simple_knn.nearestNeighbor on the cube's "
+                    f"{P} queries, batch_size 1; {nboxes} boxes per set",
+        "method": f"{args.blocks} alternating blocks x {args.iters} calls of every part after {args.warmup} warm-up calls each, device events around each "
+                  "block; public wrappers (allocation of outputs and workspace included; sample also computes the face areas and reads their sum "
+                  "back); box visits from the library's counter in a call of its own",
+        "parts": out,
+        "device": torch.cuda.get_device_name(dev),
+    }
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()

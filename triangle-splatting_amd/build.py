@@ -1,9 +1,10 @@
-"""Builds libts2d.so (the C-ABI HIP library of include/ts2d.h) for gfx950 with hipcc, in-tree, and the package's binding of it.
+"""Builds libts2d.so (the C-ABI HIP library of include/ts2d.h) for gfx950 with hipcc, in-tree, the package's binding of it, and
+libts_geom.so (include/ts_geom.h: the mesh-distance library of diff_recon_hip, GEOM_SOURCES + the product's own binning object).
 
     python triangle-splatting_amd/build.py [--force] [--verbose] [--lab]
     python triangle-splatting_amd/build.py --variant TAG [--lab] [--all "FLAGS"] [--unit NAME="FLAGS" ...]
 
-Output: triangle-splatting_amd/diff_triangle_rasterization_2D/libts2d.so and the torch extension bindings/_ts2d_torch_C.so (bindings/
+Output: triangle-splatting_amd/diff_triangle_rasterization_2D/libts2d.so, triangle-splatting_amd/diff_recon_hip/libts_geom.so and the torch extension bindings/_ts2d_torch_C.so (bindings/
 ts2d_torch_ext.cpp, linked -lts2d with an $ORIGIN-relative runpath), both git-ignored.  Every library carries the soname libts2d.so, so the
 extension's dependency on libts2d.so is met by whichever of them _C.py loaded first (TS2D_LIBRARY_PATH).
 --lab builds tools/bin/libts2d_lab.so as well: the same objects + the test hooks of tools/lab/lab_hooks.hip and api.hip compiled with
@@ -74,16 +75,23 @@ LAB_SOURCES = {  # libts2d_lab.so only
     "lab_hooks.hip": [],  # sort / scan test hooks + their rocPRIM comparators (csrc/ts2d_lab.h)
     "api.hip": ["-DTS2D_LAB"],
 }
+GEOM_SOURCES = {  # libts_geom.so only (include/ts_geom.h): a second product library, because libts2d.so's export list is closed
+    "mesh_distance.hip": ["-ffp-contract=off"],  # cross-set nearest search and surface sampler: every fp32 / fp64 operation rounds
+    "api_geom.hip": [],                          # its C ABI and its own error text (api.hip is not linked)
+}
+GEOM_SHARED = ["binning"]  # the product's own objects it links as well: the radix sort of the search's front half (no undefined project symbol)
+GEOM_LIB = os.path.join(HERE, "diff_recon_hip", "libts_geom.so")
 BIN_DIR = os.path.join(os.path.dirname(HERE), "tools", "bin")
 LAB_LIB = os.path.join(BIN_DIR, "libts2d_lab.so")
 LAB_SRC = os.path.join(os.path.dirname(HERE), "tools", "lab")  # lab_hooks.hip: the test hooks, outside the product's csrc/; it includes csrc's headers (-I)
-HEADERS = ["ts2d_common.h", "ts2d_api.h", "ts_knn_front.h", "ts_weld_launch.h", "ts2d_lab.h", "ts2d_math.h", "ts2d_wave.h", "ts2d_group.h", "ts2d_support.h", "ts2d_sh.h", "ts2d_stage.h", "ts2d_preprocess_launch.h", "ts2d_imgops.h", "ts2d_select.h", "ts2d_tri.h", os.path.join("..", "..", "include", "ts2d.h"),
+HEADERS = ["ts2d_common.h", "ts2d_api.h", "ts_knn_front.h", "ts_weld_launch.h", "ts_geom_launch.h", "ts2d_lab.h", "ts2d_math.h", "ts2d_wave.h", "ts2d_group.h", "ts2d_support.h", "ts2d_sh.h", "ts2d_stage.h", "ts2d_preprocess_launch.h", "ts2d_imgops.h", "ts2d_select.h", "ts2d_tri.h", os.path.join("..", "..", "include", "ts2d.h"),
            os.path.join("..", "..", "include", "ts_loss.h"),
            os.path.join("..", "..", "include", "ts_knn.h"),
            os.path.join("..", "..", "include", "ts_model.h"),
            os.path.join("..", "..", "include", "ts_optim.h"),
            os.path.join("..", "..", "include", "ts_mesh.h"),
-           os.path.join("..", "..", "include", "ts_weld.h")]
+           os.path.join("..", "..", "include", "ts_weld.h"),
+           os.path.join("..", "..", "include", "ts_geom.h")]
 
 
 def hipcc() -> str:
@@ -154,6 +162,24 @@ def command(unit: str, extra=(), variant: str | None = None, cc: str = "hipcc") 
     return [cc, *COMMON, *flags, *extra, "-c", src, "-o", _object(unit, variant if extra else None)]
 
 
+def geom_units() -> list:
+    """The translation units of libts_geom.so that are its own (GEOM_SOURCES); it links the objects of GEOM_SHARED besides."""
+    return [_unit(k) for k in GEOM_SOURCES]
+
+
+def geom_command(unit: str, cc: str = "hipcc") -> list:
+    """The compile command of one unit of GEOM_SOURCES: COMMON + its flags, like command()."""
+    table = {_unit(k): (k, v) for k, v in GEOM_SOURCES.items()}
+    if unit not in table:
+        raise ValueError(f"unknown unit {unit!r}; the units of libts_geom.so are {', '.join(table)}")
+    key, flags = table[unit]
+    return [cc, *COMMON, *flags, "-c", os.path.join(CSRC, key), "-o", _object(unit)]
+
+
+def geom_objects() -> list:
+    return [_object(u) for u in geom_units()] + [_object(u) for u in GEOM_SHARED]
+
+
 def ext_command(cc: str = "hipcc") -> list:
     """The build command of the torch extension (the reference's ext.cpp signatures plus the package's *_ex entry points over the C ABI)."""
     import sysconfig
@@ -191,8 +217,10 @@ def build(force: bool = False, verbose: bool = False, lab: bool = False, variant
     me = os.path.abspath(__file__)
     hdr_t = max(_newest_header(), os.path.getmtime(me))
     jobs = []
-    for u in known:
-        cmd = command(u, extra.get(u, ()), variant, cc)
+    cmds = [command(u, extra.get(u, ()), variant, cc) for u in known]
+    if variant is None:  # the second product library, include/ts_geom.h
+        cmds += [geom_command(u, cc) for u in geom_units()]
+    for cmd in cmds:
         s, o = cmd[-3], cmd[-1]
         os.makedirs(os.path.dirname(o), exist_ok=True)
         key = tool + "\n" + " ".join(cmd)
@@ -223,6 +251,12 @@ def build(force: bool = False, verbose: bool = False, lab: bool = False, variant
         if force or compiled.intersection(objs) or not _fresh(lib, key, max(os.path.getmtime(o) for o in objs)):
             os.makedirs(os.path.dirname(lib), exist_ok=True)
             make(lib, cmd, key)
+    if variant is None:
+        objs = geom_objects()
+        cmd = [cc, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-Wl,-soname,libts_geom.so", "-o", GEOM_LIB, *objs]
+        key = tool + "\n" + " ".join(cmd)
+        if force or compiled.intersection(objs) or not _fresh(GEOM_LIB, key, max(os.path.getmtime(o) for o in objs)):
+            make(GEOM_LIB, cmd, key)
     if variant is None:  # the package has no other binding, so a build against another torch must not be reused: torch's version is in the key
         import torch
         cmd = ext_command(cc)

@@ -11,8 +11,9 @@
                           (reference: src/diff_recon/models/VanillaTS_model.py:194-201, 214-345, 347-537)
     schedulers.py         exponential_scheduler / step_scheduler / exponential_step_scheduler, gamma_at, sh_degree_at
                           (reference: src/diff_recon/utils/scheduler.py:5-45, VanillaTS_model.py:548-565; pinned by tests/golden/schedules.npz)
-    raw_triangle.py       RawTriangle with loadPLY / savePLY / saveGLB / loadGLB: the on-disk formats of a triangle model, numpy only
-                          (reference: src/diff_recon/models/raw_triangle.py:12-33, 124-223)
+    raw_triangle.py       RawTriangle with loadPLY / savePLY / saveGLB / loadGLB: the on-disk formats of a triangle model, numpy only, and its set
+                          operations += / -= / - / reduce / replace (the set difference by centre distance searches on the device)
+                          (reference: src/diff_recon/models/raw_triangle.py:12-223)
     optim.py              FusedAdam (the reference's torch.optim.Adam(l, lr=0.0, eps=1e-15) as ONE fused launch, same param_groups / state) and
                           ShardedAdam (reduce-scatter of the gradient bucket -> Adam on the rank's slice -> all-gather of the parameters)
                           (reference: src/diff_recon/models/VanillaTS_model.py:108-124, src/diff_recon/trainers/VanillaTS_trainer.py:119-122)
@@ -37,12 +38,17 @@
                           faces dropped; a pure function of the input) and mesh_topology (boundary / manifold / non-manifold edges, pieces, Euler
                           characteristic) -- the counterpart of saveGLB(..., process=True)
                           (reference: src/diff_recon/models/raw_triangle.py:183-207, trimesh's vertex merging)
+    mesh_distance.py      nearest_points (exact nearest neighbour between two point sets), sample_mesh_surface (deterministic area-weighted
+                          surface samples), point_cloud_distance / mesh_distance (accuracy, completeness, Chamfer, Hausdorff, precision / recall /
+                          F-score) -- the geometric scores of an exported mesh; the search stands in for scipy's KDTree in RawTriangle's `-=`
+                          (reference: src/diff_recon/models/raw_triangle.py:79-87)
     metrics.py            psnr, ssim (= 1 - SSIMLoss) and evaluate_mesh: PSNR / SSIM of a mesh's opaque render against each view's gt_image
                           (reference: src/diff_recon/trainers/trainer_utils.py:331-336, VanillaTS_trainer.py:156-190)
     graphed.py            GraphedStep: a whole training step (sync-free forward, loss, backward, optimizer) captured once into a HIP graph and
                           replayed with one launch -- no counterpart in the reference, whose forward reads num_rendered back every step
 
-Native code: libts2d.so (include/ts_loss.h, include/ts_model.h, include/ts_optim.h, include/ts2d.h, include/ts_mesh.h, include/ts_weld.h).  No CPU / eager fallback anywhere.
+Native code: libts2d.so (include/ts_loss.h, include/ts_model.h, include/ts_optim.h, include/ts2d.h, include/ts_mesh.h, include/ts_weld.h) and, for
+mesh_distance.py, libts_geom.so beside this file (include/ts_geom.h).  No CPU / eager fallback anywhere.
 """
 from .losses import L1, SSIMLoss, ssimLoss, PhotometricLoss, photometric_loss, DepthNormalLoss, DoGLoss, SmoothnessLoss, dogLoss, smoothnessLoss, downsample_bilinear, downsample_bilinear_many  # noqa: F401
 from .triangle_renderer import TriangleRenderer  # noqa: F401
@@ -60,4 +66,5 @@ from .multirank import (ImageParallelLoop, ReplicaGuard, ReplicaDivergence, stat
 from .mesh_renderer import MeshRenderer, mesh_from_triangles  # noqa: F401
 from .mesh_census import MeshCensus, bake_face_colors, visible_triangle_mask  # noqa: F401
 from .mesh_weld import WeldedMesh, weld_mesh, mesh_topology  # noqa: F401
+from .mesh_distance import SurfaceSamples, nearest_points, face_areas, sample_mesh_surface, point_cloud_distance, mesh_distance  # noqa: F401
 from .metrics import psnr, ssim, evaluate_mesh  # noqa: F401

@@ -1,6 +1,7 @@
 """On-disk formats of a triangle model ("on-disk formats come with it").
 
-Mirror of the IO half of the reference's `RawTriangle` (src/diff_recon/models/raw_triangle.py:12-33, 124-223): the same class
+Mirror of the reference's `RawTriangle` (src/diff_recon/models/raw_triangle.py:12-223: the IO half and the set operations `+=`, `-=`,
+`-`, `reduce`, `replace` over `contained_idx`, whose centre search runs on the device, diff_recon_hip.mesh_distance): the same class
 name, constructor keywords, attributes (`vertex (P, 3, 3)`, `opacity (P, 1)` = the pre-sigmoid parameter, `shs (P, 3 K)` with
 the DC triple first) and method names `loadPLY / savePLY / saveGLB / loadGLB`, so that checkpoints move between the two code
 bases.  The reference goes through `plyfile` and `trimesh`; neither is a dependency here -- both formats are written and parsed
@@ -20,6 +21,7 @@ from __future__ import annotations
 import json
 import os
 import struct
+from copy import deepcopy
 from pathlib import Path
 
 import numpy as np
@@ -84,6 +86,22 @@ class RawTriangle:
             self.loadPLY(ply_path)
         if glb_path is not None:
             self.loadGLB(glb_path)
+        self.contained_idx = np.ones(len(self), dtype=bool)  # raw_triangle.py:31: the triangles the next reduce() keeps
+
+    @property
+    def center(self):  # raw_triangle.py:33-35
+        return self.vertex.mean(axis=1)
+
+    def printStats(self):  # raw_triangle.py:37-49
+        banner = "=" * 20 + " RawTriangle Stats " + "=" * 20
+        print(banner)
+        print(f"Number of points: {len(self)}")
+        print(f"Number of SHs: {self.shs.shape[1] // 3}")
+        for axis, name in enumerate("xyz"):
+            print(f"{name} range: {self.vertex[..., axis].min():>8.1f} - {self.vertex[..., axis].max():>8.1f}")
+        print(f"z mean: {self.vertex[..., 2].mean():>8.1f}")
+        print(f"z median: {np.median(self.vertex[..., 2]):>8.1f}")
+        print("=" * len(banner))
 
     def __len__(self):
         return len(self.vertex) if self.vertex is not None else 0
@@ -96,6 +114,63 @@ class RawTriangle:
         if key.dtype == np.bool_ and key.shape != (len(self),):
             raise IndexError(f"a boolean mask must have one entry per triangle ({len(self)}), not shape {key.shape}")
         return RawTriangle(self.vertex[key], self.opacity[key], self.shs[key])
+
+    # ---- set operations (raw_triangle.py:65-122) ------------------------------------------------------------------------------
+    def __iadd__(self, other):
+        """Appends `other`'s triangles and their contained_idx marks; an empty `other` changes nothing."""
+        if len(other) == 0:
+            return self
+        for name in ("vertex", "opacity", "shs", "contained_idx"):
+            mine, theirs = getattr(self, name), getattr(other, name)
+            setattr(self, name, np.concatenate((mine, theirs)) if mine is not None else theirs)
+        return self
+
+    def resetContainedIdx(self):
+        self.contained_idx = np.ones(len(self), dtype=bool)
+
+    def __isub__(self, other):
+        """Set difference by centre distance: drops every triangle whose centre has a centre of `other` within 1e-5 of it, i.e.
+        contained_idx &= sqrt(float64(dist2)) > 1e-5 followed by reduce(); an empty `other` changes nothing.  The reference asks
+        scipy.spatial.KDTree for the float64 distance; here dist2 is diff_recon_hip.nearest_points' fp32 squared distance between the fp32
+        centres on the HIP device (a RuntimeError without a device, there is no CPU fallback), so the two depart only for centres whose
+        distance lies within fp32 rounding of 1e-5.  A centre with a non-finite coordinate has no neighbour and is kept."""
+        if len(other) == 0:
+            return self
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("RawTriangle's set difference (MI355X build) searches the centres on a HIP device; there is no CPU fallback")
+        from .mesh_distance import nearest_points
+        device = torch.device("cuda", torch.cuda.current_device())
+        mine = torch.from_numpy(np.ascontiguousarray(self.center, dtype=np.float32)).to(device)
+        theirs = torch.from_numpy(np.ascontiguousarray(other.center, dtype=np.float32)).to(device)
+        _, dist2 = nearest_points(mine, theirs)
+        self.contained_idx &= ~(np.sqrt(dist2.cpu().numpy().astype(np.float64)) <= 1e-5)  # NaN (no neighbour): kept
+        self.reduce()
+        return self
+
+    def __sub__(self, other):
+        diff = deepcopy(self)
+        diff -= other
+        return diff
+
+    def reduce(self):
+        """Drops the triangles whose contained_idx is False and returns them as a RawTriangle; an empty one when nothing was marked."""
+        if np.all(self.contained_idx):
+            return RawTriangle()
+        gone = ~self.contained_idx
+        removed = RawTriangle(self.vertex[gone], self.opacity[gone], self.shs[gone])
+        self.vertex, self.opacity, self.shs = self.vertex[self.contained_idx], self.opacity[self.contained_idx], self.shs[self.contained_idx]
+        self.resetContainedIdx()
+        return removed
+
+    def replace(self, indices, other):
+        """Overwrites the triangles at `indices` with `other`'s, one for one."""
+        if len(indices) != len(other):
+            raise ValueError("Length of removed_triangle is not equal to other, length of removed_triangle is {}, length of other is {}".format(
+                len(indices), len(other)))
+        self.vertex[indices] = other.vertex
+        self.opacity[indices] = other.opacity
+        self.shs[indices] = other.shs
 
     def with_face_colors(self, rgb):
         """A copy whose DC coefficients are RGB2SH(rgb) (`rgb` (P, 3), e.g. diff_recon_hip.bake_face_colors' result for the front faces):

@@ -1,5 +1,5 @@
 """The C ABI of libts2d.so as ctypes sees it, declared once: the mirrors of the structs of include/*.h and the signature of every function
-they declare (and of the lab library's additions, csrc/ts2d_lab.h).  Pure ctypes: no torch, no library is loaded here -- `_C.py` binds the
+they declare (and of the lab library's additions, csrc/ts2d_lab.h, and of the second product library libts_geom.so, include/ts_geom.h).  Pure ctypes: no torch, no library is loaded here -- `_C.py` binds the
 library the package loads, the CPU tests bind a CDLL of their own.  tests/test_cabi_cpu.py holds both tables against the headers: the structs
 by sizeof / offsetof, the functions prototype by prototype.
 
@@ -166,6 +166,28 @@ LAB_SIGNATURES = {
     "ts2d_lab_depth_split": (None, [C.c_int, C.c_int]),
     "ts2d_lab_force_all_quadrants": (None, [C.c_int]),
 }
+
+# include/ts_geom.h: the whole C ABI of diff_recon_hip/libts_geom.so, a library of its own (diff_recon_hip/mesh_distance.py loads and binds it)
+GEOM_SIGNATURES = {
+    "tsg_last_error": (C.c_char_p, []),
+    "tsg_cross_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "tsg_nearest_cross": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "tsg_sample_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "tsg_face_areas": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "tsg_sample_surface": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int32, C.c_uint64, _vp, _vp, _vp, C.c_size_t, _vp]),
+}
+
+
+def bind_geom(lib):
+    """Sets restype and argtypes of every function of include/ts_geom.h on `lib` (a ctypes.CDLL of libts_geom.so); a library that lacks one is
+    refused."""
+    missing = [name for name in GEOM_SIGNATURES if not hasattr(lib, name)]
+    if missing:
+        raise ImportError(f"{getattr(lib, '_name', lib)} does not export {', '.join(missing)}: rebuild it with `python triangle-splatting_amd/build.py`")
+    for name, (restype, argtypes) in GEOM_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return lib
 
 
 def bind(lib):

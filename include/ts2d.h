@@ -34,6 +34,12 @@
  * Matrix convention (unchanged from the reference): viewmatrix / projmatrix are 16 floats, element
  * [col*4+row] of the usual column-vector matrix, i.e. the row-major storage of the transposed
  * matrices built by src/diff_recon/utils/camera.py:112-114; see R2D/src/auxiliary.h:40-58.
+ *
+ * Purity (DESIGN.md "Purity of the entry points"; tests/test_purity_gpu.py): every result is a function of the documented inputs only --
+ * what the three state buffers, the backward scratch and any output held on entry does not matter; every element of radii, of every
+ * non-NULL forward output, of every gradient output and of ts2d_sh_grad_expand's dL_dshs is written (overwritten, never accumulated
+ * into), the rows of culled triangles with zeros; and no byte outside the sizes the *_bytes queries return, or outside an output's
+ * documented extent, is written.
  */
 #ifndef TS2D_H
 #define TS2D_H

@@ -43,6 +43,10 @@
  *   `area` is meant to be what the face-area call wrote for the same mesh.  A face drawn from a foreign `area` whose indices lie outside
  *   [0, V) is never read: its point is 0.  Areas are non-negative and not NaN.
  *   N == 0 is the no-op.
+ *
+ * Purity (DESIGN.md "Purity of the entry points").  The workspaces may hold anything on entry; nearest, dist2, area, points and face are
+ * overwritten in full whatever they held; `box_visits` is a caller-cleared accumulator; no byte outside the workspace sizes or an output's
+ * extent is written.
  */
 #ifndef TS_GEOM_H
 #define TS_GEOM_H

@@ -10,7 +10,11 @@
  * (C, H, W) -- a leading batch dimension folds into C, exactly as the reference's depthwise conv + global mean does.
  * Every call enqueues on `stream` and returns TS2D_OK (0) or an error code of ts2d.h with ts2d_last_error() set.
  * Further sections: the depth / normal loss, the auxiliary image losses, the down-sampler, and the trainer's regularisers with the per-view
- * colour affine (tsl_reg_*, tsl_color_affine_*; the regularisation half of VanillaTS_trainer.py:86-116). */
+ * colour affine (tsl_reg_*, tsl_color_affine_*; the regularisation half of VanillaTS_trainer.py:86-116).
+ * Purity (DESIGN.md "Purity of the entry points"): results are functions of the documented inputs only -- a workspace or prepared buffer may
+ * hold anything on entry and may have served another size or another call before (a backward needs the workspace its own forward filled);
+ * every output -- out, masks, dL_d*, down-sampled planes, dL_dweight / dL_dbias (9 + 3 floats: overwritten, not accumulated) -- is fully
+ * written; no byte outside *_workspace_bytes / tsl_reg_prepared_bytes or outside an output's extent is written. */
 #ifndef TS_LOSS_H
 #define TS_LOSS_H
 

@@ -21,6 +21,9 @@
  * reduction (pixels won, fixed-point colour sums of a target image) that accumulates over views in integers.
  * All pointers except `cam`, `state` and `num_rendered` are device pointers; everything is enqueued on `stream` (a hipStream_t).
  * Return value and ts2d_last_error() as in ts2d.h.
+ * Purity (DESIGN.md "Purity of the entry points"): the images are functions of the documented inputs only, whatever the state buffers and
+ * the outputs held on entry; every element of every non-NULL output of the render calls is overwritten; `census` and `wave_visits` are
+ * caller-cleared accumulators (inputs); no byte outside the state sizes or an output's extent is written.
  */
 #ifndef TS_MESH_H
 #define TS_MESH_H

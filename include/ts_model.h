@@ -15,7 +15,11 @@
  * HBM-bound pass.  `num_views` > 1 applies the update for several views of the same step in one launch (image-parallel
  * training: ranks all-gather the four per-view arrays; every rank applies the same views in the same order, so all ranks end up with
  * identical state, and the views are accumulated one after the other from the state's value, so the result is bit for bit that of
- * num_views launches of one view each, i.e. of the one-process loop).  All pointers are device pointers. */
+ * num_views launches of one view each, i.e. of the one-process loop).  All pointers are device pointers.
+ * Purity (DESIGN.md "Purity of the entry points"): the select scratch may hold anything on entry; pos, code, the masks, the split children,
+ * tsm_max_vertex_distance's out and the digests are fully written (overwritten) whatever they held; the in-place statistics, the Adam moments
+ * and the parameter rows are inputs that change only where the call says so -- rows that a scatter, gather, clip or mask does not select
+ * keep their bits -- and nothing outside the documented extents is written. */
 #ifndef TS_MODEL_H
 #define TS_MODEL_H
 

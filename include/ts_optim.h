@@ -18,7 +18,9 @@
  * The two bias corrections are formed by the caller in double, like torch forms them in Python, and handed over as floats.  Built without
  * FMA contraction; torch's own kernels may contract a product into the following sum, so results agree with torch.optim.Adam to 1 ulp per
  * operation, not bit for bit (tests/test_optim_gpu.py states the bound).  HBM-bound: 16 bytes read + 12 written per element.
- * All pointers are device pointers; `count` floats each; asynchronous on `stream`. */
+ * All pointers are device pointers; `count` floats each; asynchronous on `stream`.
+ * There is no workspace.  param, exp_avg and exp_avg_sq are updated in place (inputs); the calls write those `count` floats (rows) of
+ * each slice and nothing else, at any alignment and length (DESIGN.md "Purity of the entry points"). */
 #ifndef TS_OPTIM_H
 #define TS_OPTIM_H
 

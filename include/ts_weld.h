@@ -29,6 +29,10 @@
  * a null required pointer or a workspace below ts2d_weld_workspace_bytes(V, F) return TS2D_ERR_INVALID with the text in ts2d_last_error().
  * V == 0 (F == 0 for the two calls that sweep faces) is a no-op that returns TS2D_OK.  `keep` arrays hold one byte per face (0 / 1).
  * The entry points carry the library's ts2d_ prefix like ts_mesh.h's.
+ *
+ * Purity (DESIGN.md "Purity of the entry points"): one workspace serves the whole chain in any order and may hold anything on entry;
+ * label, remap, all V rows of out_vertices (rows V' .. V-1 zero), count, out_faces, keep and counts are overwritten whatever they held;
+ * `box_visits` is a caller-cleared accumulator; no byte outside ts2d_weld_workspace_bytes(V, F) or an output's extent is written.
  */
 #ifndef TS_WELD_H
 #define TS_WELD_H

@@ -56,7 +56,17 @@ void prof_drain()
 
 #ifdef TS2D_LAB
 bool g_lab_all_quadrants = false; // ts2d_lab_force_all_quadrants (csrc/ts2d_lab.h)
+bool g_lab_kernel_cull = false;   // ts2d_lab_force_kernel_cull
 #endif
+
+// 2D variant, grids of at most 65 535 tiles: the emission writes every instance's 4x4 block mask into the top half of its tile key
+// (ts2d_support.h) and the blend kernels read it there.  A function of the call's arguments only, so the backward agrees with the forward that
+// filled the state.
+bool block_masks_in_keys(const ts2d_camera *cam, uint32_t flags)
+{
+    const int gx = (cam->width + TS_TILE - 1) / TS_TILE, gy = (cam->height + TS_TILE - 1) / TS_TILE;
+    return !(flags & TS2D_FLAG_3D) && (int64_t)gx * gy <= TS_BLOCKMASK_MAX_TILES;
+}
 
 int validate(const ts2d_camera *cam, const ts2d_geometry *geom, uint32_t flags)
 {
@@ -106,6 +116,10 @@ RenderArgs make_render(const ts2d_camera *cam, const ts2d_geometry *geom, uint32
     r.background_depth_dev = geom->background_depth_dev;
     r.background = geom->background;
     r.rich_info = flags & TS2D_FLAG_RICH_INFO;
+    r.block_masks = block_masks_in_keys(cam, flags);
+#ifdef TS2D_LAB
+    if (g_lab_kernel_cull) r.block_masks = false; // the blend kernels' second instantiation: the keys' masks are there and not looked at
+#endif
     return r;
 }
 
@@ -202,9 +216,10 @@ int forward_render_impl(const ts2d_camera *cam, const ts2d_geometry *geom, uint3
     const unsigned long long *n_dev = count_on_device ? ts_instance_count_dev(g, P) : nullptr;
 
     // quadrant masks for the blend kernels of both variants (ts2d_support.h, ts2d_common.h: QuadMaskArgs)
-    QuadMaskArgs quad{(flags & TS2D_FLAG_3D) ? 3 : 2, fmaxf(0.0f, 2.0f * geom->gamma), cam->tan_fovx, cam->tan_fovy, W, H, 1.0f / (float)W, 1.0f / (float)H};
+    QuadMaskArgs quad{(flags & TS2D_FLAG_3D) ? 3 : 2, fmaxf(0.0f, 2.0f * geom->gamma), cam->tan_fovx, cam->tan_fovy, W, H, 1.0f / (float)W, 1.0f / (float)H,
+                      block_masks_in_keys(cam, flags) ? 1 : 0};
 #ifdef TS2D_LAB
-    if (g_lab_all_quadrants) quad.variant = 0; // every instance reaches every quadrant: what the masks must not change (tests/test_qmask_gpu.py)
+    if (g_lab_all_quadrants) quad.variant = 0; // every instance reaches every quadrant (and block): what the masks must not change (tests/test_qmask_gpu.py)
 #endif
     if (int rc = ts_order_instances(flags, P, r.grid_x, ntiles, g, b, im, rich ? out->contrib_sum : nullptr, rich ? out->contrib_max : nullptr, N, n_dev,
                                     quad, s))
@@ -376,7 +391,7 @@ int ts_order_instances(uint32_t flags, int P, int grid_x, int ntiles, const Geom
     {
         { ProfScope ps("tile_sort", s); ts_sort_pairs(b, N, n_dev, ntiles, s); } // tile bits only, see binning.hip
         TS_CHECK(flags, s, "tile_sort");
-        { ProfScope ps("tile_ranges", s); ts_launch_tile_ranges(N, n_dev, b, im, s); }
+        { ProfScope ps("tile_ranges", s); ts_launch_tile_ranges(N, n_dev, ntiles, b, im, s); }
         TS_CHECK(flags, s, "tile_ranges");
     }
     return TS2D_OK;
@@ -717,7 +732,8 @@ int ts2d_debug_read_state(const ts2d_state *state, int32_t P, int64_t N, int32_t
             TS_HIP(hipStreamSynchronize(s));
         }
         uint64_t *o = (uint64_t *)dst;
-        for (int64_t i = 0; i < N; i++) o[i] = ((uint64_t)tile[i] << 32) | depth[vals[i] & TS_ID_MASK]; // id bits (the top four: quadrant mask, ts2d_support.h)
+        const uint32_t keymask = ts_tile_keymask(gx * gy); // above the tile bits: the 2D variant's block masks (ts2d_support.h)
+        for (int64_t i = 0; i < N; i++) o[i] = ((uint64_t)(tile[i] & keymask) << 32) | depth[vals[i] & TS_ID_MASK]; // id bits (the top four: quadrant mask)
         return TS2D_OK;
     }
     case 11: src = b.vals; bytes = (size_t)N * 4; break;
@@ -753,6 +769,7 @@ int ts2d_debug_read_state(const ts2d_state *state, int32_t P, int64_t N, int32_t
 // ts2d_test_sort_pairs / ts2d_test_inclusive_scan_rocprim: tools/lab/lab_hooks.hip (the rocPRIM comparators live there, outside the product's objects)
 void ts2d_lab_force_ticket_passes(int on) { ts_force_ticket_passes(on != 0); }
 void ts2d_lab_force_all_quadrants(int on) { g_lab_all_quadrants = on != 0; }
+void ts2d_lab_force_kernel_cull(int on) { g_lab_kernel_cull = on != 0; }
 void ts2d_lab_force_depth_pass4(int on) { ts_force_depth_pass4(on != 0); }
 void ts2d_lab_depth_split(int mode, int bucket_cap) { ts_lab_depth_split(mode, bucket_cap); }
 #endif // TS2D_LAB

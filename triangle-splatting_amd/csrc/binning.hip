@@ -821,6 +821,9 @@ constexpr uint32_t SMALL = 32;
 #ifndef TS_EMIT_WAVES // register budget for N waves per SIMD (0: the compiler's choice)
 #define TS_EMIT_WAVES 6
 #endif
+// BM: the instances' block masks go into the keys' top halves (QuadMaskArgs::blocks) -- an instantiation of its own, so that neither form
+// carries the other's registers.
+template <bool BM>
 #if TS_EMIT_WAVES > 0
 __global__ void __launch_bounds__(256, TS_EMIT_WAVES) scan_emit_kernel(
 #else
@@ -901,6 +904,9 @@ int P, int grid_x, int ntiles, GeometryStateView g, BinningStateView b, uint2 *r
     // the four spare bits of an instance's value say which 8x8 quadrants of its tile the triangle's support can reach (ts2d_support.h; both
     // variants since round 5, ts2d_common.h: QuadMaskArgs); the blend kernels' quadrant waves then skip the other entries unseen
     constexpr bool qm = true;
+    // 2D variant on grids of at most 65 535 tiles: the instance's sixteen 4x4 BLOCK bits go into bits 16..31 of its tile key (the tile sort ranks
+    // the low bits only and moves the word whole), the quadrant bits are the OR of their nibbles; the blend kernels then cull nothing themselves
+    constexpr bool bm = BM;
     const float quad_g2 = qmask.g2;
     auto setup_from = [&](const float4 &r0, const float4 &r1, const float4 &r2, uint32_t tminx, uint32_t tminy, uint32_t tmaxx, uint32_t tmaxy) {
         if (qmask.variant == 0) return quad_setup_all(); // lab library only: every quadrant (ts2d_lab_force_all_quadrants)
@@ -911,7 +917,7 @@ int P, int grid_x, int ntiles, GeometryStateView g, BinningStateView b, uint2 *r
                                  (float)(tminy * TS_TILE) - 1.0f, (float)(tmaxx * TS_TILE), (float)(tmaxy * TS_TILE));
         }
         const float E = quad_g2 == 2.0f ? support_scale<true>(r1.z, quad_g2) : support_scale<false>(r1.z, quad_g2);
-        return quad_setup(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, E);
+        return quad_setup<bm ? 3 : 7>(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, E); // block masks: the 4x4 sample box
     };
     auto setup_of = [&](uint32_t tri, uint32_t tminx, uint32_t tminy, uint32_t tmaxx, uint32_t tmaxy) { // another lane's triangle: gathered here
         const float4 *rp = g.rec + 4 * (size_t)tri;
@@ -963,8 +969,17 @@ int P, int grid_x, int ntiles, GeometryStateView g, BinningStateView b, uint2 *r
             for (uint32_t y = miny; y < maxy; y++)
                 for (uint32_t x = minx; x < maxx; x++)
                 {
-                    tile_out[o] = y * grid_x + x;
-                    val_out[o] = qm ? id | (quadrant_mask(qs, (float)(x * TS_TILE), (float)(y * TS_TILE)) << TS_ID_BITS) : id;
+                    if (bm)
+                    {
+                        const uint32_t m16 = block_mask(qs, (float)(x * TS_TILE), (float)(y * TS_TILE));
+                        tile_out[o] = (y * grid_x + x) | (m16 << 16);
+                        val_out[o] = id | (quadrants_of_blocks(m16) << TS_ID_BITS);
+                    }
+                    else
+                    {
+                        tile_out[o] = y * grid_x + x;
+                        val_out[o] = qm ? id | (quadrant_mask(qs, (float)(x * TS_TILE), (float)(y * TS_TILE)) << TS_ID_BITS) : id;
+                    }
                     o++;
                 }
     }
@@ -988,8 +1003,17 @@ int P, int grid_x, int ntiles, GeometryStateView g, BinningStateView b, uint2 *r
             }
             else
             {
-                tile_out[t_off + k] = y * grid_x + x;
-                val_out[t_off + k] = qm ? t_id | (quadrant_mask(tq, (float)(x * TS_TILE), (float)(y * TS_TILE)) << TS_ID_BITS) : t_id;
+                if (bm)
+                {
+                    const uint32_t m16 = block_mask(tq, (float)(x * TS_TILE), (float)(y * TS_TILE));
+                    tile_out[t_off + k] = (y * grid_x + x) | (m16 << 16);
+                    val_out[t_off + k] = t_id | (quadrants_of_blocks(m16) << TS_ID_BITS);
+                }
+                else
+                {
+                    tile_out[t_off + k] = y * grid_x + x;
+                    val_out[t_off + k] = qm ? t_id | (quadrant_mask(tq, (float)(x * TS_TILE), (float)(y * TS_TILE)) << TS_ID_BITS) : t_id;
+                }
             }
         }
     }
@@ -1005,8 +1029,17 @@ int P, int grid_x, int ntiles, GeometryStateView g, BinningStateView b, uint2 *r
                 QuadAffine qa;
                 qa.a = region_b[4 * slot]; qa.b = region_b[4 * slot + 1]; qa.c = region_b[4 * slot + 2]; qa.d = region_b[4 * slot + 3];
                 const uint32_t org = __float_as_uint(qa.d.z), x = (org & 0xffffu) + dx, y = (org >> 16) + dy;
-                v = __float_as_uint(qa.d.y) | (quadrant_mask_affine(qa, dx, dy, x, y) << TS_ID_BITS);
-                tl = y * grid_x + x;
+                if (bm)
+                {
+                    const uint32_t m16 = block_mask_affine(qa, dx, dy, x, y);
+                    v = __float_as_uint(qa.d.y) | (quadrants_of_blocks(m16) << TS_ID_BITS);
+                    tl = (y * grid_x + x) | (m16 << 16);
+                }
+                else
+                {
+                    v = __float_as_uint(qa.d.y) | (quadrant_mask_affine(qa, dx, dy, x, y) << TS_ID_BITS);
+                    tl = y * grid_x + x;
+                }
             }
             else v = stage_v[k];
             tile_out[run0 + k] = tl;
@@ -1017,8 +1050,9 @@ int P, int grid_x, int ntiles, GeometryStateView g, BinningStateView b, uint2 *r
 
 // Four consecutive instances per thread (one dwordx4 + the word in front): a quarter of the workgroups and of the loads of the one-key-per-thread
 // form (10.4 -> 7.6 us at the headline, 38.9 -> 19.1 us at 5 M triangles: profiles/r05_notes.md section 12).  `tile` is 16-byte aligned (ts_carve); words past N are never looked at.
+// keymask: the key's tile bits (ts_tile_keymask: above them a 2D instance carries its block mask).
 __global__ void __launch_bounds__(256) tile_ranges_kernel(int64_t N, const unsigned long long *n_dev, const uint32_t *__restrict__ tile,
-                                                           uint2 *__restrict__ ranges)
+                                                           uint2 *__restrict__ ranges, uint32_t keymask)
 {
     const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
     if (n_dev)
@@ -1031,11 +1065,11 @@ __global__ void __launch_bounds__(256) tile_ranges_kernel(int64_t N, const unsig
     if (i0 + 3 < N)
     {
         const uint4 q = *(const uint4 *)(tile + i0);
-        k[0] = q.x; k[1] = q.y; k[2] = q.z; k[3] = q.w;
+        k[0] = q.x & keymask; k[1] = q.y & keymask; k[2] = q.z & keymask; k[3] = q.w & keymask;
     }
     else
-        for (int j = 0; j < 4; j++) k[j] = i0 + j < N ? tile[i0 + j] : 0u;
-    uint32_t prev = i0 > 0 ? tile[i0 - 1] : 0u;
+        for (int j = 0; j < 4; j++) k[j] = i0 + j < N ? tile[i0 + j] & keymask : 0u;
+    uint32_t prev = i0 > 0 ? tile[i0 - 1] & keymask : 0u;
 #pragma unroll
     for (int j = 0; j < 4; j++)
     {
@@ -1703,8 +1737,13 @@ void ts_launch_emit_keys(int P, int grid_x, int ntiles, const GeometryStateView 
                          float *contrib_sum, float *contrib_max, int64_t capacity, int32_t *status, const QuadMaskArgs &qmask, hipStream_t s)
 {
     if (P <= 0) return;
-    hipLaunchKernelGGL(scan_emit_kernel, dim3((unsigned)(((P + SB - 1) / SB) * 4)), dim3(256), 0, s, P, grid_x, ntiles, g, b, im.ranges, contrib_sum,
-                       contrib_max, (long long)capacity, status, scan_two_level(P), qmask);
+    const dim3 grid((unsigned)(((P + SB - 1) / SB) * 4));
+    if (qmask.blocks)
+        hipLaunchKernelGGL(scan_emit_kernel<true>, grid, dim3(256), 0, s, P, grid_x, ntiles, g, b, im.ranges, contrib_sum, contrib_max, (long long)capacity,
+                           status, scan_two_level(P), qmask);
+    else
+        hipLaunchKernelGGL(scan_emit_kernel<false>, grid, dim3(256), 0, s, P, grid_x, ntiles, g, b, im.ranges, contrib_sum, contrib_max, (long long)capacity,
+                           status, scan_two_level(P), qmask);
 }
 const unsigned long long *ts_instance_count_dev(const GeometryStateView &g, int P) { return (const unsigned long long *)(g.blocksum + (P + SB - 1) / SB); }
 
@@ -1727,10 +1766,10 @@ void ts_sort_pairs(const BinningStateView &b, int64_t N, const unsigned long lon
     }
 }
 
-void ts_launch_tile_ranges(int64_t N, const unsigned long long *n_dev, const BinningStateView &b, const ImageStateView &im, hipStream_t s)
+void ts_launch_tile_ranges(int64_t N, const unsigned long long *n_dev, int ntiles, const BinningStateView &b, const ImageStateView &im, hipStream_t s)
 {
     if (N <= 0) return;
-    hipLaunchKernelGGL(tile_ranges_kernel, dim3((unsigned)((N + 1023) / 1024)), dim3(256), 0, s, N, n_dev, b.tile, im.ranges);
+    hipLaunchKernelGGL(tile_ranges_kernel, dim3((unsigned)((N + 1023) / 1024)), dim3(256), 0, s, N, n_dev, b.tile, im.ranges, ts_tile_keymask(ntiles));
 }
 
 // ---- the same sort for other callers (knn.hip: 30-bit Morton codes) --------------------------------------------------------

@@ -6,7 +6,15 @@
 // arg-min tie order a1, a2, a3, division by ecc + 1e-8).
 //
 // Structure: the lane-group skeleton of ts2d_group.h (one wave64 per 8x8 quadrant, four 16-lane groups that each walk their own culled
-// list); the cull's edge functions are affine forms of the in-quadrant pixel offset, used for CULLING only.  What this file holds:
+// list).  Front end: which of the quadrant's four 4x4 blocks an entry can reach is decided ONCE per instance, by the emission kernel
+// (ts2d_support.h: block_mask), and arrives in bits 16..31 of the instance's sorted tile key: a batch's refill loads the key beside the value,
+// keeps the entries whose nibble for this quadrant is not zero and carries the nibble along with the id (ts2d_group.h: stream_refill<.., NIB>);
+// the four per-block entry masks are ballots of its bits.  No cull runs here (about 115 of a batch's ~340 VALU instructions per lane, in the
+// forward and again in the backward, for every quadrant wave that visits the instance).  CULL = true is the kernels' second instantiation,
+// the front end of before: the quadrant bit of the value selects the entries and block_cull below tests each against the four blocks (affine
+// edge functions of the in-quadrant pixel offset, used for CULLING only).  The host picks it when the keys carry no masks (grids of more than
+// 65 535 tiles, RenderArgs::block_masks); the lab library's ts2d_lab_force_kernel_cull picks it at run time, for the A/B inside one build
+// (tests/test_blockmask_gpu.py).  What this file holds:
 //   pixels  = barycentrics are evaluated exactly as the reference does, cross(v_j - p, v_k - p) / area2 from
 //             pixel-relative vertex offsets (v - tile origin and (v - origin) - offset are exact in fp32, so the offsets
 //             are bit-identical to the reference's).  Round 1 used affine forms of the pixel offset instead: 4 FMAs
@@ -119,6 +127,19 @@ __device__ __forceinline__ BlockCull block_cull(float v1x, float v1y, float v2x,
     return s;
 }
 
+// What a batch needs of its lane's entry: the row geometry and the four block flags.  CULL: computed here (block_cull).  Otherwise the flags are
+// the nibble above the id's TS_ID_BITS, as the emission kernel formed it (ts2d_support.h: block_mask -- the same test, once per instance).
+template <bool GAMMA1, bool CULL>
+__device__ __forceinline__ BlockCull entry_blocks(const float4 &r0, const float4 &r1, uint32_t id_nibble, float g2, float OX, float OY)
+{
+    if (CULL) return block_cull<GAMMA1>(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, g2, OX, OY);
+    BlockCull s;
+    entry_geometry(s, r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, OX, OY);
+#pragma unroll
+    for (int g = 0; g < 4; g++) s.ov[g] = (id_nibble >> (TS_ID_BITS + g)) & 1u;
+    return s;
+}
+
 // Row -1: a unit triangle a thousand pixels away with opacity 0 -> every pixel of the quadrant sees ecc ~ 3000 and alpha 0.
 __device__ __forceinline__ void write_dummy_row(float *row, int lane)
 {
@@ -159,9 +180,10 @@ __device__ unsigned long long g_stats_group[12];
 #endif
 
 #if TSG_PART & 1
-template <bool RICH, bool GAMMA1>
+template <bool RICH, bool GAMMA1, bool CULL>
 __global__ void __launch_bounds__(256, TSG_FWD_WAVES) render_fwd_group_kernel(RenderArgs a, const uint2 *__restrict__ ranges,
-                                                                const uint32_t *__restrict__ point_list, const float4 *__restrict__ rec,
+                                                                const uint32_t *__restrict__ point_list, const uint32_t *__restrict__ keys,
+                                                                const float4 *__restrict__ rec,
                                                                 float *__restrict__ final_T, uint32_t *__restrict__ n_contrib,
                                                                 float *__restrict__ out_feature, float *__restrict__ out_depth,
                                                                 float *__restrict__ out_normal, float *__restrict__ contrib_sum,
@@ -194,7 +216,8 @@ __global__ void __launch_bounds__(256, TSG_FWD_WAVES) render_fwd_group_kernel(Re
 #ifdef TS2D_STATS
     unsigned long long stat_acc[12] = {0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0};
 #endif
-    // dense batches: only the entries whose quadrant bit is set are gathered and culled (ts2d_group.h, stream_refill); `pos` = list position
+    // dense batches: only the entries that reach this quadrant are gathered (ts2d_group.h, stream_refill); `pos` = list position,
+    // `id` = the triangle, and above its TS_ID_BITS the entry's block nibble (!CULL)
     uint32_t id = 0;
     int pos = 0, cursor = 0;
     for (;;)
@@ -202,13 +225,15 @@ __global__ void __launch_bounds__(256, TSG_FWD_WAVES) render_fwd_group_kernel(Re
         const unsigned long long alive = ballot(!P.done);
         if (alive == 0) break;
         int nq = 0;
-        stream_refill<false, TSG_FWD_CAP>(id, pos, nq, point_list + range.x, cursor, len, TS_ID_BITS + wave, lane);
+        stream_refill<false, TSG_FWD_CAP, !CULL>(id, pos, nq, point_list + range.x, cursor, len, CULL ? TS_ID_BITS + wave : 16 + 4 * wave, lane,
+                                                 keys + range.x);
         if (nq == 0) break;
         const bool valid = lane < nq;
         const int ent = pos;
+        const uint32_t tid = CULL ? id : id & TS_ID_MASK;
         float4 r0 = make_float4(0, 0, 0, 0), r1 = r0, r2 = r0, r3 = r0;
-        gather_record<RICH>(rec, id, valid, r0, r1, r2, r3);
-        const BlockCull s = block_cull<GAMMA1>(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, g2, OX, OY);
+        gather_record<RICH>(rec, tid, valid, r0, r1, r2, r3);
+        const BlockCull s = entry_blocks<GAMMA1, CULL>(r0, r1, id, g2, OX, OY);
         unsigned long long M[4];
         const unsigned long long any = fwd_block_masks(M, alive, valid, s.ov);
         TSG_STAT(0, __popcll(ballot(valid)));
@@ -218,7 +243,7 @@ __global__ void __launch_bounds__(256, TSG_FWD_WAVES) render_fwd_group_kernel(Re
         TSG_STAT(7, __popcll(any));
         const Compaction cp = compact_rows(any, lane);
         bool mine = in_pass(cp, false);
-        if (mine) publish_row(cst + cp.r * ROW, s, id, ent, r1, r2, r3);
+        if (mine) publish_row(cst + cp.r * ROW, s, tid, ent, r1, r2, r3);
         for (int h = 0;;)
         {
             const int steps = build_lists(list, M, pass_mask(cp, mine), row0, cp.r, ROW, dummy, lane);
@@ -293,9 +318,10 @@ __global__ void __launch_bounds__(256, TSG_FWD_WAVES) render_fwd_group_kernel(Re
 // leave as coalesced 64-byte atomic adds, one gradient record per 16 lanes.
 // One wave per workgroup (ts2d_group.h: tile_of_quadrant_block).
 #if TSG_PART & 2
-template <bool RICH, bool GAMMA1>
+template <bool RICH, bool GAMMA1, bool CULL>
 __global__ void __launch_bounds__(64, TSG_BWD_WAVES) render_bwd_group_kernel(RenderArgs a, const uint2 *__restrict__ ranges,
-                                                             const uint32_t *__restrict__ point_list, const float4 *__restrict__ rec,
+                                                             const uint32_t *__restrict__ point_list, const uint32_t *__restrict__ keys,
+                                                             const float4 *__restrict__ rec,
                                                              const float *__restrict__ final_T, const uint32_t *__restrict__ n_contrib,
                                                              const float *__restrict__ dL_dout_feature,
                                                              const float *__restrict__ dL_dout_depth,
@@ -344,20 +370,22 @@ __global__ void __launch_bounds__(64, TSG_BWD_WAVES) render_bwd_group_kernel(Ren
     for (;;)
     {
         int nq = 0;
-        stream_refill<true, TSG_BWD_CAP>(id, pos, nq, point_list + range.x, cursor, maxlast, TS_ID_BITS + quad, lane);
+        stream_refill<true, TSG_BWD_CAP, !CULL>(id, pos, nq, point_list + range.x, cursor, maxlast, CULL ? TS_ID_BITS + quad : 16 + 4 * quad, lane,
+                                                keys + range.x);
         if (nq == 0) break;
         const bool valid = lane < nq;
         const int ent = pos;
+        const uint32_t tid = CULL ? id : id & TS_ID_MASK;
         float4 r0 = make_float4(0, 0, 0, 0), r1 = r0, r2 = r0, r3 = r0;
-        gather_record<RICH>(rec, id, valid, r0, r1, r2, r3);
-        const BlockCull s = block_cull<GAMMA1>(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, g2, OX, OY);
+        gather_record<RICH>(rec, tid, valid, r0, r1, r2, r3);
+        const BlockCull s = entry_blocks<GAMMA1, CULL>(r0, r1, id, g2, OX, OY);
         unsigned long long M[4];
         const unsigned long long any = bwd_block_masks(M, valid, s.ov, pos, glast);
         if (any == 0) continue;
         // back to front = the low lanes first (lane 0 is the entry farthest back)
         const Compaction cp = compact_rows(any, lane);
         bool mine = in_pass(cp, false);
-        if (mine) publish_row(rows + cp.r * BROW, s, id, ent, r1, r2, r3);
+        if (mine) publish_row(rows + cp.r * BROW, s, tid, ent, r1, r2, r3);
         for (int h = (cp.nact - 1) / NR;;)
         {
             const unsigned long long mm = pass_mask(cp, mine);
@@ -467,14 +495,31 @@ __global__ void __launch_bounds__(64, TSG_BWD_WAVES) render_bwd_group_kernel(Ren
 #endif // TSG_PART & 2
 } // namespace
 
+// TS_LAUNCH_BLEND (ts2d_group.h) with the 2D kernels' third argument: the keys' block masks (RenderArgs::block_masks) or the in-kernel cull.
+#define TS_BLEND2D_RG(KERNEL, R, G1, A, GRID, BLOCK, STREAM, ...)                                                                  \
+    do                                                                                                                            \
+    {                                                                                                                             \
+        if ((A).block_masks) hipLaunchKernelGGL((KERNEL<R, G1, false>), dim3(GRID), dim3(BLOCK), 0, STREAM, __VA_ARGS__);          \
+        else hipLaunchKernelGGL((KERNEL<R, G1, true>), dim3(GRID), dim3(BLOCK), 0, STREAM, __VA_ARGS__);                          \
+    } while (0)
+#define TS_LAUNCH_BLEND2D(KERNEL, A, GRID, BLOCK, STREAM, ...)                                                                    \
+    do                                                                                                                            \
+    {                                                                                                                             \
+        const bool g1 = ((A).gamma == 1.0f);                                                                                      \
+        if ((A).rich_info && g1) TS_BLEND2D_RG(KERNEL, true, true, A, GRID, BLOCK, STREAM, __VA_ARGS__);                          \
+        else if ((A).rich_info) TS_BLEND2D_RG(KERNEL, true, false, A, GRID, BLOCK, STREAM, __VA_ARGS__);                          \
+        else if (g1) TS_BLEND2D_RG(KERNEL, false, true, A, GRID, BLOCK, STREAM, __VA_ARGS__);                                     \
+        else TS_BLEND2D_RG(KERNEL, false, false, A, GRID, BLOCK, STREAM, __VA_ARGS__);                                            \
+    } while (0)
+
 #if TSG_PART & 1
 void ts_launch_render_fwd_group(const RenderArgs &a, const GeometryStateView &g, const BinningStateView &b, const ImageStateView &im,
                                 float *out_feature, float *out_depth, float *out_normal, float *contrib_sum, float *contrib_max,
                                 hipStream_t s)
 {
     if (a.grid_x * a.grid_y == 0) return;
-    TS_LAUNCH_BLEND(render_fwd_group_kernel, a, ts_tile_units(a.grid_x, a.grid_y), 256, s, a, im.ranges, b.vals, g.rec, im.final_T, im.n_contrib,
-                    out_feature, out_depth, out_normal, contrib_sum, contrib_max);
+    TS_LAUNCH_BLEND2D(render_fwd_group_kernel, a, ts_tile_units(a.grid_x, a.grid_y), 256, s, a, im.ranges, b.vals, b.tile, g.rec, im.final_T, im.n_contrib,
+                      out_feature, out_depth, out_normal, contrib_sum, contrib_max);
 }
 
 #endif // TSG_PART & 1
@@ -498,7 +543,7 @@ void ts_launch_render_bwd_group(const RenderArgs &a, const GeometryStateView &g,
                                 hipStream_t s)
 {
     if (a.grid_x * a.grid_y == 0) return;
-    TS_LAUNCH_BLEND(render_bwd_group_kernel, a, ts_quadrant_units(a.grid_x, a.grid_y), 64, s, a, im.ranges, b.vals, g.rec, im.final_T, im.n_contrib,
-                    dL_dout_feature, dL_dout_depth, dL_dout_normal, grad_rec);
+    TS_LAUNCH_BLEND2D(render_bwd_group_kernel, a, ts_quadrant_units(a.grid_x, a.grid_y), 64, s, a, im.ranges, b.vals, b.tile, g.rec, im.final_T, im.n_contrib,
+                      dL_dout_feature, dL_dout_depth, dL_dout_normal, grad_rec);
 }
 #endif // TSG_PART & 2

@@ -171,6 +171,10 @@ static inline int ts_higher_msb(uint32_t n) // R2D/src/rasterizer.cu:20-35 (same
 // Key bits of the instance sort: the tile ids are 0 .. ntiles - 1.  (The reference sorts 32 + getHigherMsb(ntiles) bits, rasterizer.cu:211-222 -- one
 // more than needed when ntiles is a power of two, e.g. 9 for the 256 tiles of a 256 x 256 image: here that is one 8-bit pass instead of two.)
 static inline int ts_tile_bits(int ntiles) { return ts_higher_msb((uint32_t)(ntiles > 1 ? ntiles - 1 : 1)); }
+// Grids of at most 65 535 tiles leave bits 16..31 of an instance's tile key free: the 2D variant's emission puts the instance's sixteen 4x4 block
+// bits there (ts2d_support.h), every reader of a key masks it with ts_tile_keymask.  Larger grids: the tile alone, the blend kernels cull.
+#define TS_BLOCKMASK_MAX_TILES 65535
+static inline uint32_t ts_tile_keymask(int ntiles) { return ntiles <= TS_BLOCKMASK_MAX_TILES ? 0xFFFFu : 0xFFFFFFFFu; }
 
 static inline size_t ts_carve_binning(char *base, int64_t N, int32_t W, int32_t H, BinningStateView &v)
 {
@@ -253,13 +257,14 @@ struct QuadMaskArgs
     float tan_fovx, tan_fovy;
     int W, H;
     float inv_W, inv_H; // 1 / W, 1 / H (the 3D setup's pixel -> ray conversions; the masks' margins absorb their rounding)
+    int blocks;         // 1: variant 2 on a grid of at most TS_BLOCKMASK_MAX_TILES tiles -- block masks in bits 16..31 of the tile keys
 };
 void ts_launch_zero_words(uint32_t *p, size_t n, hipStream_t s); // binning.hip
 void ts_launch_emit_keys(int P, int grid_x, int ntiles, const GeometryStateView &g, const BinningStateView &b, const ImageStateView &im,
                          float *contrib_sum, float *contrib_max, int64_t capacity, int32_t *status, const QuadMaskArgs &qm, hipStream_t s); // offsets + instances (+ output clears); capacity < 0: synchronous path
 const unsigned long long *ts_instance_count_dev(const GeometryStateView &g, int P);                        // where the scan leaves N
 void ts_sort_pairs(const BinningStateView &b, int64_t N, const unsigned long long *n_dev, int ntiles, hipStream_t s); // stable, tile bits only
-void ts_launch_tile_ranges(int64_t N, const unsigned long long *n_dev, const BinningStateView &b, const ImageStateView &im, hipStream_t s);
+void ts_launch_tile_ranges(int64_t N, const unsigned long long *n_dev, int ntiles, const BinningStateView &b, const ImageStateView &im, hipStream_t s);
 size_t ts_quantile_scratch_bytes();                                                               // select.hip: torch.quantile of non-negative floats by radix select
 void ts_quantile_threshold(const uint32_t *keys, size_t n, float q, void *scratch, float *thr, hipStream_t s);
 void ts_quantile_passes(const uint32_t *keys, size_t n, float q, void *scratch, int first_pass, hipStream_t s); // for callers that weave the select into their own kernels (ts2d_select.h)
@@ -277,6 +282,8 @@ struct RenderArgs
     const float *background; // C floats, device
     const float *background_depth_dev; // optional: one float on the device that overrides background_depth (ts2d_geometry)
     bool rich_info;
+    bool block_masks; // 2D variant: the emission left the instances' block masks in the sorted keys' top halves (QuadMaskArgs::blocks) and the
+                      // blend kernels take them from there; false: they cull in the kernel (grids above TS_BLOCKMASK_MAX_TILES tiles, lab switches)
 };
 // lane-group blend kernels (render_group.hip): four 4x4 pixel blocks per wave, one triangle per block and step
 void ts_launch_render_fwd_group(const RenderArgs &a, const GeometryStateView &g, const BinningStateView &b,

@@ -51,15 +51,25 @@ __device__ __forceinline__ bool ecc_in_range(float ecc) { return __float_as_uint
 // (the backward walks the list back to front; lane 0 is then the entry farthest back).
 // CAP = entries per batch (64; 32 = every batch is ONE pass of the 32-row table and no record is gathered twice -- measured in round 5,
 // profiles/r05_notes.md: the extra block culls cost what the re-gathers save).
-template <bool DESC, int CAP = 64>
-__device__ __forceinline__ void stream_refill(uint32_t &id, int &pos, int &n, const uint32_t *__restrict__ list, int &cursor, int end, int qbit, int lane)
+// NIB (the 2D kernels' default front end): the candidate's sorted tile KEY is loaded beside its value; bits [qbit, qbit + 4) of it are the block
+// mask of this quadrant (ts2d_support.h: qbit = 16 + 4 * quadrant).  An entry is kept when the nibble is not zero, and the nibble travels with
+// the id through the one permutation, in the four bits above it: id = triangle | nibble << TS_ID_BITS.
+template <bool DESC, int CAP = 64, bool NIB = false>
+__device__ __forceinline__ void stream_refill(uint32_t &id, int &pos, int &n, const uint32_t *__restrict__ list, int &cursor, int end, int qbit, int lane,
+                                              const uint32_t *__restrict__ keys = nullptr)
 {
     while (n < CAP && (DESC ? cursor > 0 : cursor < end))
     {
         const int k = DESC ? cursor - 1 - lane : cursor + lane;
         const bool valid = DESC ? k >= 0 : k < end;
-        const uint32_t v = valid ? list[k] : 0u;
-        const bool want = valid && ((v >> qbit) & 1u);
+        uint32_t v = 0u, key = 0u;
+        if (valid) // one branch: the two loads are in flight together
+        {
+            v = list[k];
+            if (NIB) key = keys[k];
+        }
+        const uint32_t nib = NIB ? (key << (TS_ID_BITS - qbit)) & ~TS_ID_MASK : 0u; // already where it travels
+        const bool want = NIB ? nib != 0u : valid && ((v >> qbit) & 1u);
         unsigned long long mt = ballot(want);
         int adv = 64;
         const int room = CAP - n;
@@ -74,7 +84,7 @@ __device__ __forceinline__ void stream_refill(uint32_t &id, int &pos, int &n, co
         if (mt == 0) continue;
         const int cnt = __popcll(mt), rk = lane_rank(mt);
         const int dest = (taken ? n + rk : n + cnt + (lane - rk)) & 63; // a permutation of the 64 lanes
-        const uint32_t pid = (uint32_t)__builtin_amdgcn_ds_permute(dest << 2, (int)(v & TS_ID_MASK));
+        const uint32_t pid = (uint32_t)__builtin_amdgcn_ds_permute(dest << 2, (int)((v & TS_ID_MASK) | nib));
         const int ppos = __builtin_amdgcn_ds_permute(dest << 2, k);
         const bool fresh = lane >= n && lane < n + cnt;
         id = fresh ? pid : id;

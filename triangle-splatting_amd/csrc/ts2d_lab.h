@@ -47,6 +47,10 @@ void ts2d_lab_depth_split(int mode, int bucket_cap); // mode 0: the product's ch
  * always passes).  The masks are pure culling of work that contributes nothing, so every output must be what it is with them on:
  * tests/test_qmask_gpu.py compares the two, bit for bit where the arithmetic is ordered. */
 void ts2d_lab_force_all_quadrants(int on);
+/* on != 0: the 2D blend kernels of later forwards and backwards in this library run their second instantiation, which culls every entry
+ * against the quadrant's four 4x4 blocks itself (render_group.hip: block_cull) -- what the product runs on grids of more than 65 535 tiles --
+ * instead of reading the block masks the emission kernel left in the tile keys.  tests/test_blockmask_gpu.py compares the two in one build. */
+void ts2d_lab_force_kernel_cull(int on);
 
 #ifdef __cplusplus
 }

@@ -2,6 +2,10 @@
 // and the emission kernel, binning.hip) and the QUADRANT MASK of an instance: which of the four 8x8 quadrants of a 16x16 tile
 // the support can reach.  The emission kernel stores the mask in the four spare bits of the instance's value (triangle id < 2^28); a quadrant
 // wave of the blend kernels then gathers and culls only the entries whose bit is set (36 % of a tile's list on the headline scene).
+// The 2D variant goes one level further down: the BLOCK MASK of an instance says which of the tile's sixteen 4x4 blocks the support can reach.
+// It is the blend kernels' own block cull (render_group.hip: block_cull), made once per instance at emission instead of once per quadrant wave
+// in the forward and once more in the backward, and it travels in bits 16..31 of the instance's tile key (grids of at most 65 535 tiles; the
+// tile sort looks at the low bits only).  The quadrant mask is then the OR of the four nibbles.
 #pragma once
 #include "ts2d_wave.h"
 
@@ -32,14 +36,17 @@ struct QuadSetup
 {
     float v1x, v1y, v2x, v2y, v3x, v3y, ia;
     float A1, B1, A2, B2, A3, B3;
-    float P1, P2, P3; // max(0, 7 A) + max(0, 7 B) - m + the part of the rounding margin that does not depend on the tile
+    float P1, P2, P3; // max(0, 7 A) + max(0, 7 B) - m + the part of the rounding margin that does not depend on the tile (7 = BOX)
     float bminx, bmaxx, bminy, bmaxy;
     bool live;
 };
 // pad_px: an extra acceptance margin in pixels on the three edge tests (0 for the 2D variant, whose per-pixel test IS the fp32 evaluation of
 // these barycentrics; the 3D variant's per-pixel test goes through the ray / plane intersection, whose rounding it has to cover)
+// BOX: the sample box's extent, 7 for the quadrant masks (8x8), 3 for a setup that block_mask / quad_anchor + block_mask_affine use (4x4)
+template <int BOX = 7>
 __device__ __forceinline__ QuadSetup quad_setup(float v1x, float v1y, float v2x, float v2y, float v3x, float v3y, float E, float pad_px = 0.0f)
 {
+    constexpr float box = (float)BOX;
     QuadSetup q;
     q.v1x = v1x; q.v1y = v1y; q.v2x = v2x; q.v2y = v2y; q.v3x = v3x; q.v3y = v3y;
     const float area2 = __fsub_rn(__fmul_rn(v2x - v1x, v3y - v1y), __fmul_rn(v2y - v1y, v3x - v1x)); // as the blend kernels form it
@@ -50,9 +57,9 @@ __device__ __forceinline__ QuadSetup quad_setup(float v1x, float v1y, float v2x,
     const float m = (1.0f - E) * (1.0f / 3.0f); // ecc <= E  <=>  min_k a_k >= m
     // rounding of the slopes (2 ulp) times sample offsets up to 15; the tile-dependent part is added in quadrant_mask
     const float slope_margin = 2e-6f * 15.0f + pad_px;
-    q.P1 = fmaxf(0.0f, 7.0f * q.A1) + fmaxf(0.0f, 7.0f * q.B1) - m + slope_margin * (fabsf(q.A1) + fabsf(q.B1));
-    q.P2 = fmaxf(0.0f, 7.0f * q.A2) + fmaxf(0.0f, 7.0f * q.B2) - m + slope_margin * (fabsf(q.A2) + fabsf(q.B2));
-    q.P3 = fmaxf(0.0f, 7.0f * q.A3) + fmaxf(0.0f, 7.0f * q.B3) - m + slope_margin * (fabsf(q.A3) + fabsf(q.B3));
+    q.P1 = fmaxf(0.0f, box * q.A1) + fmaxf(0.0f, box * q.B1) - m + slope_margin * (fabsf(q.A1) + fabsf(q.B1));
+    q.P2 = fmaxf(0.0f, box * q.A2) + fmaxf(0.0f, box * q.B2) - m + slope_margin * (fabsf(q.A2) + fabsf(q.B2));
+    q.P3 = fmaxf(0.0f, box * q.A3) + fmaxf(0.0f, box * q.B3) - m + slope_margin * (fabsf(q.A3) + fabsf(q.B3));
     const float cx = (v1x + v2x + v3x) * (1.0f / 3.0f), cy = (v1y + v2y + v3y) * (1.0f / 3.0f);
     const float e1x = E * (v1x - cx), e2x = E * (v2x - cx), e3x = E * (v3x - cx);
     const float e1y = E * (v1y - cy), e2y = E * (v2y - cy), e3y = E * (v3y - cy);
@@ -136,6 +143,61 @@ __device__ __forceinline__ uint32_t quadrant_mask(const QuadSetup &q, float TX, 
     return m;
 }
 
+// ---- block masks (2D variant) ------------------------------------------------------------------------------------------------------------------
+// Bit 4 q + g = the support can reach a pixel of block g = (gy << 1 | gx) of quadrant q = (qy << 1 | qx): the 4x4 block at (TX + 8 qx + 4 gx,
+// TY + 8 qy + 4 gy) -- g in the order of block_cull's ov[].  The test is block_cull's: the bounding box of the scaled triangle with its pad, and
+// the three edge normals against the 4x4 sample box, with the margins of the quadrant test above (they bound the rounding of the blend kernels'
+// products, of the reciprocal and of the slopes times sample offsets up to 15, whatever the box).  k_e = edge e's acceptance value for the block
+// at the tile's origin.  The edge terms are separable: block (i, j) passes edge e iff (k_e + 4 i A_e) + 4 j B_e >= 0, compared as
+// k_e + 4 i A_e >= -4 j B_e (four x terms, four y terms per edge, no rounding in the last step).  tools/sim/blockmask_model.py replays this
+// against the per-pixel test (tests/test_blockmask_model_cpu.py).
+// One edge at a time (eight live values instead of twenty-four: the emission kernel has no registers to spare): bit b of the result = the
+// block of mask bit b passes edge (k, A, B).
+__device__ __forceinline__ uint32_t block_edge_bits(float k, float A, float B)
+{
+    const float x0 = k, x1 = fmaf(4.0f, A, k), x2 = fmaf(8.0f, A, k), x3 = fmaf(12.0f, A, k);
+    const float y1 = -4.0f * B, y2 = -8.0f * B, y3 = -12.0f * B;
+    // columns that pass in row j, as the bits of quadrant-row 0 / block-row 0: column i -> bit (i >> 1) * 4 + (i & 1)
+    const uint32_t c0 = (x0 >= 0.0f ? 0x01u : 0u) | (x1 >= 0.0f ? 0x02u : 0u) | (x2 >= 0.0f ? 0x10u : 0u) | (x3 >= 0.0f ? 0x20u : 0u);
+    const uint32_t c1 = (x0 >= y1 ? 0x01u : 0u) | (x1 >= y1 ? 0x02u : 0u) | (x2 >= y1 ? 0x10u : 0u) | (x3 >= y1 ? 0x20u : 0u);
+    const uint32_t c2 = (x0 >= y2 ? 0x01u : 0u) | (x1 >= y2 ? 0x02u : 0u) | (x2 >= y2 ? 0x10u : 0u) | (x3 >= y2 ? 0x20u : 0u);
+    const uint32_t c3 = (x0 >= y3 ? 0x01u : 0u) | (x1 >= y3 ? 0x02u : 0u) | (x2 >= y3 ? 0x10u : 0u) | (x3 >= y3 ? 0x20u : 0u);
+    return c0 | (c1 << 2) | (c2 << 8) | (c3 << 10); // row j -> + (j >> 1) * 8 + (j & 1) * 2
+}
+__device__ __forceinline__ uint32_t block_bits(float k1, float k2, float k3, float A1, float A2, float A3, float B1, float B2, float B3, float bminx,
+                                               float bmaxx, float bminy, float bmaxy, float TX, float TY)
+{
+    // the bounding box: columns (as bits of row 0) and rows (as bits of column 0) it reaches, spread over the mask by two multiplications
+    uint32_t cols = 0, rows = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+    {
+        cols |= (bminx <= TX + (float)(4 * i + 3) && bmaxx >= TX + (float)(4 * i)) ? 1u << ((i >> 1) * 4 + (i & 1)) : 0u;
+        rows |= (bminy <= TY + (float)(4 * i + 3) && bmaxy >= TY + (float)(4 * i)) ? 1u << ((i >> 1) * 8 + (i & 1) * 2) : 0u;
+    }
+    uint32_t m = (cols * 0x0505u) & (rows * 0x0033u); // cols * (1 + 4 + 256 + 1024): every row; rows * (1 + 2 + 16 + 32): every column
+    if (m) m &= block_edge_bits(k1, A1, B1);
+    if (m) m &= block_edge_bits(k2, A2, B2);
+    if (m) m &= block_edge_bits(k3, A3, B3);
+    return m;
+}
+// Per tile, like quadrant_mask: the constants evaluated at the tile's own origin.
+__device__ __forceinline__ uint32_t block_mask(const QuadSetup &q, float TX, float TY)
+{
+    const float u1x = q.v1x - TX, u1y = q.v1y - TY, u2x = q.v2x - TX, u2y = q.v2y - TY, u3x = q.v3x - TX, u3y = q.v3y - TY;
+    const float t1a = u2x * u3y, t1b = u2y * u3x, t2a = u3x * u1y, t2b = u3y * u1x, aia = fabsf(q.ia);
+    const float C1 = (t1a - t1b) * q.ia, C2 = (t2a - t2b) * q.ia;
+    const float C3 = 1.0f - C1 - C2;
+    const float r1 = 4e-7f * (fabsf(t1a) + fabsf(t1b)) * aia, r2 = 4e-7f * (fabsf(t2a) + fabsf(t2b)) * aia;
+    const float k1 = C1 + q.P1 + r1, k2 = C2 + q.P2 + r2, k3 = C3 + q.P3 + (r1 + r2 + 4e-7f); // a setup with BOX = 3
+    return block_bits(k1, k2, k3, q.A1, q.A2, q.A3, q.B1, q.B2, q.B3, q.live ? q.bminx : 3e38f, q.live ? q.bmaxx : -3e38f, q.bminy, q.bmaxy, TX, TY);
+}
+// The quadrant mask that goes with a block mask: the OR of its nibbles.
+__device__ __forceinline__ uint32_t quadrants_of_blocks(uint32_t m)
+{
+    return ((m & 0x000Fu) ? 1u : 0u) | ((m & 0x00F0u) ? 2u : 0u) | ((m & 0x0F00u) ? 4u : 0u) | ((m & 0xF000u) ? 8u : 0u);
+}
+
 // ---- the same test, affine over a triangle's tile rectangle (round 5: one setup per TRIANGLE instead of one per instance) -----------------
 // C_k is affine in the tile origin: C_k(TX0 + dx, TY0 + dy) = C_k(TX0, TY0) + A_k dx + B_k dy.  quad_anchor evaluates the constants once at
 // the rectangle's first tile; quadrant_mask_affine then needs two FMAs per edge and no gather.  What the affine step adds in rounding goes into
@@ -146,6 +208,7 @@ __device__ __forceinline__ uint32_t quadrant_mask(const QuadSetup &q, float TX, 
 //     6e-7 (|A_k| Wpx + |B_k| Hpx) + 2.5e-7 |C_k(anchor)| covers both.
 // 16 dwords per triangle: K1 K2 K3 A1 | A2 A3 B1 B2 | B3 bminx bmaxx bminy | bmaxy id (minx | miny << 16) spare.  A dead triangle (E <= 0) gets
 // an empty bounding box.  Pinned by tools/sim/qmask_model.py (tests/test_qmask_model_cpu.py) against the per-pixel test, like quadrant_mask.
+// From a setup with BOX = 3 (quad_setup<3>) the same sixteen dwords serve block_mask_affine.
 struct QuadAffine { float4 a, b, c, d; };
 __device__ __forceinline__ QuadAffine quad_anchor(const QuadSetup &q, uint32_t id, uint32_t minx, uint32_t miny, uint32_t w, uint32_t h)
 {
@@ -184,5 +247,13 @@ __device__ __forceinline__ uint32_t quadrant_mask_affine(const QuadAffine &o, ui
     m |= (x0 && y1 && k1 + by1 >= 0.0f && k2 + by2 >= 0.0f && k3 + by3 >= 0.0f) ? 4u : 0u;
     m |= (x1 && y1 && k1 + ax1 + by1 >= 0.0f && k2 + ax2 + by2 >= 0.0f && k3 + ax3 + by3 >= 0.0f) ? 8u : 0u;
     return m;
+}
+// the anchor of a setup with BOX = 3
+__device__ __forceinline__ uint32_t block_mask_affine(const QuadAffine &o, uint32_t dx, uint32_t dy, uint32_t x, uint32_t y)
+{
+    const float fx = (float)(dx * TS_TILE), fy = (float)(dy * TS_TILE), TX = (float)(x * TS_TILE), TY = (float)(y * TS_TILE);
+    const float A1 = o.a.w, A2 = o.b.x, A3 = o.b.y, B1 = o.b.z, B2 = o.b.w, B3 = o.c.x;
+    const float k1 = fmaf(B1, fy, fmaf(A1, fx, o.a.x)), k2 = fmaf(B2, fy, fmaf(A2, fx, o.a.y)), k3 = fmaf(B3, fy, fmaf(A3, fx, o.a.z));
+    return block_bits(k1, k2, k3, A1, A2, A3, B1, B2, B3, o.c.y, o.c.z, o.c.w, o.d.x, TX, TY);
 }
 } // namespace

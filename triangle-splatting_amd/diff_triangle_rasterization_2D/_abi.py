@@ -165,6 +165,7 @@ LAB_SIGNATURES = {
     "ts2d_test_quantile": (C.c_int, [_vp, C.c_size_t, C.c_float, _vp, _vp, _vp]),
     "ts2d_lab_depth_split": (None, [C.c_int, C.c_int]),
     "ts2d_lab_force_all_quadrants": (None, [C.c_int]),
+    "ts2d_lab_force_kernel_cull": (None, [C.c_int]),
 }
 
 # include/ts_geom.h: the whole C ABI of diff_recon_hip/libts_geom.so, a library of its own (diff_recon_hip/mesh_distance.py loads and binds it)

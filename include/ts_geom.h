@@ -4,7 +4,7 @@
  * completeness / Chamfer / precision / recall / F-score on the two, and RawTriangle's set difference on the first.
  *
  * A library of its own, beside libts2d.so: the entry points of libts2d.so are a closed list.  libts_geom.so links
- * the same radix sort (csrc/binning.hip) and the same front half of the box searches (csrc/ts_knn_front.h) and keeps its own error text.
+ * the same radix sort (csrc/radix_sort.hip) and the same front half of the box searches (csrc/ts_knn_front.h) and keeps its own error text.
  * The error codes are ts2d.h's.
  *
  * All pointers are device pointers; everything is enqueued on `stream` (a hipStream_t); no call allocates or synchronises with the host.

@@ -16,7 +16,7 @@ import helpers  # noqa: E402
 import synthetic  # noqa: E402
 from diff_triangle_rasterization_2D import _C  # noqa: E402
 
-STAGE, SMALL, SB = 2048, 32, 256  # csrc/binning.hip: scan_emit_kernel
+STAGE, SMALL, SB = 2048, 32, 256  # csrc/emit.hip: scan_emit_kernel
 
 
 def world_of_pixel(s, px, py, zv):

@@ -22,7 +22,7 @@ if FORCE_TICKETS:
 
 out = []
 if os.environ.get("LAB_DEPTH_ORDER") == "1":
-    # the one-launch depth order of small scenes (binning.hip: depth_order_small_kernel) has its own census, its own fourth-pass rule and
+    # the one-launch depth order of small scenes (depth_order.hip: depth_order_small_kernel) has its own census, its own fourth-pass rule and
     # its own block sums.  Same scene through the three forms -- one launch (the product's path up to 12 288 triangles), the multi-launch ticket-free
     # passes (reached through ts2d_lab_force_depth_pass4) and the hierarchical ticket passes (ts2d_lab_force_ticket_passes): the depth permutation,
     # the instance offsets (= block sums + scan), the instance count and the sorted instance list must be IDENTICAL.
@@ -52,7 +52,7 @@ if os.environ.get("LAB_DEPTH_ORDER") == "1":
     print("LAB_RESULT " + json.dumps(out))
     sys.exit(0)
 if os.environ.get("LAB_DEPTH_SPLIT") == "1":
-    # Round 6: the depth order of mid-sized scenes by sampled splitters + per-bucket sorts in LDS (binning.hip: depth_split_* / depth_bucket_sort_kernel,
+    # Round 6: the depth order of mid-sized scenes by sampled splitters + per-bucket sorts in LDS (depth_order.hip: depth_split_* / depth_bucket_sort_kernel,
     # the product's path between 12 288 and 500 000 triangles; here up to the 1.6 M it supports) against the LSD passes (ts2d_lab_depth_split(1, 0)) and against itself
     # with a per-bucket register capacity of 512 pairs (ts2d_lab_depth_split(2, 512): every ordinary bucket takes the kernel's global-memory
     # path).  Depth permutation, instance offsets (= tiles in depth order + block sums + scan), instance count, sorted instance list and image

@@ -1,4 +1,4 @@
-"""The hand-written binning primitives (csrc/binning.hip) against AMD's rocPRIM on the same arrays and against numpy:
+"""The hand-written binning primitives (csrc/radix_sort.hip, depth_order.hip, emit.hip) against AMD's rocPRIM on the same arrays and against numpy:
 stable LSD radix sort of (key, value) pairs (replaces cub::DeviceRadixSort::SortPairs, R2D/src/rasterizer.cu:210-218) and the
 tile-count prefix sum (replaces cub::DeviceScan::InclusiveSum, :186), bit for bit."""
 import ctypes as C
@@ -84,7 +84,7 @@ def test_instance_offsets_match_rocprim_scan(P, W, H):
 @pytest.mark.parametrize("P", [1, 63, 64, 65, 1000, 1024, 1025, 4097, 10_000, 12_287, 12_288, 12_289, 20_000])
 @pytest.mark.parametrize("spread", [False, True])
 def test_depth_order_of_small_scenes_is_the_stable_sort(P, spread):
-    """Up to 12 288 triangles ONE launch orders the triangles (binning.hip: depth_order_small_kernel -- one workgroup, the pairs in registers, LDS
+    """Up to 12 288 triangles ONE launch orders the triangles (depth_order.hip: depth_order_small_kernel -- one workgroup, the pairs in registers, LDS
     between the passes) and leaves what the census and the block-sum launch leave at larger sizes; above, the multi-launch sort.  Either way:
     ids in (depth bits, id) order = numpy's stable argsort of the keys (culled triangles carry key 0), offsets = the running sum of the tile
     counts in that order, N = its last value.  `spread`: depths over a factor > 4, so the top key byte varies and the fourth pass runs."""
@@ -127,7 +127,7 @@ def test_tiny_scene_in_recycled_state_buffers(P, variant):
 
 def test_last_arrival_handoffs_under_uneven_load():
     """Every block-to-block hand-off of the binning kernels (per-slab / per-pass prefixes of the radix sort, the scan's block sums: write-through
-    stores, a drained ticket, sc1 loads in the last-arriving block -- a gfx950 hardware contract, binning.hip) repeated under UNEVEN load:
+    stores, a drained ticket, sc1 loads in the last-arriving block -- a gfx950 hardware contract, ts2d_radix.h) repeated under UNEVEN load:
     a second stream keeps some CUs busy with streaming copies and matrix products while sorts of several sizes run back to back on
     the first, so that producers and the elected consumer meet on busy and idle CUs, same and different XCDs, warm and cold L1s.
     Every result is compared bit for bit against numpy's stable sort; 60 sorts x up to 6 passes x 2 hand-off levels."""

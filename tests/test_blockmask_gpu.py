@@ -47,7 +47,7 @@ def test_masks_from_the_keys_equal_the_in_kernel_cull(results, name):
 
 
 def test_the_scenes_cover_what_they_are_meant_to(results):
-    """Each emission path (csrc/binning.hip: scan_emit_kernel) is taken by thousands of instances in the scene named for it, one of them through
+    """Each emission path (csrc/emit.hip: scan_emit_kernel) is taken by thousands of instances in the scene named for it, one of them through
     runs beyond the 2048-entry stage; a view that culls part of its scene; quadrant lists longer than the 32-row table (second pass)."""
     r = results
     assert r["small_staged"]["staged"] == r["small_staged"]["num_rendered"] and r["small_staged"]["largest_run"] <= 2048, r["small_staged"]

@@ -39,7 +39,7 @@ def test_unknown_units_are_refused():
 
 @pytest.mark.parametrize("lab", [False, True])
 def test_variant_objects_replace_exactly_the_named_units(lab):
-    extra = {"render_group_bwd": ["-DTS2D_STATS"], "binning": EXTRA}
+    extra = {"render_group_bwd": ["-DTS2D_STATS"], "depth_order": EXTRA}
     if lab:
         extra["lab/lab_hooks"] = ["-DNDEBUG"]
     product, variant = build.objects(lab), build.objects(lab, "x", extra)

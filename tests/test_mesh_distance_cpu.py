@@ -132,6 +132,14 @@ def test_library_exports_exactly_the_header(geom_path):
     assert "libts_geom.so" in soname and "libts2d.so" not in soname
 
 
+def test_library_registers_the_radix_sort_and_none_of_the_rasterizer_binning_kernels(geom_path):
+    names = open(geom_path, "rb").read()  # the kernel names the library registers with the runtime are strings of the file
+    assert b"rs_scatter_kernel" in names
+    for kernel in (b"scan_emit_kernel", b"tile_ranges_kernel", b"gather_blocksum_kernel", b"depth_order_small_kernel", b"depth_bucket_sort_kernel",
+                   b"depth_split_"):
+        assert kernel not in names, kernel
+
+
 def test_ctypes_table_matches_the_header_name_for_name_and_in_arity():
     declared = _header_prototypes()
     assert set(declared) == set(GEOM_SIGNATURES)
@@ -149,7 +157,8 @@ def test_build_tables_name_the_units_and_flags():
     assert "-ffp-contract=off" in build.GEOM_SOURCES["mesh_distance.hip"]
     cmd = build.geom_command("mesh_distance", cc="hipcc")
     assert cmd[:1 + len(build.COMMON)] == ["hipcc", *build.COMMON] and "-ffp-contract=off" in cmd and "-fvisibility=hidden" in cmd
-    assert build.geom_objects() == [os.path.join(build.OBJ_DIR, n + ".o") for n in ("mesh_distance", "api_geom", "binning")]
+    assert build.geom_objects() == [os.path.join(build.OBJ_DIR, n + ".o") for n in ("mesh_distance", "api_geom", "radix_sort")]
+    assert not {os.path.join(build.OBJ_DIR, n + ".o") for n in ("depth_order", "emit")} & set(build.geom_objects())  # the rasterizer's own binning units
     assert "mesh_distance" not in build.units() and "api_geom" not in build.units()  # libts2d.so links neither
     stamp = open(os.path.join(build.OBJ_DIR, "mesh_distance.o.cmd")).read()  # what the object on disk was compiled with
     assert "-ffp-contract=off" in stamp

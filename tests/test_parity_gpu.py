@@ -243,7 +243,7 @@ def test_forced_ticket_passes_match_oracle():
 
 
 def test_one_launch_depth_order_equals_the_multi_launch_forms():
-    """up to 12 288 triangles ONE launch (binning.hip: depth_order_small_kernel) replaces the depth sort's eight launches and the block-sum
+    """up to 12 288 triangles ONE launch (depth_order.hip: depth_order_small_kernel) replaces the depth sort's eight launches and the block-sum
     launch, with its own census and its own rule for the skipped fourth pass.  P = 1, 63, 64, 65, 1023, 12 287, 12 288 (the limit), 12 289 (first scene
     past it) and two all-culled scenes through the one-launch form, the ticket-free multi-launch passes and the hierarchical ticket passes (lab
     switches, tests/lab_worker.py): depth permutation, instance offsets, num_rendered, the sorted instance list and the image are identical."""

@@ -1,5 +1,5 @@
 // lab_hooks.hip -- tools/bin/libts2d_lab.so only (csrc/ts2d_lab.h): the sort / scan test hooks and their rocPRIM comparators.
-// The product library links no rocPRIM; the hand-written passes under test are the product's own objects (binning.hip), reached
+// The product library links no rocPRIM; the hand-written passes under test are the product's own objects (radix_sort.hip), reached
 // through the same internal entry point that knn.hip uses.
 #pragma GCC visibility push(default)
 #include "ts2d_lab.h"

@@ -1,5 +1,5 @@
 """Builds libts2d.so (the C-ABI HIP library of include/ts2d.h) for gfx950 with hipcc, in-tree, the package's binding of it, and
-libts_geom.so (include/ts_geom.h: the mesh-distance library of diff_recon_hip, GEOM_SOURCES + the product's own binning object).
+libts_geom.so (include/ts_geom.h: the mesh-distance library of diff_recon_hip, GEOM_SOURCES + the product's own radix_sort object).
 
     python triangle-splatting_amd/build.py [--force] [--verbose] [--lab]
     python triangle-splatting_amd/build.py --variant TAG [--lab] [--all "FLAGS"] [--unit NAME="FLAGS" ...]
@@ -11,10 +11,11 @@ extension's dependency on libts2d.so is met by whichever of them _C.py loaded fi
 -DTS2D_LAB, which exports the switches and readers of csrc/ts2d_lab.h.  The product library contains one blend path per variant and reads no
 environment; only tools/ and tests/ load the lab library (TS2D_LIBRARY_PATH, see _C.py).
 --variant TAG builds an A/B or instrumentation variant instead: each unit named by --unit (an object name of objects(): render_group_fwd,
-lab/api, ...) is compiled with the product's own command line plus FLAGS into build/variants/TAG/; --all appends FLAGS to every unit (the lab
+depth_order, emit, lab/api, ...) is compiled with the product's own command line plus FLAGS into build/variants/TAG/; --all appends FLAGS to every unit (the lab
 units too with --lab).  Every other unit links the product's object.  Output: tools/bin/libts2d_TAG.so, with --lab also
 tools/bin/libts2d_lab_TAG.so (TS2D_LIBRARY_PATH / TS2D_LAB_LIBRARY_PATH); the product's libraries are not written.  E.g. the lane-group
-statistics build: --variant stats --lab --unit render_group_fwd=-DTS2D_STATS --unit render_group_bwd=-DTS2D_STATS.
+statistics build: --variant stats --lab --unit render_group_fwd=-DTS2D_STATS --unit render_group_bwd=-DTS2D_STATS; a depth-order switch-over
+under test: --variant split16 --unit depth_order=-DTS_DEPTH_SPLIT_MAX_VALUE=1600000; the emission's register budget: --unit emit=-DTS_EMIT_WAVES=5.
 hipcc cross-compiles without a GPU.  Per-file flags matter:
   * preprocess.hip is built with -ffp-contract=off (bit-comparable integer state, see the file header);
   * the blend kernels use the default fast contraction and hardware float atomics (-munsafe-fp-atomics).
@@ -59,7 +60,9 @@ SOURCES = {
     "knn.hip": [],
     "model_update.hip": [],
     "optim.hip": ["-ffp-contract=off"],
-    "binning.hip": [],
+    "radix_sort.hip": [],   # the binning, three units over csrc/ts2d_radix.h: the radix passes, the tile sort, the sort for other callers ...
+    "depth_order.hip": [],  # ... steps 1-2: the triangles in depth order, their tile counts, N ...
+    "emit.hip": [],         # ... steps 3 and 5: instance emission, tile ranges
     "select.hip": [],
     # the 2D blend kernels: ONE source, two translation units (TSG_PART), so that each kernel gets the machine-scheduler strategy it measured best
     # with (round 5, profiles/r05_sched_strategies.txt: max-ilp +1.3 % for the forward, -1 % for the backward; round 6: profiles/r06_blend_ab.txt)
@@ -79,12 +82,12 @@ GEOM_SOURCES = {  # libts_geom.so only (include/ts_geom.h): a second product lib
     "mesh_distance.hip": ["-ffp-contract=off"],  # cross-set nearest search and surface sampler: every fp32 / fp64 operation rounds
     "api_geom.hip": [],                          # its C ABI and its own error text (api.hip is not linked)
 }
-GEOM_SHARED = ["binning"]  # the product's own objects it links as well: the radix sort of the search's front half (no undefined project symbol)
+GEOM_SHARED = ["radix_sort"]  # the product's own objects it links as well: the radix sort of the search's front half (no undefined project symbol)
 GEOM_LIB = os.path.join(HERE, "diff_recon_hip", "libts_geom.so")
 BIN_DIR = os.path.join(os.path.dirname(HERE), "tools", "bin")
 LAB_LIB = os.path.join(BIN_DIR, "libts2d_lab.so")
 LAB_SRC = os.path.join(os.path.dirname(HERE), "tools", "lab")  # lab_hooks.hip: the test hooks, outside the product's csrc/; it includes csrc's headers (-I)
-HEADERS = ["ts2d_common.h", "ts2d_api.h", "ts_knn_front.h", "ts_weld_launch.h", "ts_geom_launch.h", "ts2d_lab.h", "ts2d_math.h", "ts2d_wave.h", "ts2d_group.h", "ts2d_support.h", "ts2d_sh.h", "ts2d_stage.h", "ts2d_preprocess_launch.h", "ts2d_imgops.h", "ts2d_select.h", "ts2d_tri.h", os.path.join("..", "..", "include", "ts2d.h"),
+HEADERS = ["ts2d_common.h", "ts2d_radix.h", "ts2d_api.h", "ts_knn_front.h", "ts_weld_launch.h", "ts_geom_launch.h", "ts2d_lab.h", "ts2d_math.h", "ts2d_wave.h", "ts2d_group.h", "ts2d_support.h", "ts2d_sh.h", "ts2d_stage.h", "ts2d_preprocess_launch.h", "ts2d_imgops.h", "ts2d_select.h", "ts2d_tri.h", os.path.join("..", "..", "include", "ts2d.h"),
            os.path.join("..", "..", "include", "ts_loss.h"),
            os.path.join("..", "..", "include", "ts_knn.h"),
            os.path.join("..", "..", "include", "ts_model.h"),

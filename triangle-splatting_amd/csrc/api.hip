@@ -389,7 +389,7 @@ int ts_order_instances(uint32_t flags, int P, int grid_x, int ntiles, const Geom
     else ts_launch_zero_words((uint32_t *)im.ranges, 2 * (size_t)ntiles, s); // no triangles: nobody else clears the ranges (a kernel: see ts2d_backward)
     if (N > 0)
     {
-        { ProfScope ps("tile_sort", s); ts_sort_pairs(b, N, n_dev, ntiles, s); } // tile bits only, see binning.hip
+        { ProfScope ps("tile_sort", s); ts_sort_pairs(b, N, n_dev, ntiles, s); } // tile bits only, see radix_sort.hip
         TS_CHECK(flags, s, "tile_sort");
         { ProfScope ps("tile_ranges", s); ts_launch_tile_ranges(N, n_dev, ntiles, b, im, s); }
         TS_CHECK(flags, s, "tile_ranges");

@@ -84,7 +84,7 @@ __global__ void __launch_bounds__(256) mask_count_kernel(int P, const uint8_t *_
     const int nblocks = gridDim.x;
     if (t == 0)
     {
-        // same hand-off as binning.hip's last_arrival(): write-through store, drained, then the ticket; sc1 loads in the elected block --
+        // same hand-off as ts2d_radix.h's last_arrival(): write-through store, drained, then the ticket; sc1 loads in the elected block --
         // a gfx950 hardware contract (MI355X_MICROARCH.md "valid forms"), checked for the target at the top of this file
         __hip_atomic_store(blocksum + blockIdx.x, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

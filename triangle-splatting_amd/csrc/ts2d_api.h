@@ -38,7 +38,7 @@ struct ProfScope
     ~ProfScope();
 };
 
-// Early read-back of the instance count (binning.hip, count_instances_kernel): a pinned host word + an event per call in flight
+// Early read-back of the instance count (ts2d_radix.h, publish_instance_count): a pinned host word + an event per call in flight
 struct EarlyCount
 {
     unsigned long long *host = nullptr;

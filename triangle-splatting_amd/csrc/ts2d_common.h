@@ -35,7 +35,7 @@
 //   [0..5] dL/dv{1,2,3}_2D   [6] dL/dopacity   [7..9] dL/drgb   [10..12] dL/dnormal_view   [13..15] dL/dv_depth
 #define TS_GRAD_FLOATS 16
 
-// Scratch of one stable LSD radix pass over n (key, value) pairs (binning.hip): per-chunk digit counts, their per-slab
+// Scratch of one stable LSD radix pass over n (key, value) pairs (ts2d_radix.h): per-chunk digit counts, their per-slab
 // and per-digit prefixes.  One chunk = consecutive pairs handled by one workgroup; one slab = 64 chunks.  The chunk length is a property
 // of the sort, picked from its size: 4096 pairs for instance lists of millions (longer digit runs = better coalesced scatter stores; keys and
 // values through one staging array), 1024 for everything up to 2.5 M pairs -- such a sort is a few hundred to a few thousand workgroups that
@@ -55,14 +55,14 @@ static inline int ts_depth_chunk(size_t n) { return n <= (size_t)TS_RS_SMALL_BEL
 #define TS_RS_BINS 256
 #define TS_RS_TICKET_EXTRA 8 /* words behind the per-slab tickets; [slabs + 4] = the depth sort's top_const flag.  (The census of the depth sort's
                                 first histogram needs no words here: its per-chunk sums / key-bit ORs / ANDs borrow g.blocksum, g.tiles_sorted and
-                                g.offsets, which the scan rewrites afterwards -- binning.hip, ts_sort_by_depth_begin.) */
+                                g.offsets, which the scan rewrites afterwards -- depth_order.hip, ts_sort_by_depth_begin.) */
 struct RadixScratchView
 {
     uint32_t *table;   // chunks x 256   count of digit d in chunk c, then (in place) its exclusive prefix inside the slab
     uint32_t *slabtot; // slabs x 256    per-slab totals, then (in place) their exclusive prefix over the slabs
     uint32_t *binbase; // 256            exclusive prefix of the digit totals
     uint32_t *tickets; // TS_RS_TICKETS  "last block finishes" tickets: [0] pass, [1] scan blocks, [2 + slab] per slab; zero between launches
-    uint32_t *slabacc[2]; // slabs x 256 each: per-slab digit totals of the ticket-free passes (binning.hip, rs_hist_direct_kernel), accumulated
+    uint32_t *slabacc[2]; // slabs x 256 each: per-slab digit totals of the ticket-free passes (ts2d_radix.h, rs_hist_direct_kernel), accumulated
                           // with atomics; pass p uses [p & 1], and whoever runs before it has cleared that buffer
     int chunks, slabs;
     int chunk; // pairs per chunk: TS_RS_CHUNK, TS_RS_CHUNK_MID or TS_RS_CHUNK_SMALL
@@ -79,7 +79,7 @@ struct GeometryStateView
     uint32_t *depth_sorted;  //     = sk[1]: depth keys in ascending order (after the 4th pass)
     uint32_t *perm;          //     = sv[1]: triangle ids in (depth, id) order after the 4th pass
     uint32_t *top_const;     // device flag (one of the sort's scratch words, cleared with the tickets): the visible triangles' depth keys share
-                             // their top byte, the 4th pass was skipped and the order is in sk[0] / sv[0] (binning.hip, sorted_ids())
+                             // their top byte, the 4th pass was skipped and the order is in sk[0] / sv[0] (ts2d_radix.h, sorted_ids())
     uint32_t *tiles_sorted;  // P   tiles_touched[perm[i]]
     uint32_t *offsets;       // P   inclusive prefix sum of tiles_sorted: instance slots of the i-th nearest triangle
     uint64_t *blocksum;      // ceil(P / 1024) + 2   raw per-block sums of tiles_sorted; [nblocks] = N (scratch of the depth sort's census before that)
@@ -185,7 +185,7 @@ static inline size_t ts_carve_binning(char *base, int64_t N, int32_t W, int32_t 
     ts_carve(p, v.k[1], n);
     ts_carve(p, v.v[0], n);
     ts_carve(p, v.v[1], n);
-    v.passes = (ts_tile_bits(gx * gy) + 7) / 8; // tile bits only (see binning.hip)
+    v.passes = (ts_tile_bits(gx * gy) + 7) / 8; // tile bits only (see ts2d_radix.h)
     v.tile = v.k[v.passes & 1];
     v.vals = v.v[v.passes & 1];
     ts_carve_radix(p, n, v.rs, ts_instance_chunk(n), TS_RS_CHUNK_SMALL);
@@ -242,7 +242,8 @@ struct PreprocessArgs
 };
 
 void ts_launch_preprocess_fwd(const PreprocessArgs &a, int32_t *radii, const GeometryStateView &g, hipStream_t s);
-// binning.hip -- every step hand-written for gfx950 (the round-1 rocPRIM calls survive only as test comparators)
+// depth_order.hip, emit.hip, radix_sort.hip (what they share: ts2d_radix.h) -- every step hand-written for gfx950 (the round-1 rocPRIM calls
+// survive only as test comparators)
 void ts_sort_by_depth_begin(const GeometryStateView &g, int32_t P, unsigned long long *host_out, hipStream_t s); // first histogram + N + key-bit census
 void ts_sort_by_depth_finish(const GeometryStateView &g, int32_t P, hipStream_t s);          // the rest: (depth bits, id) -> sorted ids
 void ts_scan_offsets(const GeometryStateView &g, int32_t P, hipStream_t s);                  // tiles_sorted, block sums + their groups' sums
@@ -259,20 +260,20 @@ struct QuadMaskArgs
     float inv_W, inv_H; // 1 / W, 1 / H (the 3D setup's pixel -> ray conversions; the masks' margins absorb their rounding)
     int blocks;         // 1: variant 2 on a grid of at most TS_BLOCKMASK_MAX_TILES tiles -- block masks in bits 16..31 of the tile keys
 };
-void ts_launch_zero_words(uint32_t *p, size_t n, hipStream_t s); // binning.hip
+void ts_launch_zero_words(uint32_t *p, size_t n, hipStream_t s); // radix_sort.hip
 void ts_launch_emit_keys(int P, int grid_x, int ntiles, const GeometryStateView &g, const BinningStateView &b, const ImageStateView &im,
                          float *contrib_sum, float *contrib_max, int64_t capacity, int32_t *status, const QuadMaskArgs &qm, hipStream_t s); // offsets + instances (+ output clears); capacity < 0: synchronous path
-const unsigned long long *ts_instance_count_dev(const GeometryStateView &g, int P);                        // where the scan leaves N
-void ts_sort_pairs(const BinningStateView &b, int64_t N, const unsigned long long *n_dev, int ntiles, hipStream_t s); // stable, tile bits only
+const unsigned long long *ts_instance_count_dev(const GeometryStateView &g, int P);                        // emit.hip: where the scan leaves N
+void ts_sort_pairs(const BinningStateView &b, int64_t N, const unsigned long long *n_dev, int ntiles, hipStream_t s); // radix_sort.hip: stable, tile bits only
 void ts_launch_tile_ranges(int64_t N, const unsigned long long *n_dev, int ntiles, const BinningStateView &b, const ImageStateView &im, hipStream_t s);
 size_t ts_quantile_scratch_bytes();                                                               // select.hip: torch.quantile of non-negative floats by radix select
 void ts_quantile_threshold(const uint32_t *keys, size_t n, float q, void *scratch, float *thr, hipStream_t s);
 void ts_quantile_passes(const uint32_t *keys, size_t n, float q, void *scratch, int first_pass, hipStream_t s); // for callers that weave the select into their own kernels (ts2d_select.h)
 size_t ts_quantile_state_words();
-size_t ts_radix_scratch_bytes(size_t n);                                                          // the same sort for other callers (knn.hip)
+size_t ts_radix_scratch_bytes(size_t n);                                                          // radix_sort.hip: the same sort for other callers (knn.hip)
 int ts_radix_sort_pairs(uint32_t *const k[2], uint32_t *const v[2], size_t n, int end_bit, void *scratch, hipStream_t s, bool force_tickets = false);
-void ts_force_ticket_passes(bool on); // lab library only (csrc/ts2d_lab.h): no exported entry point of the product library reaches it
-void ts_force_depth_pass4(bool on);   // likewise
+void ts_force_ticket_passes(bool on); // radix_sort.hip; lab library only (csrc/ts2d_lab.h): no exported entry point of the product library reaches it
+void ts_force_depth_pass4(bool on);   // depth_order.hip; likewise, and the next one
 void ts_lab_depth_split(int mode, int bucket_cap); // mode 1: never the sampled-splitter depth order, 2: up to 1.6 M triangles; bucket_cap > 0: its per-bucket register capacity
 
 struct RenderArgs

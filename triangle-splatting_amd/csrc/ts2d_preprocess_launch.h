@@ -14,7 +14,7 @@
 
 namespace ts
 {
-// The binning kernels' "last block finishes" tickets (binning.hip) are zeroed by the first launch of the step.  Every grid has at
+// The binning kernels' "last block finishes" tickets (ts2d_radix.h) are zeroed by the first launch of the step.  Every grid has at
 // least 64 threads and slabs + TS_RS_TICKET_EXTRA <= max(P, 64), so the threads beyond P of a tiny scene take part.  The slab totals of the
 // depth sort's first (ticket-free) histogram and the group sums of the scan are cleared here as well.
 __device__ __forceinline__ void clear_tickets(const GeometryStateView &g, int idx, int P)
@@ -22,7 +22,7 @@ __device__ __forceinline__ void clear_tickets(const GeometryStateView &g, int id
     if (idx < g.rs.slabs + TS_RS_TICKET_EXTRA) g.rs.tickets[idx] = 0u;
     const int nthreads = (int)(gridDim.x * blockDim.x);
     for (int k = idx; k < g.rs.slabs * TS_RS_BINS; k += nthreads) g.rs.slabacc[0][k] = 0u;
-    const int groups = (((P + 1023) >> 10) + 63) >> 6; // the scan's second level (binning.hip): one sum per 64 scan blocks of 1024 triangles
+    const int groups = (((P + 1023) >> 10) + 63) >> 6; // the scan's second level (depth_order.hip): one sum per 64 scan blocks of 1024 triangles
     for (int k = idx; k < groups + 1; k += nthreads) g.supersum[k] = 0ull;
 }
 

@@ -1,5 +1,5 @@
 // ts2d_support.h -- where a 2D triangle's window can reach: the scale of its support (shared by the blend kernels' block cull, render_group.hip,
-// and the emission kernel, binning.hip) and the QUADRANT MASK of an instance: which of the four 8x8 quadrants of a 16x16 tile
+// and the emission kernel, emit.hip) and the QUADRANT MASK of an instance: which of the four 8x8 quadrants of a 16x16 tile
 // the support can reach.  The emission kernel stores the mask in the four spare bits of the instance's value (triangle id < 2^28); a quadrant
 // wave of the blend kernels then gathers and culls only the entries whose bit is set (36 % of a tile's list on the headline scene).
 // The 2D variant goes one level further down: the BLOCK MASK of an instance says which of the tile's sixteen 4x4 blocks the support can reach.

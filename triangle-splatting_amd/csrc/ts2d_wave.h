@@ -1,4 +1,4 @@
-// ts2d_wave.h -- wave64 building blocks of the 2D and 3D blend kernels (gfx950): the wave-order LDS fence (binning.hip uses it too), DPP lane
+// ts2d_wave.h -- wave64 building blocks of the 2D and 3D blend kernels (gfx950): the wave-order LDS fence (ts2d_radix.h uses it too), DPP lane
 // moves, a fast power of non-negative floats, XCD-aware tile mapping.
 // Costs measured on MI355X (profiles/r01_valu_microbench.txt): DPP add 4.5, plain VOP2 fp32 2.6, v_exp/v_rcp 8.3 cycles per wave instruction.
 #pragma once

@@ -165,7 +165,7 @@ KnnCarve knn_carve(void *ws, int P)
     c.boxes = (Box *)take((size_t)c.nboxes * sizeof(Box));
     c.partial = (Box *)take((size_t)c.npartial * sizeof(Box));
     c.bbox = (Box *)take(sizeof(Box));
-    c.sort_temp_bytes = ts_radix_scratch_bytes(n); // the hand-written radix sort of binning.hip
+    c.sort_temp_bytes = ts_radix_scratch_bytes(n); // the hand-written radix sort of radix_sort.hip
     c.sort_temp = take(c.sort_temp_bytes);
     c.bytes = (size_t)(p - (char *)ws);
     return c;

@@ -27,6 +27,9 @@ A "ground truth" is rendered from a hidden set of triangles from several cameras
     python examples/train_synthetic.py --eval-mesh --eval-geometry N
                                                         then compare N surface samples of the model's front faces with N of the hidden target
                                                         triangles (diff_recon_hip.mesh_distance): accuracy, completeness, Chamfer, F-score
+    python examples/train_synthetic.py --eval-mesh --eval-surface N
+                                                        the same scores measured sample to SURFACE (diff_recon_hip.mesh_surface_distance): N samples
+                                                        of each mesh against the triangles of the other, free of the sampling spacing
 """
 import argparse
 import math
@@ -198,7 +201,7 @@ def train(rasterizer="2D", iters=200, triangles=20000, width=256, height=192, se
     return [float(x) for x in torch.stack(losses).cpu()], m, sec
 
 
-def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, height=192, seed=0, views=2, refine=False, weld=None, geometry=None):
+def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, height=192, seed=0, views=2, refine=False, weld=None, geometry=None, surface=None):
     """PSNR / SSIM of the model's opaque mesh -- mesh_from_triangles: one colour per face from the DC coefficients, back faces as reversed
     twins, the soup saveGLB writes -- against the hidden targets of train() called with the same arguments (diff_recon_hip.evaluate_mesh).
     refine: the result also holds "refined", the same scores (plus "kept" and "triangles") of the mesh after a census over these views
@@ -209,7 +212,9 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
     mesh it was welded from.  The renderer culls nothing, so the front faces alone draw what the soup with its back twins draws.
     geometry = N: the result also holds "geometry": diff_recon_hip.mesh_distance between N surface samples of the model's front faces and N of
     the hidden target triangles (the scene of train() called with the same arguments) -- accuracy, completeness, Chamfer and the F-score at
-    0.5, 1 and 2 times the target's median edge length ("median_edge")."""
+    0.5, 1 and 2 times the target's median edge length ("median_edge").
+    surface = N: the result also holds "surface": the same dictionary from diff_recon_hip.mesh_surface_distance, every sample measured against
+    the other mesh's TRIANGLES instead of its samples."""
     _, _, cams, gts, kw, _, _ = _setup(rasterizer, iters, triangles, width, height, seed, views, 0.0, False, False)
     for cam, gt in zip(cams, gts):
         cam.gt_image = gt
@@ -229,23 +234,28 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
         res["welded"] = dict(D.evaluate_mesh(cams, w.vertices, w.faces, w.faces_color, bg_color=kw["bg_color"]), stats=w.stats,
                              topology=D.mesh_topology(w.stats["num_vertices"], w.faces), eps=float(weld),
                              soup={k: soup[k] for k in ("mean_psnr", "mean_ssim")})
-    if geometry is not None:
+    if geometry is not None or surface is not None:
         target = torch.from_numpy(np.ascontiguousarray(synthetic.scene(triangles, width, height, 2, seed=seed, edge_px=10.0)["vertex"])).to(m._vertex.device)
         edges = (target - target.roll(1, dims=1)).norm(dim=2)  # the hidden scene of _setup: every draw comes from the seeded generator
         median_edge = float(edges.median())
         soup_of = lambda tri: (tri.detach().reshape(-1, 3), torch.arange(3 * tri.shape[0], device=tri.device, dtype=torch.int32).reshape(-1, 3))
-        res["geometry"] = dict(D.mesh_distance(soup_of(m._vertex), soup_of(target), int(geometry), seed=seed,
-                                               thresholds=[0.5 * median_edge, median_edge, 2.0 * median_edge]), median_edge=median_edge)
+        thresholds = [0.5 * median_edge, median_edge, 2.0 * median_edge]
+        if geometry is not None:
+            res["geometry"] = dict(D.mesh_distance(soup_of(m._vertex), soup_of(target), int(geometry), seed=seed, thresholds=thresholds),
+                                   median_edge=median_edge)
+        if surface is not None:
+            res["surface"] = dict(D.mesh_surface_distance(soup_of(m._vertex), soup_of(target), int(surface), seed=seed, thresholds=thresholds),
+                                  median_edge=median_edge)
     return res
 
 
-def geometry_report(g):
-    """The lines --eval-geometry prints for mesh_scores(...)["geometry"]."""
-    return [f"mesh geometry, {g['a_count']} + {g['b_count']} surface samples (areas: model {g['area_a']:.4g}, target {g['area_b']:.4g}): accuracy {g['accuracy']:.4g}, "
+def geometry_report(g, title="mesh geometry"):
+    """The lines --eval-geometry prints for mesh_scores(...)["geometry"]; --eval-surface prints the same for ["surface"] under its own title."""
+    return [f"{title}, {g['a_count']} + {g['b_count']} surface samples (areas: model {g['area_a']:.4g}, target {g['area_b']:.4g}): accuracy {g['accuracy']:.4g}, "
             f"completeness {g['completeness']:.4g}, Chamfer {g['chamfer']:.4g}, Hausdorff {g['hausdorff']:.4g}",
-            f"mesh geometry, target's median edge {g['median_edge']:.4g}: F-score " +
+            f"{title}, target's median edge {g['median_edge']:.4g}: F-score " +
             ", ".join(f"{f:.4f} at {k:g} edges" for k, f in zip((0.5, 1, 2), g["fscore"])),
-            "mesh geometry, precision / recall: " + ", ".join(f"{p:.4f} / {r:.4f} at {k:g} edges" for k, p, r in zip((0.5, 1, 2), g["precision"], g["recall"]))]
+            f"{title}, precision / recall: " + ", ".join(f"{p:.4f} / {r:.4f} at {k:g} edges" for k, p, r in zip((0.5, 1, 2), g["precision"], g["recall"]))]
 
 
 def weld_report(welded):
@@ -406,7 +416,14 @@ if __name__ == "__main__":
     ap.add_argument("--eval-geometry", type=int, default=None, metavar="N", help="with --eval-mesh: compare N surface samples of the model's front faces with N of the hidden "
                                                                                    "target triangles (diff_recon_hip.mesh_distance) and print accuracy, completeness, "
                                                                                    "Chamfer and the F-score at 0.5, 1 and 2 times the target's median edge length")
+    ap.add_argument("--eval-surface", type=int, default=None, metavar="N", help="with --eval-mesh: measure N surface samples of the model's front faces against the TRIANGLES "
+                                                                                  "of the hidden target and N of the target against the model's "
+                                                                                  "(diff_recon_hip.mesh_surface_distance) and print the scores of --eval-geometry")
     a = ap.parse_args()
+    if a.eval_surface is not None and not a.eval_mesh:
+        ap.error("--eval-surface measures the mesh that --eval-mesh scores")
+    if a.eval_surface is not None and a.eval_surface < 1:
+        ap.error("--eval-surface needs at least one sample")
     if a.eval_geometry is not None and not a.eval_mesh:
         ap.error("--eval-geometry measures the mesh that --eval-mesh scores")
     if a.eval_geometry is not None and a.eval_geometry < 1:
@@ -425,7 +442,8 @@ if __name__ == "__main__":
         print("  update", row)
     print(f"{a.rasterizer}: loss {losses[0]:.5f} -> {losses[-1]:.5f} in {a.iters} iterations, {sec * 1e3:.2f} ms/iteration (incl. Python)")
     if a.eval_mesh:
-        res = mesh_scores(m, a.rasterizer, a.iters, a.triangles, views=a.views, refine=a.refine_mesh, weld=a.weld_mesh, geometry=a.eval_geometry)
+        res = mesh_scores(m, a.rasterizer, a.iters, a.triangles, views=a.views, refine=a.refine_mesh, weld=a.weld_mesh, geometry=a.eval_geometry,
+                          surface=a.eval_surface)
         for v, (p_, s_) in enumerate(zip(res["psnr"], res["ssim"])):
             print(f"  opaque mesh, view {v}: PSNR {p_:.2f} dB  SSIM {s_:.4f}")
         print(f"opaque mesh of {m._vertex.shape[0]} triangles: mean PSNR {res['mean_psnr']:.2f} dB, mean SSIM {res['mean_ssim']:.4f} over {len(res['psnr'])} views")
@@ -438,4 +456,7 @@ if __name__ == "__main__":
                 print(line)
         if a.eval_geometry is not None:
             for line in geometry_report(res["geometry"]):
+                print(line)
+        if a.eval_surface is not None:
+            for line in geometry_report(res["surface"], title="mesh surface"):
                 print(line)

@@ -16,7 +16,17 @@ allocator included):
 
 and reads each search's (workgroup, ref box) visits from the library's counter in a run of its own.  Writes, and prints as one JSON line,
 the median block time of every part with the slowest and fastest block, the visits and the ratios to the yardstick.  Needs a HIP device;
-there is no fallback."""
+there is no fallback.
+
+    python tools/bench_mesh_distance.py --surface [--points 1000000 --faces 1000000 ... --out profiles/mesh_surface.json]
+
+times the point-to-SURFACE query instead (diff_recon_hip.mesh_surface over csrc/mesh_bvh.hip), the same way:
+
+    build            MeshBVH of the second height field (about --faces faces)
+    closest          MeshBVH.closest of --points surface samples of the first field against it
+    cross_surface    nearest_points between those samples and as many of the second field: the point-to-point search, as context
+
+and reads the (wave, leaf) visits of the query from the library's counter in a run of its own."""
 import argparse
 import json
 import os
@@ -46,8 +56,11 @@ def main():
     ap.add_argument("--blocks", type=int, default=10, help="alternating blocks per part")
     ap.add_argument("--iters", type=int, default=5, help="calls per block")
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mesh_distance.json"))
+    ap.add_argument("--surface", action="store_true", help="time the point-to-surface query (MeshBVH) instead")
+    ap.add_argument("--out", default=None, help="default: profiles/mesh_distance.json, with --surface profiles/mesh_surface.json")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "mesh_surface.json" if args.surface else "mesh_distance.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_mesh_distance.py needs a HIP device (the mesh scores have no CPU fallback)")
     dev = torch.device("cuda", 0)
@@ -76,12 +89,21 @@ def main():
     def summary(v):
         return {"ms": round(statistics.median(v), 4), "min_block_ms": round(min(v), 4), "max_block_ms": round(max(v), 4)}
 
-    parts = {
-        "cross_volume": lambda: nearest_points(vol_q, vol_r),
-        "cross_surface": lambda: nearest_points(surf_q, surf_r),
-        "sample": lambda: sample_mesh_surface(*mesh_a, P, seed=0),
-        "nearest_other": lambda: nearestNeighbor(vol_q, 1),
-    }
+    if args.surface:
+        from diff_recon_hip.mesh_surface import MeshBVH
+        bvh = MeshBVH(*mesh_b)
+        parts = {
+            "build": lambda: MeshBVH(*mesh_b),
+            "closest": lambda: bvh.closest(surf_q),
+            "cross_surface": lambda: nearest_points(surf_q, surf_r),
+        }
+    else:
+        parts = {
+            "cross_volume": lambda: nearest_points(vol_q, vol_r),
+            "cross_surface": lambda: nearest_points(surf_q, surf_r),
+            "sample": lambda: sample_mesh_surface(*mesh_a, P, seed=0),
+            "nearest_other": lambda: nearestNeighbor(vol_q, 1),
+        }
     for _ in range(args.warmup):
         for fn in parts.values():
             fn()
@@ -92,6 +114,30 @@ def main():
             times[k].append(block(fn, args.iters))
     out = {k: summary(v) for k, v in times.items()}
     print(", ".join(f"{k} {v['ms']:.3f} ms" for k, v in out.items()), file=sys.stderr, flush=True)
+
+    if args.surface:
+        visits = torch.zeros(1, device=dev, dtype=torch.int64)
+        _, d2, _ = bvh.closest(surf_q, visits)
+        torch.cuda.synchronize()
+        waves, leaves = (P + 63) // 64, (F + 7) // 8
+        out["closest"].update({"leaf_visits": int(visits.item()), "leaf_visits_per_wave": round(int(visits.item()) / waves, 2), "leaves": leaves,
+                               "mean_distance": float(d2.sqrt().mean().item()),
+                               "over_cross_surface": round(out["closest"]["ms"] / out["cross_surface"]["ms"], 3)})
+        result = {
+            "workload": f"{P} surface samples of an {n} x {n} height field against the {F} faces of the same field a phase of 0.02 apart; "
+                        f"cross_surface: the same samples against {P} samples of the second field (nearest_points)",
+            "method": f"{args.blocks} alternating blocks x {args.iters} calls of every part after {args.warmup} warm-up calls each, device events around "
+                      "each block; public wrappers (allocation of the index, outputs and workspaces included); leaf visits from the library's "
+                      "counter in a call of its own",
+            "parts": out,
+            "device": torch.cuda.get_device_name(dev),
+        }
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+        print(json.dumps(result))
+        return
 
     nboxes = (P + 1023) // 1024
     for name, (q, r) in (("cross_volume", (vol_q, vol_r)), ("cross_surface", (surf_q, surf_r))):

@@ -30,6 +30,9 @@ A "ground truth" is rendered from a hidden set of triangles from several cameras
     python examples/train_synthetic.py --eval-mesh --eval-surface N
                                                         the same scores measured sample to SURFACE (diff_recon_hip.mesh_surface_distance): N samples
                                                         of each mesh against the triangles of the other, free of the sampling spacing
+    python examples/train_synthetic.py --eval-mesh --eval-surface N --eval-visible
+                                                        those scores over the OBSERVED samples only: the ones that a training camera's centre sees
+                                                        past their own mesh (ray casts, diff_recon_hip.point_visibility); prints the hidden counts
 """
 import argparse
 import math
@@ -201,7 +204,8 @@ def train(rasterizer="2D", iters=200, triangles=20000, width=256, height=192, se
     return [float(x) for x in torch.stack(losses).cpu()], m, sec
 
 
-def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, height=192, seed=0, views=2, refine=False, weld=None, geometry=None, surface=None):
+def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, height=192, seed=0, views=2, refine=False, weld=None, geometry=None, surface=None,
+                visible=False):
     """PSNR / SSIM of the model's opaque mesh -- mesh_from_triangles: one colour per face from the DC coefficients, back faces as reversed
     twins, the soup saveGLB writes -- against the hidden targets of train() called with the same arguments (diff_recon_hip.evaluate_mesh).
     refine: the result also holds "refined", the same scores (plus "kept" and "triangles") of the mesh after a census over these views
@@ -214,7 +218,9 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
     the hidden target triangles (the scene of train() called with the same arguments) -- accuracy, completeness, Chamfer and the F-score at
     0.5, 1 and 2 times the target's median edge length ("median_edge").
     surface = N: the result also holds "surface": the same dictionary from diff_recon_hip.mesh_surface_distance, every sample measured against
-    the other mesh's TRIANGLES instead of its samples."""
+    the other mesh's TRIANGLES instead of its samples.
+    visible (with surface): only the samples that at least one training camera's centre sees past their own mesh are scored
+    (mesh_surface_distance(visible_from=...), ray casts on the mesh's own index); "a_hidden" / "b_hidden" count the samples left out."""
     _, _, cams, gts, kw, _, _ = _setup(rasterizer, iters, triangles, width, height, seed, views, 0.0, False, False)
     for cam, gt in zip(cams, gts):
         cam.gt_image = gt
@@ -244,18 +250,21 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
             res["geometry"] = dict(D.mesh_distance(soup_of(m._vertex), soup_of(target), int(geometry), seed=seed, thresholds=thresholds),
                                    median_edge=median_edge)
         if surface is not None:
-            res["surface"] = dict(D.mesh_surface_distance(soup_of(m._vertex), soup_of(target), int(surface), seed=seed, thresholds=thresholds),
-                                  median_edge=median_edge)
+            centres = torch.stack([cam.camera_center.reshape(3) for cam in cams]).to(m._vertex.device) if visible else None
+            res["surface"] = dict(D.mesh_surface_distance(soup_of(m._vertex), soup_of(target), int(surface), seed=seed, thresholds=thresholds,
+                                                          visible_from=centres), median_edge=median_edge)
     return res
 
 
 def geometry_report(g, title="mesh geometry"):
-    """The lines --eval-geometry prints for mesh_scores(...)["geometry"]; --eval-surface prints the same for ["surface"] under its own title."""
+    """The lines --eval-geometry prints for mesh_scores(...)["geometry"]; --eval-surface prints the same for ["surface"] under its own title, and
+    with --eval-visible one more: the samples no camera sees."""
+    hidden = [f"{title}, hidden from every camera centre and left out: {g['a_hidden']} samples of the model, {g['b_hidden']} of the target"] if "a_hidden" in g else []
     return [f"{title}, {g['a_count']} + {g['b_count']} surface samples (areas: model {g['area_a']:.4g}, target {g['area_b']:.4g}): accuracy {g['accuracy']:.4g}, "
             f"completeness {g['completeness']:.4g}, Chamfer {g['chamfer']:.4g}, Hausdorff {g['hausdorff']:.4g}",
             f"{title}, target's median edge {g['median_edge']:.4g}: F-score " +
             ", ".join(f"{f:.4f} at {k:g} edges" for k, f in zip((0.5, 1, 2), g["fscore"])),
-            f"{title}, precision / recall: " + ", ".join(f"{p:.4f} / {r:.4f} at {k:g} edges" for k, p, r in zip((0.5, 1, 2), g["precision"], g["recall"]))]
+            f"{title}, precision / recall: " + ", ".join(f"{p:.4f} / {r:.4f} at {k:g} edges" for k, p, r in zip((0.5, 1, 2), g["precision"], g["recall"]))] + hidden
 
 
 def weld_report(welded):
@@ -419,7 +428,11 @@ if __name__ == "__main__":
     ap.add_argument("--eval-surface", type=int, default=None, metavar="N", help="with --eval-mesh: measure N surface samples of the model's front faces against the TRIANGLES "
                                                                                   "of the hidden target and N of the target against the model's "
                                                                                   "(diff_recon_hip.mesh_surface_distance) and print the scores of --eval-geometry")
+    ap.add_argument("--eval-visible", action="store_true", help="with --eval-surface: score only the samples that at least one training camera's centre sees past their own "
+                                                                "mesh (ray casts, diff_recon_hip.point_visibility) and print how many were hidden")
     a = ap.parse_args()
+    if a.eval_visible and a.eval_surface is None:
+        ap.error("--eval-visible restricts the scores of --eval-surface")
     if a.eval_surface is not None and not a.eval_mesh:
         ap.error("--eval-surface measures the mesh that --eval-mesh scores")
     if a.eval_surface is not None and a.eval_surface < 1:
@@ -443,7 +456,7 @@ if __name__ == "__main__":
     print(f"{a.rasterizer}: loss {losses[0]:.5f} -> {losses[-1]:.5f} in {a.iters} iterations, {sec * 1e3:.2f} ms/iteration (incl. Python)")
     if a.eval_mesh:
         res = mesh_scores(m, a.rasterizer, a.iters, a.triangles, views=a.views, refine=a.refine_mesh, weld=a.weld_mesh, geometry=a.eval_geometry,
-                          surface=a.eval_surface)
+                          surface=a.eval_surface, visible=a.eval_visible)
         for v, (p_, s_) in enumerate(zip(res["psnr"], res["ssim"])):
             print(f"  opaque mesh, view {v}: PSNR {p_:.2f} dB  SSIM {s_:.4f}")
         print(f"opaque mesh of {m._vertex.shape[0]} triangles: mean PSNR {res['mean_psnr']:.2f} dB, mean SSIM {res['mean_ssim']:.4f} over {len(res['psnr'])} views")

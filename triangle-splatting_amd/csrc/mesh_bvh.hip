@@ -18,65 +18,16 @@
 // nearest is popped first.  At a leaf every lane evaluates D' of the leaf's faces for its own query; the faces' words are wave-uniform loads.
 // `best` is seeded from the leaf that holds the Morton code of the wave's mean query (binary search among the sorted face codes).
 //
-// Stack bound.  F <= 2^31 - 1 gives at most 2^28 leaves, so at most MAX_LEVELS = 11 levels (2^28, 2^25, ..., 2, 1 nodes).  A pop removes one
-// entry and pushes at most FAN children of the level below; leaves push nothing.  By induction the stack holds at most 1 + (FAN - 1) entries
-// per inner level on the current path: STACK = 1 + (FAN - 1) (MAX_LEVELS - 1) = 71, whatever the data.
-#include "ts_knn_front.h"
+// Stack bound.  STACK = 1 + (FAN - 1) (MAX_LEVELS - 1) = 71 entries, whatever the data: the argument stands with the layout, in ts_bvh_layout.h.
+#include "ts_bvh_layout.h" // LEAF, FAN, MAX_LEVELS, STACK, Leaf, BvhView, bvh_view: shared with the ray query (mesh_ray.hip)
 #include "ts_bvh_launch.h"
 
 #include <algorithm>
 
 namespace
 {
-constexpr int LEAF = 8, FAN = 8, FAN_SHIFT = 3;
-constexpr int MAX_LEVELS = 11;
-constexpr int STACK = 1 + (FAN - 1) * (MAX_LEVELS - 1);
 constexpr int WAVES = TPB / 64;
 constexpr uint32_t CODE_INELIGIBLE = 0x40000000u; // above every 30-bit Morton code
-
-struct Leaf
-{
-    float v[LEAF][9];
-    int32_t id[LEAF];
-};
-
-// ---- layout --------------------------------------------------------------------------------------------------------------------------
-struct BvhView
-{
-    Box *bbox;       // of the eligible centroids
-    uint32_t *codes; // F sorted codes
-    Leaf *leaves;    // nleaves
-    Box *nodes;      // every level, level 0 (the leaves' boxes) first
-    int nleaves, nlevels;
-    int count[MAX_LEVELS];
-    size_t offset[MAX_LEVELS]; // of a level's first node in `nodes`
-    size_t bytes;
-};
-
-BvhView bvh_view(void *base, int F)
-{
-    BvhView v;
-    const size_t n = (size_t)(F > 0 ? F : 0);
-    v.nleaves = (int)((n + LEAF - 1) / LEAF);
-    v.nlevels = 0;
-    size_t total = 0;
-    for (int c = v.nleaves; c > 0; c = (c + FAN - 1) >> FAN_SHIFT)
-    {
-        v.count[v.nlevels] = c;
-        v.offset[v.nlevels] = total;
-        total += (size_t)c;
-        v.nlevels++;
-        if (c == 1) break;
-    }
-    char *p = (char *)base;
-    auto take = [&](size_t bytes) { char *q = p; p += ts_align_up(bytes); return q; };
-    v.bbox = (Box *)take(sizeof(Box));
-    v.codes = (uint32_t *)take(n * 4);
-    v.leaves = (Leaf *)take((size_t)v.nleaves * sizeof(Leaf));
-    v.nodes = (Box *)take(total * sizeof(Box));
-    v.bytes = (size_t)(p - (char *)base);
-    return v;
-}
 
 struct BuildCarve
 {

@@ -45,13 +45,16 @@
     mesh_surface.py       MeshBVH (a bounding-volume hierarchy over the triangles of a mesh; .closest: the exact nearest face, squared distance
                           and closest point of every query, float64), point_to_mesh_distance, mesh_surface_distance (the scores of
                           mesh_distance measured sample to SURFACE: identical surfaces score 0, not the sample spacing)
+    mesh_ray.py           ray_cast (the exact first hit of every ray on a MeshBVH: face, t, barycentric weights, side; watertight, equal to brute
+                          force bit for bit), camera_rays (the pixel-centre rays of a view; t is MeshRenderer's depth), point_visibility (how many
+                          centres see a point past the mesh; behind mesh_surface_distance(visible_from=...)) -- loaded on first use
     metrics.py            psnr, ssim (= 1 - SSIMLoss) and evaluate_mesh: PSNR / SSIM of a mesh's opaque render against each view's gt_image
                           (reference: src/diff_recon/trainers/trainer_utils.py:331-336, VanillaTS_trainer.py:156-190)
     graphed.py            GraphedStep: a whole training step (sync-free forward, loss, backward, optimizer) captured once into a HIP graph and
                           replayed with one launch -- no counterpart in the reference, whose forward reads num_rendered back every step
 
 Native code: libts2d.so (include/ts_loss.h, include/ts_model.h, include/ts_optim.h, include/ts2d.h, include/ts_mesh.h, include/ts_weld.h) and, for
-mesh_distance.py, libts_geom.so beside this file (include/ts_geom.h), for mesh_surface.py, libts_bvh.so (include/ts_bvh.h).  No CPU / eager fallback anywhere.
+mesh_distance.py, libts_geom.so beside this file (include/ts_geom.h), for mesh_surface.py, libts_bvh.so (include/ts_bvh.h), for mesh_ray.py, libts_ray.so (include/ts_ray.h).  No CPU / eager fallback anywhere.
 """
 from .losses import L1, SSIMLoss, ssimLoss, PhotometricLoss, photometric_loss, DepthNormalLoss, DoGLoss, SmoothnessLoss, dogLoss, smoothnessLoss, downsample_bilinear, downsample_bilinear_many  # noqa: F401
 from .triangle_renderer import TriangleRenderer  # noqa: F401
@@ -72,3 +75,14 @@ from .mesh_weld import WeldedMesh, weld_mesh, mesh_topology  # noqa: F401
 from .mesh_distance import SurfaceSamples, nearest_points, face_areas, sample_mesh_surface, point_cloud_distance, mesh_distance  # noqa: F401
 from .mesh_surface import MeshBVH, point_to_mesh_distance, mesh_surface_distance  # noqa: F401
 from .metrics import psnr, ssim, evaluate_mesh  # noqa: F401
+
+_RAY_NAMES = ("RayHits", "ray_cast", "camera_rays", "point_visibility")
+
+
+def __getattr__(name):
+    # mesh_ray.py and its library (libts_ray.so) are loaded on first use: without that library everything else here, MeshBVH.closest included, still works
+    if name in _RAY_NAMES or name == "mesh_ray":
+        import importlib
+        module = importlib.import_module(".mesh_ray", __name__)
+        return module if name == "mesh_ray" else getattr(module, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

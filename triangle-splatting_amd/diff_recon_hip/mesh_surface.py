@@ -1,9 +1,11 @@
 """Exact point-to-SURFACE distance on the device: a bounding-volume hierarchy over the triangles of a mesh, and the scores built on it.
 
-    MeshBVH(vertices, faces, keep=None)                 the index of a mesh, built once; .closest(queries) -> (face, dist2, point)
+    MeshBVH(vertices, faces, keep=None)                 the index of a mesh, built once; .closest(queries) -> (face, dist2, point);
+                                                        .ray_cast(origins, directions) -> the first hit of every ray (mesh_ray.py)
     point_to_mesh_distance(points, (vertices, faces))   the same in one call
-    mesh_surface_distance((va, fa), (vb, fb), samples, seed=0, thresholds=())
-                                                        accuracy / completeness / Chamfer / Hausdorff / precision / recall / F-score, sample to surface
+    mesh_surface_distance((va, fa), (vb, fb), samples, seed=0, thresholds=(), visible_from=None)
+                                                        accuracy / completeness / Chamfer / Hausdorff / precision / recall / F-score, sample to surface;
+                                                        with visible_from = (C, 3) centres over the samples that some centre sees (mesh_ray.py)
 
 mesh_distance.mesh_distance measures point to POINT: both surfaces are sampled and two identical surfaces score about half the sample
 spacing.  Here the samples of one mesh are measured against the triangles of the other, so identical surfaces score 0 (up to the fp32
@@ -114,6 +116,12 @@ class MeshBVH:
                                         ws.data_ptr(), ws.numel(), _native.stream()), "MeshBVH.closest")
         return face, dist2, point
 
+    def ray_cast(self, origins: torch.Tensor, directions: torch.Tensor, **kwargs):
+        """mesh_ray.ray_cast(self, origins, directions, ...): the first hit of every ray.  The module and its library (libts_ray.so) are
+        loaded here, on the first call: `closest` needs neither."""
+        from .mesh_ray import ray_cast
+        return ray_cast(self, origins, directions, **kwargs)
+
 
 def point_to_mesh_distance(points: torch.Tensor, mesh) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """MeshBVH(*mesh).closest(points) for mesh = (vertices, faces) or (vertices, faces, keep); a MeshBVH is taken as it is."""
@@ -131,7 +139,8 @@ def _mean(x: torch.Tensor) -> float:
     return float(x.sum().item()) / x.numel() if x.numel() else float("nan")
 
 
-def mesh_surface_distance(mesh_a, mesh_b, samples: int, seed: int = 0, thresholds: Sequence[float] = ()) -> Dict[str, object]:
+def mesh_surface_distance(mesh_a, mesh_b, samples: int, seed: int = 0, thresholds: Sequence[float] = (),
+                          visible_from: Optional[torch.Tensor] = None) -> Dict[str, object]:
     """Scores between the candidate mesh_a = (vertices, faces) and the ground truth mesh_b: `samples` surface points of a, drawn with `seed`,
     against the SURFACE of b, and as many of b, drawn with `seed + 1`, against the surface of a.  The keys are mesh_distance's:
 
@@ -140,13 +149,26 @@ def mesh_surface_distance(mesh_a, mesh_b, samples: int, seed: int = 0, threshold
         hausdorff      the largest of all those distances (of the samples: a lower bound of the surfaces')
         a_count / b_count, a_dropped / b_dropped, thresholds, precision, recall, fscore, a_within, b_within, area_a, area_b
 
+    visible_from: a (C, 3) tensor of viewing centres (the camera centres of the captured views).  The samples of each mesh are then restricted,
+    before they are scored, to those that at least one centre sees past their OWN mesh (mesh_ray.point_visibility): the faces buried inside a
+    triangle soup stop counting in accuracy and precision.  a_hidden / b_hidden count the samples left out, a_count / b_count what remains.
+    With None the result is what it was without the parameter, bit for bit, and has no such keys.
+
     Pass FRONT faces only, as for mesh_distance."""
     from .mesh_distance import sample_mesh_surface
     (va, fa), (vb, fb) = mesh_a, mesh_b
     sa = sample_mesh_surface(va, fa, samples, seed)
     sb = sample_mesh_surface(vb, fb, samples, int(seed) + 1)
-    face_ab, d2_ab, _ = MeshBVH(vb, fb).closest(sa.points)
-    face_ba, d2_ba, _ = MeshBVH(va, fa).closest(sb.points)
+    bvh_a, bvh_b = MeshBVH(va, fa), MeshBVH(vb, fb)
+    pa, pb = sa.points, sb.points
+    hidden = None
+    if visible_from is not None:
+        from .mesh_ray import point_visibility
+        seen_a, seen_b = point_visibility(bvh_a, pa, visible_from) > 0, point_visibility(bvh_b, pb, visible_from) > 0
+        hidden = (int((~seen_a).sum().item()), int((~seen_b).sum().item()))
+        pa, pb = pa[seen_a], pb[seen_b]
+    face_ab, d2_ab, _ = bvh_b.closest(pa)
+    face_ba, d2_ba, _ = bvh_a.closest(pb)
     sq_a, da, a_dropped = _one_way(d2_ab, face_ab)
     sq_b, db, b_dropped = _one_way(d2_ba, face_ba)
     accuracy, completeness = _mean(da), _mean(db)
@@ -155,6 +177,8 @@ def mesh_surface_distance(mesh_a, mesh_b, samples: int, seed: int = 0, threshold
            "a_count": int(da.numel()), "b_count": int(db.numel()), "a_dropped": a_dropped, "b_dropped": b_dropped,
            "thresholds": [float(t) for t in thresholds], "precision": [], "recall": [], "fscore": [], "a_within": [], "b_within": [],
            "area_a": sa.area, "area_b": sb.area}
+    if hidden is not None:
+        res["a_hidden"], res["b_hidden"] = hidden
     for tau in res["thresholds"]:
         na, nb = int((da <= tau).sum().item()), int((db <= tau).sum().item())
         p = na / da.numel() if da.numel() else 0.0

@@ -1,5 +1,5 @@
 """The C ABI of libts2d.so as ctypes sees it, declared once: the mirrors of the structs of include/*.h and the signature of every function
-they declare (and of the lab library's additions, csrc/ts2d_lab.h, and of the other two product libraries: libts_geom.so, include/ts_geom.h, and libts_bvh.so, include/ts_bvh.h).  Pure ctypes: no torch, no library is loaded here -- `_C.py` binds the
+they declare (and of the lab library's additions, csrc/ts2d_lab.h, and of the other three product libraries: libts_geom.so, include/ts_geom.h, libts_bvh.so, include/ts_bvh.h, and libts_ray.so, include/ts_ray.h).  Pure ctypes: no torch, no library is loaded here -- `_C.py` binds the
 library the package loads, the CPU tests bind a CDLL of their own.  tests/test_cabi_cpu.py holds both tables against the headers: the structs
 by sizeof / offsetof, the functions prototype by prototype.
 
@@ -188,6 +188,27 @@ BVH_SIGNATURES = {
     "tsb_closest_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "tsb_closest": (C.c_int, [C.c_int32, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
 }
+
+
+# include/ts_ray.h: the whole C ABI of diff_recon_hip/libts_ray.so, the fourth library (diff_recon_hip/mesh_ray.py loads and binds it)
+RAY_SIGNATURES = {
+    "tsr_last_error": (C.c_char_p, []),
+    "tsr_cast_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "tsr_cast": (C.c_int, [C.c_int32, _vp, _vp, _vp, C.c_double, C.c_double, C.c_int32, C.c_int32, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp,
+                           C.c_size_t, _vp]),
+}
+
+
+def bind_ray(lib):
+    """Sets restype and argtypes of every function of include/ts_ray.h on `lib` (a ctypes.CDLL of libts_ray.so); a library that lacks one is
+    refused."""
+    missing = [name for name in RAY_SIGNATURES if not hasattr(lib, name)]
+    if missing:
+        raise ImportError(f"{getattr(lib, '_name', lib)} does not export {', '.join(missing)}: rebuild it with `python triangle-splatting_amd/build.py`")
+    for name, (restype, argtypes) in RAY_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return lib
 
 
 def bind_bvh(lib):

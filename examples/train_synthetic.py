@@ -30,6 +30,10 @@ A "ground truth" is rendered from a hidden set of triangles from several cameras
     python examples/train_synthetic.py --eval-mesh --eval-surface N
                                                         the same scores measured sample to SURFACE (diff_recon_hip.mesh_surface_distance): N samples
                                                         of each mesh against the triangles of the other, free of the sampling spacing
+    python examples/train_synthetic.py --eval-mesh --extract-mesh RES
+                                                        fuse the training views' depth of that mesh into a TSDF volume of RES samples a side and
+                                                        extract one closed surface (diff_recon_hip.fuse_mesh); prints the topology of the soup
+                                                        against the fused mesh's and the surface distance between the two and to the target
     python examples/train_synthetic.py --eval-mesh --eval-surface N --eval-visible
                                                         those scores over the OBSERVED samples only: the ones that a training camera's centre sees
                                                         past their own mesh (ray casts, diff_recon_hip.point_visibility); prints the hidden counts
@@ -205,7 +209,7 @@ def train(rasterizer="2D", iters=200, triangles=20000, width=256, height=192, se
 
 
 def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, height=192, seed=0, views=2, refine=False, weld=None, geometry=None, surface=None,
-                visible=False):
+                visible=False, extract=None):
     """PSNR / SSIM of the model's opaque mesh -- mesh_from_triangles: one colour per face from the DC coefficients, back faces as reversed
     twins, the soup saveGLB writes -- against the hidden targets of train() called with the same arguments (diff_recon_hip.evaluate_mesh).
     refine: the result also holds "refined", the same scores (plus "kept" and "triangles") of the mesh after a census over these views
@@ -220,7 +224,10 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
     surface = N: the result also holds "surface": the same dictionary from diff_recon_hip.mesh_surface_distance, every sample measured against
     the other mesh's TRIANGLES instead of its samples.
     visible (with surface): only the samples that at least one training camera's centre sees past their own mesh are scored
-    (mesh_surface_distance(visible_from=...), ray casts on the mesh's own index); "a_hidden" / "b_hidden" count the samples left out."""
+    (mesh_surface_distance(visible_from=...), ray casts on the mesh's own index); "a_hidden" / "b_hidden" count the samples left out.
+    extract = RES: the result also holds "fused": diff_recon_hip.fuse_mesh of the front faces over these views at resolution RES -- the
+    "topology" of the fused mesh and of the "soup" (the front faces welded with eps = 0), "to_soup" = mesh_surface_distance between the two and
+    "to_target" = the same against the hidden target triangles (None for a fused mesh without faces)."""
     _, _, cams, gts, kw, _, _ = _setup(rasterizer, iters, triangles, width, height, seed, views, 0.0, False, False)
     for cam, gt in zip(cams, gts):
         cam.gt_image = gt
@@ -253,7 +260,30 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
             centres = torch.stack([cam.camera_center.reshape(3) for cam in cams]).to(m._vertex.device) if visible else None
             res["surface"] = dict(D.mesh_surface_distance(soup_of(m._vertex), soup_of(target), int(surface), seed=seed, thresholds=thresholds,
                                                           visible_from=centres), median_edge=median_edge)
+    if extract is not None:
+        soup_v, soup_f = m._vertex.detach().reshape(-1, 3), torch.arange(3 * m._vertex.shape[0], device=m._vertex.device, dtype=torch.int32).reshape(-1, 3)
+        target = torch.from_numpy(np.ascontiguousarray(synthetic.scene(triangles, width, height, 2, seed=seed, edge_px=10.0)["vertex"])).to(soup_v.device)
+        target_f = torch.arange(3 * target.shape[0], device=soup_v.device, dtype=torch.int32).reshape(-1, 3)
+        fused = D.fuse_mesh(cams, soup_v, soup_f, int(extract))
+        welded = D.weld_mesh(soup_v, soup_f, eps=0.0)
+        samples = int(surface) if surface is not None else 20000
+        some = fused.faces.shape[0] > 0
+        res["fused"] = dict(resolution=int(extract), topology=D.mesh_topology(fused.stats["num_vertices"], fused.faces),
+                            soup=D.mesh_topology(welded.stats["num_vertices"], welded.faces),
+                            to_soup=D.mesh_surface_distance((fused.vertices, fused.faces), (soup_v, soup_f), samples, seed=seed) if some else None,
+                            to_target=D.mesh_surface_distance((fused.vertices, fused.faces), (target.reshape(-1, 3), target_f), samples, seed=seed) if some else None)
     return res
+
+
+def fused_report(f):
+    """The three lines --extract-mesh prints for mesh_scores(...)["fused"]."""
+    t, s = f["topology"], f["soup"]
+    dist = lambda g: (f"accuracy {g['accuracy']:.4g}, completeness {g['completeness']:.4g}, Chamfer {g['chamfer']:.4g}, Hausdorff {g['hausdorff']:.4g}"
+                      if g is not None else "no surface was extracted")
+    return [f"fused mesh, resolution {f['resolution']}: {t['faces']} faces, {t['boundary']} boundary edges, {t['pieces']} pieces, Euler characteristic {t['euler']} "
+            f"(the soup: {s['faces']} faces, {s['boundary']} boundary edges, {s['pieces']} pieces, Euler characteristic {s['euler']})",
+            f"fused mesh against the soup: {dist(f['to_soup'])}",
+            f"fused mesh against the target: {dist(f['to_target'])}"]
 
 
 def geometry_report(g, title="mesh geometry"):
@@ -430,7 +460,14 @@ if __name__ == "__main__":
                                                                                   "(diff_recon_hip.mesh_surface_distance) and print the scores of --eval-geometry")
     ap.add_argument("--eval-visible", action="store_true", help="with --eval-surface: score only the samples that at least one training camera's centre sees past their own "
                                                                 "mesh (ray casts, diff_recon_hip.point_visibility) and print how many were hidden")
+    ap.add_argument("--extract-mesh", type=int, default=None, metavar="RES", help="with --eval-mesh: fuse the training views' depth of the mesh into a TSDF volume of RES samples "
+                                                                                    "along its longest side and extract one surface (diff_recon_hip.fuse_mesh); print its "
+                                                                                    "topology beside the soup's and its surface distance to the soup and to the target")
     a = ap.parse_args()
+    if a.extract_mesh is not None and not a.eval_mesh:
+        ap.error("--extract-mesh fuses the mesh of --eval-mesh")
+    if a.extract_mesh is not None and a.extract_mesh < 10:
+        ap.error("--extract-mesh needs a resolution of at least 10 (four voxels of padding either side)")
     if a.eval_visible and a.eval_surface is None:
         ap.error("--eval-visible restricts the scores of --eval-surface")
     if a.eval_surface is not None and not a.eval_mesh:
@@ -456,7 +493,7 @@ if __name__ == "__main__":
     print(f"{a.rasterizer}: loss {losses[0]:.5f} -> {losses[-1]:.5f} in {a.iters} iterations, {sec * 1e3:.2f} ms/iteration (incl. Python)")
     if a.eval_mesh:
         res = mesh_scores(m, a.rasterizer, a.iters, a.triangles, views=a.views, refine=a.refine_mesh, weld=a.weld_mesh, geometry=a.eval_geometry,
-                          surface=a.eval_surface, visible=a.eval_visible)
+                          surface=a.eval_surface, visible=a.eval_visible, extract=a.extract_mesh)
         for v, (p_, s_) in enumerate(zip(res["psnr"], res["ssim"])):
             print(f"  opaque mesh, view {v}: PSNR {p_:.2f} dB  SSIM {s_:.4f}")
         print(f"opaque mesh of {m._vertex.shape[0]} triangles: mean PSNR {res['mean_psnr']:.2f} dB, mean SSIM {res['mean_ssim']:.4f} over {len(res['psnr'])} views")
@@ -472,4 +509,7 @@ if __name__ == "__main__":
                 print(line)
         if a.eval_surface is not None:
             for line in geometry_report(res["surface"], title="mesh surface"):
+                print(line)
+        if a.extract_mesh is not None:
+            for line in fused_report(res["fused"]):
                 print(line)

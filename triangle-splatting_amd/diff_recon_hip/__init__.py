@@ -48,13 +48,17 @@
     mesh_ray.py           ray_cast (the exact first hit of every ray on a MeshBVH: face, t, barycentric weights, side; watertight, equal to brute
                           force bit for bit), camera_rays (the pixel-centre rays of a view; t is MeshRenderer's depth), point_visibility (how many
                           centres see a point past the mesh; behind mesh_surface_distance(visible_from=...)) -- loaded on first use
+    volume.py             TSDFVolume (per-view depth fused into a truncated signed distance volume held in integers: bit-identical in any view
+                          order, volumes add), extract_isosurface (marching tetrahedra on any fp32 grid: an oriented soup that weld_mesh(eps=0)
+                          closes) and fuse_mesh (MeshRenderer depth of many views -> one connected, closed mesh) -- no counterpart in the
+                          reference; loaded on first use
     metrics.py            psnr, ssim (= 1 - SSIMLoss) and evaluate_mesh: PSNR / SSIM of a mesh's opaque render against each view's gt_image
                           (reference: src/diff_recon/trainers/trainer_utils.py:331-336, VanillaTS_trainer.py:156-190)
     graphed.py            GraphedStep: a whole training step (sync-free forward, loss, backward, optimizer) captured once into a HIP graph and
                           replayed with one launch -- no counterpart in the reference, whose forward reads num_rendered back every step
 
 Native code: libts2d.so (include/ts_loss.h, include/ts_model.h, include/ts_optim.h, include/ts2d.h, include/ts_mesh.h, include/ts_weld.h) and, for
-mesh_distance.py, libts_geom.so beside this file (include/ts_geom.h), for mesh_surface.py, libts_bvh.so (include/ts_bvh.h), for mesh_ray.py, libts_ray.so (include/ts_ray.h).  No CPU / eager fallback anywhere.
+mesh_distance.py, libts_geom.so beside this file (include/ts_geom.h), for mesh_surface.py, libts_bvh.so (include/ts_bvh.h), for mesh_ray.py, libts_ray.so (include/ts_ray.h), for volume.py, libts_volume.so (include/ts_volume.h).  No CPU / eager fallback anywhere.
 """
 from .losses import L1, SSIMLoss, ssimLoss, PhotometricLoss, photometric_loss, DepthNormalLoss, DoGLoss, SmoothnessLoss, dogLoss, smoothnessLoss, downsample_bilinear, downsample_bilinear_many  # noqa: F401
 from .triangle_renderer import TriangleRenderer  # noqa: F401
@@ -77,6 +81,7 @@ from .mesh_surface import MeshBVH, point_to_mesh_distance, mesh_surface_distance
 from .metrics import psnr, ssim, evaluate_mesh  # noqa: F401
 
 _RAY_NAMES = ("RayHits", "ray_cast", "camera_rays", "point_visibility")
+_VOLUME_NAMES = ("TSDFVolume", "extract_isosurface", "fuse_mesh")
 
 
 def __getattr__(name):
@@ -85,4 +90,8 @@ def __getattr__(name):
         import importlib
         module = importlib.import_module(".mesh_ray", __name__)
         return module if name == "mesh_ray" else getattr(module, name)
+    if name in _VOLUME_NAMES or name == "volume":  # volume.py and libts_volume.so likewise
+        import importlib
+        module = importlib.import_module(".volume", __name__)
+        return module if name == "volume" else getattr(module, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -199,6 +199,30 @@ RAY_SIGNATURES = {
 }
 
 
+# include/ts_volume.h: the whole C ABI of diff_recon_hip/libts_volume.so, the fifth library (diff_recon_hip/volume.py loads and binds it)
+VOLUME_SIGNATURES = {
+    "tsv_last_error": (C.c_char_p, []),
+    "tsv_integrate": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _vp, C.c_float, C.c_float,
+                                C.c_int32, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp]),
+    "tsv_field": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp]),
+    "tsv_extract_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "tsv_extract": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, _vp, C.c_float, C.c_int64, _vp, _vp, _vp,
+                              _vp, C.c_size_t, _vp]),
+}
+
+
+def bind_volume(lib):
+    """Sets restype and argtypes of every function of include/ts_volume.h on `lib` (a ctypes.CDLL of libts_volume.so); a library that lacks
+    one is refused."""
+    missing = [name for name in VOLUME_SIGNATURES if not hasattr(lib, name)]
+    if missing:
+        raise ImportError(f"{getattr(lib, '_name', lib)} does not export {', '.join(missing)}: rebuild it with `python triangle-splatting_amd/build.py`")
+    for name, (restype, argtypes) in VOLUME_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return lib
+
+
 def bind_ray(lib):
     """Sets restype and argtypes of every function of include/ts_ray.h on `lib` (a ctypes.CDLL of libts_ray.so); a library that lacks one is
     refused."""

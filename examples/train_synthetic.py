@@ -34,6 +34,9 @@ A "ground truth" is rendered from a hidden set of triangles from several cameras
                                                         fuse the training views' depth of that mesh into a TSDF volume of RES samples a side and
                                                         extract one closed surface (diff_recon_hip.fuse_mesh); prints the topology of the soup
                                                         against the fused mesh's and the surface distance between the two and to the target
+    python examples/train_synthetic.py --eval-mesh --extract-mesh RES --extract-color
+                                                        fuse the training targets' colour in the same volume (diff_recon_hip.fuse_colored_mesh) and
+                                                        print the PSNR / SSIM of the vertex-coloured fused mesh beside the soup's own
     python examples/train_synthetic.py --eval-mesh --eval-surface N --eval-visible
                                                         those scores over the OBSERVED samples only: the ones that a training camera's centre sees
                                                         past their own mesh (ray casts, diff_recon_hip.point_visibility); prints the hidden counts
@@ -209,7 +212,7 @@ def train(rasterizer="2D", iters=200, triangles=20000, width=256, height=192, se
 
 
 def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, height=192, seed=0, views=2, refine=False, weld=None, geometry=None, surface=None,
-                visible=False, extract=None):
+                visible=False, extract=None, extract_color=False):
     """PSNR / SSIM of the model's opaque mesh -- mesh_from_triangles: one colour per face from the DC coefficients, back faces as reversed
     twins, the soup saveGLB writes -- against the hidden targets of train() called with the same arguments (diff_recon_hip.evaluate_mesh).
     refine: the result also holds "refined", the same scores (plus "kept" and "triangles") of the mesh after a census over these views
@@ -227,7 +230,10 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
     (mesh_surface_distance(visible_from=...), ray casts on the mesh's own index); "a_hidden" / "b_hidden" count the samples left out.
     extract = RES: the result also holds "fused": diff_recon_hip.fuse_mesh of the front faces over these views at resolution RES -- the
     "topology" of the fused mesh and of the "soup" (the front faces welded with eps = 0), "to_soup" = mesh_surface_distance between the two and
-    "to_target" = the same against the hidden target triangles (None for a fused mesh without faces)."""
+    "to_target" = the same against the hidden target triangles (None for a fused mesh without faces).
+    extract_color (with extract): the views' targets are fused as colour in the same volume (diff_recon_hip.fuse_colored_mesh; the mesh is the
+    same) and "fused" also holds "color": diff_recon_hip.evaluate_vertex_colors of the vertex-coloured fused mesh on these views, "vertices"
+    and "coloured", the number of vertices that found a colour."""
     _, _, cams, gts, kw, _, _ = _setup(rasterizer, iters, triangles, width, height, seed, views, 0.0, False, False)
     for cam, gt in zip(cams, gts):
         cam.gt_image = gt
@@ -264,7 +270,10 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
         soup_v, soup_f = m._vertex.detach().reshape(-1, 3), torch.arange(3 * m._vertex.shape[0], device=m._vertex.device, dtype=torch.int32).reshape(-1, 3)
         target = torch.from_numpy(np.ascontiguousarray(synthetic.scene(triangles, width, height, 2, seed=seed, edge_px=10.0)["vertex"])).to(soup_v.device)
         target_f = torch.arange(3 * target.shape[0], device=soup_v.device, dtype=torch.int32).reshape(-1, 3)
-        fused = D.fuse_mesh(cams, soup_v, soup_f, int(extract))
+        if extract_color:
+            fused = D.fuse_colored_mesh(cams, soup_v, soup_f, D.mesh_from_triangles(m._vertex, shs, save_back=False)[2], int(extract), images=gts)
+        else:
+            fused = D.fuse_mesh(cams, soup_v, soup_f, int(extract))
         welded = D.weld_mesh(soup_v, soup_f, eps=0.0)
         samples = int(surface) if surface is not None else 20000
         some = fused.faces.shape[0] > 0
@@ -272,6 +281,10 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
                             soup=D.mesh_topology(welded.stats["num_vertices"], welded.faces),
                             to_soup=D.mesh_surface_distance((fused.vertices, fused.faces), (soup_v, soup_f), samples, seed=seed) if some else None,
                             to_target=D.mesh_surface_distance((fused.vertices, fused.faces), (target.reshape(-1, 3), target_f), samples, seed=seed) if some else None)
+        if extract_color:
+            res["fused"]["color"] = dict(D.evaluate_vertex_colors(cams, fused.vertices, fused.faces, fused.vertex_color, bg_color=kw["bg_color"]),
+                                         vertices=int(fused.vertices.shape[0]), coloured=int(fused.color_valid.sum()),
+                                         soup={k: res[k] for k in ("mean_psnr", "mean_ssim")})
     return res
 
 
@@ -284,6 +297,13 @@ def fused_report(f):
             f"(the soup: {s['faces']} faces, {s['boundary']} boundary edges, {s['pieces']} pieces, Euler characteristic {s['euler']})",
             f"fused mesh against the soup: {dist(f['to_soup'])}",
             f"fused mesh against the target: {dist(f['to_target'])}"]
+
+
+def fused_color_report(c):
+    """The two lines --extract-color prints for mesh_scores(...)["fused"]["color"]."""
+    return [f"fused mesh, colours fused from the {len(c['psnr'])} training views ({c['coloured']} of {c['vertices']} vertices coloured): "
+            f"mean PSNR {c['mean_psnr']:.2f} dB, mean SSIM {c['mean_ssim']:.4f}",
+            f"the soup, one colour per face: mean PSNR {c['soup']['mean_psnr']:.2f} dB, mean SSIM {c['soup']['mean_ssim']:.4f}"]
 
 
 def geometry_report(g, title="mesh geometry"):
@@ -463,7 +483,11 @@ if __name__ == "__main__":
     ap.add_argument("--extract-mesh", type=int, default=None, metavar="RES", help="with --eval-mesh: fuse the training views' depth of the mesh into a TSDF volume of RES samples "
                                                                                     "along its longest side and extract one surface (diff_recon_hip.fuse_mesh); print its "
                                                                                     "topology beside the soup's and its surface distance to the soup and to the target")
+    ap.add_argument("--extract-color", action="store_true", help="with --extract-mesh: fuse the training targets' colour in the same volume (diff_recon_hip.fuse_colored_mesh) "
+                                                                 "and print the PSNR / SSIM of the vertex-coloured fused mesh beside the soup's own")
     a = ap.parse_args()
+    if a.extract_color and a.extract_mesh is None:
+        ap.error("--extract-color colours the mesh of --extract-mesh")
     if a.extract_mesh is not None and not a.eval_mesh:
         ap.error("--extract-mesh fuses the mesh of --eval-mesh")
     if a.extract_mesh is not None and a.extract_mesh < 10:
@@ -493,7 +517,7 @@ if __name__ == "__main__":
     print(f"{a.rasterizer}: loss {losses[0]:.5f} -> {losses[-1]:.5f} in {a.iters} iterations, {sec * 1e3:.2f} ms/iteration (incl. Python)")
     if a.eval_mesh:
         res = mesh_scores(m, a.rasterizer, a.iters, a.triangles, views=a.views, refine=a.refine_mesh, weld=a.weld_mesh, geometry=a.eval_geometry,
-                          surface=a.eval_surface, visible=a.eval_visible, extract=a.extract_mesh)
+                          surface=a.eval_surface, visible=a.eval_visible, extract=a.extract_mesh, extract_color=a.extract_color)
         for v, (p_, s_) in enumerate(zip(res["psnr"], res["ssim"])):
             print(f"  opaque mesh, view {v}: PSNR {p_:.2f} dB  SSIM {s_:.4f}")
         print(f"opaque mesh of {m._vertex.shape[0]} triangles: mean PSNR {res['mean_psnr']:.2f} dB, mean SSIM {res['mean_ssim']:.4f} over {len(res['psnr'])} views")
@@ -513,3 +537,6 @@ if __name__ == "__main__":
         if a.extract_mesh is not None:
             for line in fused_report(res["fused"]):
                 print(line)
+            if a.extract_color:
+                for line in fused_color_report(res["fused"]["color"]):
+                    print(line)

@@ -52,13 +52,18 @@
                           order, volumes add), extract_isosurface (marching tetrahedra on any fp32 grid: an oriented soup that weld_mesh(eps=0)
                           closes) and fuse_mesh (MeshRenderer depth of many views -> one connected, closed mesh) -- no counterpart in the
                           reference; loaded on first use
-    metrics.py            psnr, ssim (= 1 - SSIMLoss) and evaluate_mesh: PSNR / SSIM of a mesh's opaque render against each view's gt_image
+    color_volume.py       ColorTSDFVolume (colour fused beside the distances, in integers), sample_grid (trilinear over the samples that have
+                          data: the colour of every extracted vertex, a function of its position alone), interpolate_vertex_attributes /
+                          render_vertex_colors (vertex colours drawn over MeshRenderer's coverage), fuse_colored_mesh (fuse_mesh with colour)
+                          and save_glb_mesh (an indexed, vertex-coloured GLB) -- no counterpart in the reference; loaded on first use
+    metrics.py            psnr, ssim (= 1 - SSIMLoss), evaluate_mesh and evaluate_vertex_colors: PSNR / SSIM of a mesh's opaque render (one
+                          colour per face, or per vertex) against each view's gt_image
                           (reference: src/diff_recon/trainers/trainer_utils.py:331-336, VanillaTS_trainer.py:156-190)
     graphed.py            GraphedStep: a whole training step (sync-free forward, loss, backward, optimizer) captured once into a HIP graph and
                           replayed with one launch -- no counterpart in the reference, whose forward reads num_rendered back every step
 
 Native code: libts2d.so (include/ts_loss.h, include/ts_model.h, include/ts_optim.h, include/ts2d.h, include/ts_mesh.h, include/ts_weld.h) and, for
-mesh_distance.py, libts_geom.so beside this file (include/ts_geom.h), for mesh_surface.py, libts_bvh.so (include/ts_bvh.h), for mesh_ray.py, libts_ray.so (include/ts_ray.h), for volume.py, libts_volume.so (include/ts_volume.h).  No CPU / eager fallback anywhere.
+mesh_distance.py, libts_geom.so beside this file (include/ts_geom.h), for mesh_surface.py, libts_bvh.so (include/ts_bvh.h), for mesh_ray.py, libts_ray.so (include/ts_ray.h), for volume.py, libts_volume.so (include/ts_volume.h), for color_volume.py, libts_color.so (include/ts_color.h).  No CPU / eager fallback anywhere.
 """
 from .losses import L1, SSIMLoss, ssimLoss, PhotometricLoss, photometric_loss, DepthNormalLoss, DoGLoss, SmoothnessLoss, dogLoss, smoothnessLoss, downsample_bilinear, downsample_bilinear_many  # noqa: F401
 from .triangle_renderer import TriangleRenderer  # noqa: F401
@@ -78,10 +83,12 @@ from .mesh_census import MeshCensus, bake_face_colors, visible_triangle_mask  # 
 from .mesh_weld import WeldedMesh, weld_mesh, mesh_topology  # noqa: F401
 from .mesh_distance import SurfaceSamples, nearest_points, face_areas, sample_mesh_surface, point_cloud_distance, mesh_distance  # noqa: F401
 from .mesh_surface import MeshBVH, point_to_mesh_distance, mesh_surface_distance  # noqa: F401
-from .metrics import psnr, ssim, evaluate_mesh  # noqa: F401
+from .metrics import psnr, ssim, evaluate_mesh, evaluate_vertex_colors  # noqa: F401
 
 _RAY_NAMES = ("RayHits", "ray_cast", "camera_rays", "point_visibility")
 _VOLUME_NAMES = ("TSDFVolume", "extract_isosurface", "fuse_mesh")
+_COLOR_NAMES = ("ColorTSDFVolume", "ColoredMesh", "sample_grid", "interpolate_vertex_attributes", "render_vertex_colors", "fuse_colored_mesh",
+                "save_glb_mesh")
 
 
 def __getattr__(name):
@@ -94,4 +101,8 @@ def __getattr__(name):
         import importlib
         module = importlib.import_module(".volume", __name__)
         return module if name == "volume" else getattr(module, name)
+    if name in _COLOR_NAMES or name == "color_volume":  # color_volume.py and libts_color.so likewise
+        import importlib
+        module = importlib.import_module(".color_volume", __name__)
+        return module if name == "color_volume" else getattr(module, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

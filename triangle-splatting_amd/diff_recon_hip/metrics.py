@@ -45,3 +45,18 @@ def evaluate_mesh(views: Iterable, vertices: torch.Tensor, faces: torch.Tensor, 
         ssims.append(float(ssim(image, gt.contiguous()).item()))
     n = len(psnrs)
     return {"psnr": psnrs, "ssim": ssims, "mean_psnr": sum(psnrs) / n if n else float("nan"), "mean_ssim": sum(ssims) / n if n else float("nan")}
+
+
+def evaluate_vertex_colors(views: Iterable, vertices: torch.Tensor, faces: torch.Tensor, vertex_color: torch.Tensor,
+                           bg_color: torch.Tensor = torch.Tensor([0, 0, 0])) -> Dict[str, object]:
+    """evaluate_mesh for a mesh with one colour per VERTEX (V, 3), drawn by color_volume.render_vertex_colors: the same loop, the same keys."""
+    from .color_volume import render_vertex_colors  # libts_color.so is loaded on first use
+    psnrs, ssims = [], []
+    for view in views:
+        image = render_vertex_colors(view, vertices, faces, vertex_color, bg_color)["render"]
+        gt = view.gt_image.to(image.device)
+        alpha = getattr(view, "alpha_mask", None)
+        psnrs.append(float(psnr(image, gt, alpha.to(image.device) if alpha is not None else None).item()))
+        ssims.append(float(ssim(image, gt.contiguous()).item()))
+    n = len(psnrs)
+    return {"psnr": psnrs, "ssim": ssims, "mean_psnr": sum(psnrs) / n if n else float("nan"), "mean_ssim": sum(ssims) / n if n else float("nan")}

@@ -156,10 +156,25 @@ def fuse_mesh(views, vertices: torch.Tensor, faces: torch.Tensor, resolution: in
     carving into a volume of `resolution` samples along the longest side of the bounding box of the finite vertices, padded by trunc
     (default 4 voxels); then extracted and welded.  Returns a WeldedMesh (with return_volume: and the TSDFVolume)."""
     from .mesh_renderer import MeshRenderer
+    if int(resolution) < 2:
+        raise ValueError("resolution must be at least 2")
+    device = _cuda_device(vertices.device)
+    v = vertices.detach().to(torch.float32)
+    volume = TSDFVolume(*fusion_bounds(v, resolution, trunc), device)
+    colour = torch.zeros((faces.shape[0], 3), device=device, dtype=torch.float32)
+    for cam in views:
+        out = MeshRenderer(cam).render(vertices=v, faces=faces, faces_color=colour)
+        volume.integrate(cam, out["depth"], carve_uncovered=True)
+    mesh = volume.extract()
+    return (mesh, volume) if return_volume else mesh
+
+
+def fusion_bounds(vertices: torch.Tensor, resolution: int, trunc: Optional[float] = None):
+    """(origin, voxel_size, dims, trunc) of the volume fuse_mesh builds around `vertices` (V, 3): `resolution` samples along the longest side
+    of the bounding box of the finite vertices, padded by trunc (default 4 voxels) either side."""
     resolution = int(resolution)
     if resolution < 2:
         raise ValueError("resolution must be at least 2")
-    device = _cuda_device(vertices.device)
     v = vertices.detach().to(torch.float32)
     finite = v[torch.isfinite(v).all(dim=1)]
     if finite.shape[0] == 0:
@@ -172,13 +187,7 @@ def fuse_mesh(views, vertices: torch.Tensor, faces: torch.Tensor, resolution: in
         raise ValueError(f"resolution {resolution} leaves no room for the padding of {'4 voxels' if trunc is None else trunc} either side")
     tr = float(trunc) if trunc is not None else 4.0 * h
     dims = tuple(min(resolution, int(math.ceil((float(hi[a] - lo[a]) + 2.0 * tr) / h - 1e-9)) + 1) for a in range(3))
-    volume = TSDFVolume((lo - tr).tolist(), h, dims, tr, device)
-    colour = torch.zeros((faces.shape[0], 3), device=device, dtype=torch.float32)
-    for cam in views:
-        out = MeshRenderer(cam).render(vertices=v, faces=faces, faces_color=colour)
-        volume.integrate(cam, out["depth"], carve_uncovered=True)
-    mesh = volume.extract()
-    return (mesh, volume) if return_volume else mesh
+    return (lo - tr).tolist(), h, dims, tr
 
 
-__all__ = ["TSDFVolume", "extract_isosurface", "fuse_mesh", "CARVE_UNCOVERED"]
+__all__ = ["TSDFVolume", "extract_isosurface", "fuse_mesh", "fusion_bounds", "CARVE_UNCOVERED"]

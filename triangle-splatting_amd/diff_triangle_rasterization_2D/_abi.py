@@ -1,5 +1,5 @@
 """The C ABI of libts2d.so as ctypes sees it, declared once: the mirrors of the structs of include/*.h and the signature of every function
-they declare (and of the lab library's additions, csrc/ts2d_lab.h, and of the other three product libraries: libts_geom.so, include/ts_geom.h, libts_bvh.so, include/ts_bvh.h, and libts_ray.so, include/ts_ray.h).  Pure ctypes: no torch, no library is loaded here -- `_C.py` binds the
+they declare (and of the lab library's additions, csrc/ts2d_lab.h, and of the other five product libraries: libts_geom.so, include/ts_geom.h, libts_bvh.so, include/ts_bvh.h, libts_ray.so, include/ts_ray.h, libts_volume.so, include/ts_volume.h, and libts_color.so, include/ts_color.h).  Pure ctypes: no torch, no library is loaded here -- `_C.py` binds the
 library the package loads, the CPU tests bind a CDLL of their own.  tests/test_cabi_cpu.py holds both tables against the headers: the structs
 by sizeof / offsetof, the functions prototype by prototype.
 
@@ -209,6 +209,31 @@ VOLUME_SIGNATURES = {
     "tsv_extract": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, _vp, C.c_float, C.c_int64, _vp, _vp, _vp,
                               _vp, C.c_size_t, _vp]),
 }
+
+
+# include/ts_color.h: the whole C ABI of diff_recon_hip/libts_color.so, the sixth library (diff_recon_hip/color_volume.py loads and binds it)
+COLOR_SIGNATURES = {
+    "tsc_last_error": (C.c_char_p, []),
+    "tsc_integrate": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _vp, C.c_float, C.c_float,
+                                C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tsc_color_field": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp]),
+    "tsc_sample": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp,
+                             _vp]),
+    "tsc_interpolate": (C.c_int, [_vp, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp, _vp,
+                                  _vp, _vp]),
+}
+
+
+def bind_color(lib):
+    """Sets restype and argtypes of every function of include/ts_color.h on `lib` (a ctypes.CDLL of libts_color.so); a library that lacks one
+    is refused."""
+    missing = [name for name in COLOR_SIGNATURES if not hasattr(lib, name)]
+    if missing:
+        raise ImportError(f"{getattr(lib, '_name', lib)} does not export {', '.join(missing)}: rebuild it with `python triangle-splatting_amd/build.py`")
+    for name, (restype, argtypes) in COLOR_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return lib
 
 
 def bind_volume(lib):

@@ -37,6 +37,11 @@ A "ground truth" is rendered from a hidden set of triangles from several cameras
     python examples/train_synthetic.py --eval-mesh --extract-mesh RES --extract-color
                                                         fuse the training targets' colour in the same volume (diff_recon_hip.fuse_colored_mesh) and
                                                         print the PSNR / SSIM of the vertex-coloured fused mesh beside the soup's own
+    python examples/train_synthetic.py --eval-mesh --extract-mesh RES --simplify-mesh K [--min-piece N]
+                                                        simplify the fused mesh by vertex clustering in cells of K voxels with quadric placement
+                                                        (diff_recon_hip.simplify_mesh) and drop the pieces below N faces (drop_small_pieces);
+                                                        prints the simplified mesh's faces, topology and surface distance to the soup, and with
+                                                        --extract-color its PSNR / SSIM
     python examples/train_synthetic.py --eval-mesh --eval-surface N --eval-visible
                                                         those scores over the OBSERVED samples only: the ones that a training camera's centre sees
                                                         past their own mesh (ray casts, diff_recon_hip.point_visibility); prints the hidden counts
@@ -212,7 +217,7 @@ def train(rasterizer="2D", iters=200, triangles=20000, width=256, height=192, se
 
 
 def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, height=192, seed=0, views=2, refine=False, weld=None, geometry=None, surface=None,
-                visible=False, extract=None, extract_color=False):
+                visible=False, extract=None, extract_color=False, simplify=None, min_piece=0):
     """PSNR / SSIM of the model's opaque mesh -- mesh_from_triangles: one colour per face from the DC coefficients, back faces as reversed
     twins, the soup saveGLB writes -- against the hidden targets of train() called with the same arguments (diff_recon_hip.evaluate_mesh).
     refine: the result also holds "refined", the same scores (plus "kept" and "triangles") of the mesh after a census over these views
@@ -233,7 +238,10 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
     "to_target" = the same against the hidden target triangles (None for a fused mesh without faces).
     extract_color (with extract): the views' targets are fused as colour in the same volume (diff_recon_hip.fuse_colored_mesh; the mesh is the
     same) and "fused" also holds "color": diff_recon_hip.evaluate_vertex_colors of the vertex-coloured fused mesh on these views, "vertices"
-    and "coloured", the number of vertices that found a colour."""
+    and "coloured", the number of vertices that found a colour.
+    simplify = K and / or min_piece = N (with extract): "fused" also holds "simplified": the fused mesh after diff_recon_hip.simplify_mesh on the
+    volume's grid in cells of K voxels and drop_small_pieces(N) (diff_recon_hip.simplify_fused) -- its "topology", "to_soup", the "stats" of the two steps and, with
+    extract_color, "color" (the vertex colours averaged per cluster)."""
     _, _, cams, gts, kw, _, _ = _setup(rasterizer, iters, triangles, width, height, seed, views, 0.0, False, False)
     for cam, gt in zip(cams, gts):
         cam.gt_image = gt
@@ -270,10 +278,14 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
         soup_v, soup_f = m._vertex.detach().reshape(-1, 3), torch.arange(3 * m._vertex.shape[0], device=m._vertex.device, dtype=torch.int32).reshape(-1, 3)
         target = torch.from_numpy(np.ascontiguousarray(synthetic.scene(triangles, width, height, 2, seed=seed, edge_px=10.0)["vertex"])).to(soup_v.device)
         target_f = torch.arange(3 * target.shape[0], device=soup_v.device, dtype=torch.int32).reshape(-1, 3)
+        post = simplify is not None or int(min_piece) > 0
         if extract_color:
-            fused = D.fuse_colored_mesh(cams, soup_v, soup_f, D.mesh_from_triangles(m._vertex, shs, save_back=False)[2], int(extract), images=gts)
+            fused = D.fuse_colored_mesh(cams, soup_v, soup_f, D.mesh_from_triangles(m._vertex, shs, save_back=False)[2], int(extract), images=gts,
+                                        return_volume=post)
         else:
-            fused = D.fuse_mesh(cams, soup_v, soup_f, int(extract))
+            fused = D.fuse_mesh(cams, soup_v, soup_f, int(extract), return_volume=post)
+        if post:
+            fused, volume = fused
         welded = D.weld_mesh(soup_v, soup_f, eps=0.0)
         samples = int(surface) if surface is not None else 20000
         some = fused.faces.shape[0] > 0
@@ -285,7 +297,35 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
             res["fused"]["color"] = dict(D.evaluate_vertex_colors(cams, fused.vertices, fused.faces, fused.vertex_color, bg_color=kw["bg_color"]),
                                          vertices=int(fused.vertices.shape[0]), coloured=int(fused.color_valid.sum()),
                                          soup={k: res[k] for k in ("mean_psnr", "mean_ssim")})
+        if post:
+            small = D.simplify_fused(fused, volume, simplify, int(min_piece))
+            sv, sf, stats = small.vertices, small.faces, small.stats
+            res["fused"]["simplified"] = dict(cell=simplify, min_piece=int(min_piece), faces_in=int(fused.faces.shape[0]), stats=stats,
+                                              topology=D.mesh_topology(sv.shape[0], sf),
+                                              to_soup=D.mesh_surface_distance((sv, sf), (soup_v, soup_f), samples, seed=seed) if sf.shape[0] else None)
+            if extract_color:
+                res["fused"]["simplified"]["color"] = dict(D.evaluate_vertex_colors(cams, sv, sf, small.vertex_color, bg_color=kw["bg_color"]),
+                                                           vertices=int(sv.shape[0]), coloured=int(small.color_valid.sum()))
     return res
+
+
+def simplified_report(f):
+    """The lines --simplify-mesh / --min-piece print for mesh_scores(...)["fused"]["simplified"]."""
+    t, st = f["topology"], f["stats"]
+    how = [] if f["cell"] is None else [f"cells of {f['cell']:g} voxels"]
+    how += [f"pieces below {f['min_piece']} faces dropped"] if f["min_piece"] > 0 else []
+    simp = st.get("simplify")
+    swept = f"; {simp['collapsed']} faces collapsed, {simp['duplicates']} duplicates removed, {simp['flaps']} flaps, largest cluster {simp['largest_cluster']}" if simp else ""
+    g = f["to_soup"]
+    lines = [f"simplified mesh, {', '.join(how)}: {t['faces']} of {f['faces_in']} faces, {t['boundary']} boundary edges, {t['nonmanifold']} non-manifold edges, "
+             f"{t['pieces']} pieces, Euler characteristic {t['euler']}{swept}",
+             "simplified mesh against the soup: " + (f"accuracy {g['accuracy']:.4g}, completeness {g['completeness']:.4g}, Chamfer {g['chamfer']:.4g}, "
+                                                     f"Hausdorff {g['hausdorff']:.4g}" if g is not None else "no surface is left")]
+    if "color" in f:
+        c = f["color"]
+        lines.append(f"simplified mesh, colours averaged per cluster ({c['coloured']} of {c['vertices']} vertices coloured): "
+                     f"mean PSNR {c['mean_psnr']:.2f} dB, mean SSIM {c['mean_ssim']:.4f}")
+    return lines
 
 
 def fused_report(f):
@@ -485,7 +525,20 @@ if __name__ == "__main__":
                                                                                     "topology beside the soup's and its surface distance to the soup and to the target")
     ap.add_argument("--extract-color", action="store_true", help="with --extract-mesh: fuse the training targets' colour in the same volume (diff_recon_hip.fuse_colored_mesh) "
                                                                  "and print the PSNR / SSIM of the vertex-coloured fused mesh beside the soup's own")
+    ap.add_argument("--simplify-mesh", type=float, default=None, metavar="K", help="with --extract-mesh: simplify the fused mesh by vertex clustering in cells of K voxels with "
+                                                                                   "quadric placement (diff_recon_hip.simplify_mesh) and print its faces, topology and "
+                                                                                   "surface distance to the soup (with --extract-color: its PSNR / SSIM)")
+    ap.add_argument("--min-piece", type=int, default=0, metavar="N", help="with --extract-mesh: drop the connected pieces of the (simplified) fused mesh below N faces "
+                                                                         "(diff_recon_hip.drop_small_pieces)")
     a = ap.parse_args()
+    if a.simplify_mesh is not None and a.extract_mesh is None:
+        ap.error("--simplify-mesh simplifies the mesh of --extract-mesh")
+    if a.min_piece and a.extract_mesh is None:
+        ap.error("--min-piece filters the mesh of --extract-mesh")
+    if a.simplify_mesh is not None and not (a.simplify_mesh > 0 and math.isfinite(a.simplify_mesh)):
+        ap.error("--simplify-mesh needs a positive cell size in voxels")
+    if a.min_piece < 0:
+        ap.error("--min-piece needs a face count >= 0")
     if a.extract_color and a.extract_mesh is None:
         ap.error("--extract-color colours the mesh of --extract-mesh")
     if a.extract_mesh is not None and not a.eval_mesh:
@@ -517,7 +570,8 @@ if __name__ == "__main__":
     print(f"{a.rasterizer}: loss {losses[0]:.5f} -> {losses[-1]:.5f} in {a.iters} iterations, {sec * 1e3:.2f} ms/iteration (incl. Python)")
     if a.eval_mesh:
         res = mesh_scores(m, a.rasterizer, a.iters, a.triangles, views=a.views, refine=a.refine_mesh, weld=a.weld_mesh, geometry=a.eval_geometry,
-                          surface=a.eval_surface, visible=a.eval_visible, extract=a.extract_mesh, extract_color=a.extract_color)
+                          surface=a.eval_surface, visible=a.eval_visible, extract=a.extract_mesh, extract_color=a.extract_color, simplify=a.simplify_mesh,
+                          min_piece=a.min_piece)
         for v, (p_, s_) in enumerate(zip(res["psnr"], res["ssim"])):
             print(f"  opaque mesh, view {v}: PSNR {p_:.2f} dB  SSIM {s_:.4f}")
         print(f"opaque mesh of {m._vertex.shape[0]} triangles: mean PSNR {res['mean_psnr']:.2f} dB, mean SSIM {res['mean_ssim']:.4f} over {len(res['psnr'])} views")
@@ -539,4 +593,7 @@ if __name__ == "__main__":
                 print(line)
             if a.extract_color:
                 for line in fused_color_report(res["fused"]["color"]):
+                    print(line)
+            if "simplified" in res["fused"]:
+                for line in simplified_report(res["fused"]["simplified"]):
                     print(line)

@@ -7,7 +7,8 @@ connected, oriented, closed mesh.
         .extract(min_weight=1, iso=0.0, weld=True)                 the level set as a WeldedMesh (mesh_weld.py)
         .sum (int64), .weight (int32)                              the state: integers, so volumes add (`a.sum += b.sum; a.weight += b.weight`)
     extract_isosurface(field, origin, voxel_size, iso=0.0)         marching tetrahedra on any (nz, ny, nx) fp32 grid -> (vertices (3T, 3), faces (T, 3))
-    fuse_mesh(views, vertices, faces, resolution, trunc=None)      MeshRenderer depth of every view, fused with carving, extracted and welded
+    fuse_mesh(views, vertices, faces, resolution, trunc=None)      MeshRenderer depth of every view, fused with carving, extracted and welded;
+                                                                   simplify_cell=K (voxels) / min_piece_faces=N: mesh_simplify.py behind it
 
 Both kernels are pure functions of their input (include/ts_volume.h): the sums are integers, so the state is bit-identical in
 any view order; the vertex of a grid edge is a function of the edge alone, so every tetrahedron that shares it writes the same bits and
@@ -151,10 +152,14 @@ class TSDFVolume:
 
 
 def fuse_mesh(views, vertices: torch.Tensor, faces: torch.Tensor, resolution: int, trunc: Optional[float] = None,
-              return_volume: bool = False):
+              return_volume: bool = False, simplify_cell: Optional[float] = None, min_piece_faces: int = 0):
     """The closed surface that the views see of the mesh (vertices (V, 3), faces (F, 3)): every view's MeshRenderer depth integrated with
     carving into a volume of `resolution` samples along the longest side of the bounding box of the finite vertices, padded by trunc
-    (default 4 voxels); then extracted and welded.  Returns a WeldedMesh (with return_volume: and the TSDFVolume)."""
+    (default 4 voxels); then extracted and welded.  Returns a WeldedMesh (with return_volume: and the TSDFVolume).
+    simplify_cell (in voxels, on the volume's own grid) and min_piece_faces, when given, run simplify_mesh and drop_small_pieces
+    (mesh_simplify.py) on the welded level set: vertex_map and face_keep then lead from the level set to the result and stats gains
+    "simplify" / "small_piece_faces" (mesh_simplify.simplify_fused; the same call serves a fuse_colored_mesh result).  Their defaults change
+    nothing."""
     from .mesh_renderer import MeshRenderer
     if int(resolution) < 2:
         raise ValueError("resolution must be at least 2")
@@ -166,6 +171,9 @@ def fuse_mesh(views, vertices: torch.Tensor, faces: torch.Tensor, resolution: in
         out = MeshRenderer(cam).render(vertices=v, faces=faces, faces_color=colour)
         volume.integrate(cam, out["depth"], carve_uncovered=True)
     mesh = volume.extract()
+    if simplify_cell is not None or int(min_piece_faces) > 0:
+        from .mesh_simplify import simplify_fused
+        mesh = simplify_fused(mesh, volume, simplify_cell, min_piece_faces)
     return (mesh, volume) if return_volume else mesh
 
 

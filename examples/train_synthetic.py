@@ -37,6 +37,10 @@ A "ground truth" is rendered from a hidden set of triangles from several cameras
     python examples/train_synthetic.py --eval-mesh --extract-mesh RES --extract-color
                                                         fuse the training targets' colour in the same volume (diff_recon_hip.fuse_colored_mesh) and
                                                         print the PSNR / SSIM of the vertex-coloured fused mesh beside the soup's own
+    python examples/train_synthetic.py --eval-mesh --extract-mesh RES --smooth-mesh N
+                                                        smooth the fused mesh with N Taubin iterations before anything simplifies it, every vertex within
+                                                        one voxel of its level set (diff_recon_hip.smooth_fused); prints its largest displacement in
+                                                        voxels, its surface distance and normal consistency to the soup, and its topology (unchanged)
     python examples/train_synthetic.py --eval-mesh --extract-mesh RES --simplify-mesh K [--min-piece N]
                                                         simplify the fused mesh by vertex clustering in cells of K voxels with quadric placement
                                                         (diff_recon_hip.simplify_mesh) and drop the pieces below N faces (drop_small_pieces);
@@ -217,7 +221,7 @@ def train(rasterizer="2D", iters=200, triangles=20000, width=256, height=192, se
 
 
 def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, height=192, seed=0, views=2, refine=False, weld=None, geometry=None, surface=None,
-                visible=False, extract=None, extract_color=False, simplify=None, min_piece=0):
+                visible=False, extract=None, extract_color=False, simplify=None, min_piece=0, smooth=None):
     """PSNR / SSIM of the model's opaque mesh -- mesh_from_triangles: one colour per face from the DC coefficients, back faces as reversed
     twins, the soup saveGLB writes -- against the hidden targets of train() called with the same arguments (diff_recon_hip.evaluate_mesh).
     refine: the result also holds "refined", the same scores (plus "kept" and "triangles") of the mesh after a census over these views
@@ -241,7 +245,10 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
     and "coloured", the number of vertices that found a colour.
     simplify = K and / or min_piece = N (with extract): "fused" also holds "simplified": the fused mesh after diff_recon_hip.simplify_mesh on the
     volume's grid in cells of K voxels and drop_small_pieces(N) (diff_recon_hip.simplify_fused) -- its "topology", "to_soup", the "stats" of the two steps and, with
-    extract_color, "color" (the vertex colours averaged per cluster)."""
+    extract_color, "color" (the vertex colours averaged per cluster).
+    smooth = N (with extract): the fused mesh is smoothed with N Taubin iterations, every vertex kept within one voxel of its level set
+    (diff_recon_hip.smooth_fused), BEFORE it is simplified, and "fused" also holds "smoothed": "iterations", "moved", "max_displacement_voxels", its
+    "topology", "to_soup" and "normals" = diff_recon_hip.mesh_normal_consistency to the soup, with "normals_before", the same of the mesh as fused."""
     _, _, cams, gts, kw, _, _ = _setup(rasterizer, iters, triangles, width, height, seed, views, 0.0, False, False)
     for cam, gt in zip(cams, gts):
         cam.gt_image = gt
@@ -278,7 +285,8 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
         soup_v, soup_f = m._vertex.detach().reshape(-1, 3), torch.arange(3 * m._vertex.shape[0], device=m._vertex.device, dtype=torch.int32).reshape(-1, 3)
         target = torch.from_numpy(np.ascontiguousarray(synthetic.scene(triangles, width, height, 2, seed=seed, edge_px=10.0)["vertex"])).to(soup_v.device)
         target_f = torch.arange(3 * target.shape[0], device=soup_v.device, dtype=torch.int32).reshape(-1, 3)
-        post = simplify is not None or int(min_piece) > 0
+        simplified = simplify is not None or int(min_piece) > 0
+        post = simplified or smooth is not None
         if extract_color:
             fused = D.fuse_colored_mesh(cams, soup_v, soup_f, D.mesh_from_triangles(m._vertex, shs, save_back=False)[2], int(extract), images=gts,
                                         return_volume=post)
@@ -297,7 +305,14 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
             res["fused"]["color"] = dict(D.evaluate_vertex_colors(cams, fused.vertices, fused.faces, fused.vertex_color, bg_color=kw["bg_color"]),
                                          vertices=int(fused.vertices.shape[0]), coloured=int(fused.color_valid.sum()),
                                          soup={k: res[k] for k in ("mean_psnr", "mean_ssim")})
-        if post:
+        if smooth is not None:
+            plain = fused
+            fused = D.smooth_fused(plain, volume, iterations=int(smooth))
+            both = lambda mesh: D.mesh_normal_consistency((mesh.vertices, mesh.faces), (soup_v, soup_f), samples, seed=seed) if some else None
+            res["fused"]["smoothed"] = dict(fused.stats["smooth"], topology=D.mesh_topology(fused.vertices.shape[0], fused.faces),
+                                            to_soup=D.mesh_surface_distance((fused.vertices, fused.faces), (soup_v, soup_f), samples, seed=seed) if some else None,
+                                            normals=both(fused), normals_before=both(plain))
+        if simplified:
             small = D.simplify_fused(fused, volume, simplify, int(min_piece))
             sv, sf, stats = small.vertices, small.faces, small.stats
             res["fused"]["simplified"] = dict(cell=simplify, min_piece=int(min_piece), faces_in=int(fused.faces.shape[0]), stats=stats,
@@ -307,6 +322,19 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
                 res["fused"]["simplified"]["color"] = dict(D.evaluate_vertex_colors(cams, sv, sf, small.vertex_color, bg_color=kw["bg_color"]),
                                                            vertices=int(sv.shape[0]), coloured=int(small.color_valid.sum()))
     return res
+
+
+def smoothed_report(f):
+    """The line --smooth-mesh prints for mesh_scores(...)["fused"]: the smoothed mesh of ["smoothed"] beside the fused one."""
+    s, t = f["smoothed"], f["smoothed"]["topology"]
+    same = "unchanged" if t == f["topology"] else "CHANGED"
+    if s["to_soup"] is None:
+        return [f"smoothed mesh, {s['iterations']} Taubin iterations: no surface was extracted"]
+    g, n, b = s["to_soup"], s["normals"], s["normals_before"]
+    return [f"smoothed mesh, {s['iterations']} Taubin iterations: {s['moved']} vertices moved, largest displacement {s['max_displacement_voxels']:.3f} voxels; against the "
+            f"soup: accuracy {g['accuracy']:.4g}, completeness {g['completeness']:.4g}, Chamfer {g['chamfer']:.4g}, normal consistency "
+            f"{n['abs_normal_consistency']:.4f} (as fused: {b['abs_normal_consistency']:.4f}); topology {same} ({t['faces']} faces, {t['boundary']} boundary edges, "
+            f"{t['pieces']} pieces, Euler characteristic {t['euler']})"]
 
 
 def simplified_report(f):
@@ -530,7 +558,14 @@ if __name__ == "__main__":
                                                                                    "surface distance to the soup (with --extract-color: its PSNR / SSIM)")
     ap.add_argument("--min-piece", type=int, default=0, metavar="N", help="with --extract-mesh: drop the connected pieces of the (simplified) fused mesh below N faces "
                                                                          "(diff_recon_hip.drop_small_pieces)")
+    ap.add_argument("--smooth-mesh", type=int, default=None, metavar="N", help="with --extract-mesh: smooth the fused mesh with N Taubin iterations before it is simplified, every "
+                                                                               "vertex within one voxel of its level set (diff_recon_hip.smooth_fused), and print its "
+                                                                               "displacement, surface distance and normal consistency to the soup, and its topology")
     a = ap.parse_args()
+    if a.smooth_mesh is not None and a.extract_mesh is None:
+        ap.error("--smooth-mesh smooths the mesh of --extract-mesh")
+    if a.smooth_mesh is not None and a.smooth_mesh < 0:
+        ap.error("--smooth-mesh needs a number of iterations >= 0")
     if a.simplify_mesh is not None and a.extract_mesh is None:
         ap.error("--simplify-mesh simplifies the mesh of --extract-mesh")
     if a.min_piece and a.extract_mesh is None:
@@ -571,7 +606,7 @@ if __name__ == "__main__":
     if a.eval_mesh:
         res = mesh_scores(m, a.rasterizer, a.iters, a.triangles, views=a.views, refine=a.refine_mesh, weld=a.weld_mesh, geometry=a.eval_geometry,
                           surface=a.eval_surface, visible=a.eval_visible, extract=a.extract_mesh, extract_color=a.extract_color, simplify=a.simplify_mesh,
-                          min_piece=a.min_piece)
+                          min_piece=a.min_piece, smooth=a.smooth_mesh)
         for v, (p_, s_) in enumerate(zip(res["psnr"], res["ssim"])):
             print(f"  opaque mesh, view {v}: PSNR {p_:.2f} dB  SSIM {s_:.4f}")
         print(f"opaque mesh of {m._vertex.shape[0]} triangles: mean PSNR {res['mean_psnr']:.2f} dB, mean SSIM {res['mean_ssim']:.4f} over {len(res['psnr'])} views")
@@ -593,6 +628,9 @@ if __name__ == "__main__":
                 print(line)
             if a.extract_color:
                 for line in fused_color_report(res["fused"]["color"]):
+                    print(line)
+            if "smoothed" in res["fused"]:
+                for line in smoothed_report(res["fused"]):
                     print(line)
             if "simplified" in res["fused"]:
                 for line in simplified_report(res["fused"]["simplified"]):

@@ -60,14 +60,19 @@
                           result is a pure function of the input and bit-equal to a float64 reference; attributes are averaged, duplicate
                           faces swept) and drop_small_pieces (connected pieces below a face count removed) -- the pass behind
                           extract_isosurface / fuse_mesh(simplify_cell=...); no counterpart in the reference; loaded on first use
-    metrics.py            psnr, ssim (= 1 - SSIMLoss), evaluate_mesh and evaluate_vertex_colors: PSNR / SSIM of a mesh's opaque render (one
+    mesh_smooth.py        vertex_adjacency (the one-ring of every vertex as CSR, edge use counts, vertex classes), smooth_mesh / smooth_fused
+                          (Taubin lambda|mu smoothing in float64, bounded per axis, bit-equal to a float64 reference), face_normals /
+                          vertex_normals, mesh_normal_consistency (the score beside Chamfer and F-score) and save_glb_shaded_mesh (a GLB
+                          with a NORMAL accessor) -- the pass between extraction and simplify_mesh; no counterpart in the reference;
+                          loaded on first use
+    metrics.py           psnr, ssim (= 1 - SSIMLoss), evaluate_mesh and evaluate_vertex_colors: PSNR / SSIM of a mesh's opaque render (one
                           colour per face, or per vertex) against each view's gt_image
                           (reference: src/diff_recon/trainers/trainer_utils.py:331-336, VanillaTS_trainer.py:156-190)
     graphed.py            GraphedStep: a whole training step (sync-free forward, loss, backward, optimizer) captured once into a HIP graph and
                           replayed with one launch -- no counterpart in the reference, whose forward reads num_rendered back every step
 
 Native code: libts2d.so (include/ts_loss.h, include/ts_model.h, include/ts_optim.h, include/ts2d.h, include/ts_mesh.h, include/ts_weld.h) and, for
-mesh_distance.py, libts_geom.so beside this file (include/ts_geom.h), for mesh_surface.py, libts_bvh.so (include/ts_bvh.h), for mesh_ray.py, libts_ray.so (include/ts_ray.h), for volume.py, libts_volume.so (include/ts_volume.h), for color_volume.py, libts_color.so (include/ts_color.h), for mesh_simplify.py, libts_simplify.so (include/ts_simplify.h).  No CPU / eager fallback anywhere.
+mesh_distance.py, libts_geom.so beside this file (include/ts_geom.h), for mesh_surface.py, libts_bvh.so (include/ts_bvh.h), for mesh_ray.py, libts_ray.so (include/ts_ray.h), for volume.py, libts_volume.so (include/ts_volume.h), for color_volume.py, libts_color.so (include/ts_color.h), for mesh_simplify.py, libts_simplify.so (include/ts_simplify.h), for mesh_smooth.py, libts_smooth.so (include/ts_smooth.h).  No CPU / eager fallback anywhere.
 """
 from .losses import L1, SSIMLoss, ssimLoss, PhotometricLoss, photometric_loss, DepthNormalLoss, DoGLoss, SmoothnessLoss, dogLoss, smoothnessLoss, downsample_bilinear, downsample_bilinear_many  # noqa: F401
 from .triangle_renderer import TriangleRenderer  # noqa: F401
@@ -94,6 +99,8 @@ _VOLUME_NAMES = ("TSDFVolume", "extract_isosurface", "fuse_mesh")
 _COLOR_NAMES = ("ColorTSDFVolume", "ColoredMesh", "sample_grid", "interpolate_vertex_attributes", "render_vertex_colors", "fuse_colored_mesh",
                 "save_glb_mesh")
 _SIMPLIFY_NAMES = ("SimplifiedMesh", "simplify_mesh", "drop_small_pieces", "simplify_fused", "cluster_labels", "place_clusters", "unique_faces")
+_SMOOTH_NAMES = ("MeshAdjacency", "SmoothedMesh", "vertex_adjacency", "smooth_mesh", "face_normals", "vertex_normals", "smooth_fused",
+                 "mesh_normal_consistency", "save_glb_shaded_mesh")
 
 
 def __getattr__(name):
@@ -114,4 +121,8 @@ def __getattr__(name):
         import importlib
         module = importlib.import_module(".mesh_simplify", __name__)
         return module if name == "mesh_simplify" else getattr(module, name)
+    if name in _SMOOTH_NAMES or name == "mesh_smooth":  # mesh_smooth.py and libts_smooth.so likewise
+        import importlib
+        module = importlib.import_module(".mesh_smooth", __name__)
+        return module if name == "mesh_smooth" else getattr(module, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -37,6 +37,10 @@ A "ground truth" is rendered from a hidden set of triangles from several cameras
     python examples/train_synthetic.py --eval-mesh --extract-mesh RES --extract-color
                                                         fuse the training targets' colour in the same volume (diff_recon_hip.fuse_colored_mesh) and
                                                         print the PSNR / SSIM of the vertex-coloured fused mesh beside the soup's own
+    python examples/train_synthetic.py --eval-mesh --extract-mesh RES --fill-holes N
+                                                        close the boundary loops of the fused mesh of at most N edges with centroid fans before anything
+                                                        smooths or simplifies it (diff_recon_hip.fill_fused); prints the loops, the filled ones, the open
+                                                        half-edges and boundary edges / pieces / Euler characteristic before -> after
     python examples/train_synthetic.py --eval-mesh --extract-mesh RES --smooth-mesh N
                                                         smooth the fused mesh with N Taubin iterations before anything simplifies it, every vertex within
                                                         one voxel of its level set (diff_recon_hip.smooth_fused); prints its largest displacement in
@@ -221,7 +225,7 @@ def train(rasterizer="2D", iters=200, triangles=20000, width=256, height=192, se
 
 
 def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, height=192, seed=0, views=2, refine=False, weld=None, geometry=None, surface=None,
-                visible=False, extract=None, extract_color=False, simplify=None, min_piece=0, smooth=None):
+                visible=False, extract=None, extract_color=False, simplify=None, min_piece=0, smooth=None, fill=None):
     """PSNR / SSIM of the model's opaque mesh -- mesh_from_triangles: one colour per face from the DC coefficients, back faces as reversed
     twins, the soup saveGLB writes -- against the hidden targets of train() called with the same arguments (diff_recon_hip.evaluate_mesh).
     refine: the result also holds "refined", the same scores (plus "kept" and "triangles") of the mesh after a census over these views
@@ -248,7 +252,10 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
     extract_color, "color" (the vertex colours averaged per cluster).
     smooth = N (with extract): the fused mesh is smoothed with N Taubin iterations, every vertex kept within one voxel of its level set
     (diff_recon_hip.smooth_fused), BEFORE it is simplified, and "fused" also holds "smoothed": "iterations", "moved", "max_displacement_voxels", its
-    "topology", "to_soup" and "normals" = diff_recon_hip.mesh_normal_consistency to the soup, with "normals_before", the same of the mesh as fused."""
+    "topology", "to_soup" and "normals" = diff_recon_hip.mesh_normal_consistency to the soup, with "normals_before", the same of the mesh as fused.
+    fill = N (with extract): the boundary loops of the fused mesh of at most N edges are closed with centroid fans (diff_recon_hip.fill_fused)
+    BEFORE it is smoothed or simplified, and "fused" also holds "filled": fill_holes' stats and the "topology" of the filled mesh; "topology",
+    "to_soup" and "to_target" stay those of the mesh as fused."""
     _, _, cams, gts, kw, _, _ = _setup(rasterizer, iters, triangles, width, height, seed, views, 0.0, False, False)
     for cam, gt in zip(cams, gts):
         cam.gt_image = gt
@@ -305,6 +312,9 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
             res["fused"]["color"] = dict(D.evaluate_vertex_colors(cams, fused.vertices, fused.faces, fused.vertex_color, bg_color=kw["bg_color"]),
                                          vertices=int(fused.vertices.shape[0]), coloured=int(fused.color_valid.sum()),
                                          soup={k: res[k] for k in ("mean_psnr", "mean_ssim")})
+        if fill is not None:
+            fused = D.fill_fused(fused, int(fill))
+            res["fused"]["filled"] = dict(fused.stats["fill"], max_loop_edges=int(fill), topology=D.mesh_topology(fused.vertices.shape[0], fused.faces))
         if smooth is not None:
             plain = fused
             fused = D.smooth_fused(plain, volume, iterations=int(smooth))
@@ -327,7 +337,7 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
 def smoothed_report(f):
     """The line --smooth-mesh prints for mesh_scores(...)["fused"]: the smoothed mesh of ["smoothed"] beside the fused one."""
     s, t = f["smoothed"], f["smoothed"]["topology"]
-    same = "unchanged" if t == f["topology"] else "CHANGED"
+    same = "unchanged" if t == (f["filled"]["topology"] if "filled" in f else f["topology"]) else "CHANGED"
     if s["to_soup"] is None:
         return [f"smoothed mesh, {s['iterations']} Taubin iterations: no surface was extracted"]
     g, n, b = s["to_soup"], s["normals"], s["normals_before"]
@@ -335,6 +345,14 @@ def smoothed_report(f):
             f"soup: accuracy {g['accuracy']:.4g}, completeness {g['completeness']:.4g}, Chamfer {g['chamfer']:.4g}, normal consistency "
             f"{n['abs_normal_consistency']:.4f} (as fused: {b['abs_normal_consistency']:.4f}); topology {same} ({t['faces']} faces, {t['boundary']} boundary edges, "
             f"{t['pieces']} pieces, Euler characteristic {t['euler']})"]
+
+
+def filled_report(f):
+    """The line --fill-holes prints for mesh_scores(...)["fused"]: the filled mesh of ["filled"] beside the fused one."""
+    s, b, a = f["filled"], f["topology"], f["filled"]["topology"]
+    return [f"filled mesh, loops of up to {s['max_loop_edges']} edges: {s['loops']} loops, {s['filled_loops']} filled ({s['new_vertices']} vertices and "
+            f"{s['new_faces']} faces added), {s['open_half_edges']} open half-edges; {b['boundary']} -> {a['boundary']} boundary edges, "
+            f"{b['pieces']} -> {a['pieces']} pieces, Euler characteristic {b['euler']} -> {a['euler']}"]
 
 
 def simplified_report(f):
@@ -561,7 +579,14 @@ if __name__ == "__main__":
     ap.add_argument("--smooth-mesh", type=int, default=None, metavar="N", help="with --extract-mesh: smooth the fused mesh with N Taubin iterations before it is simplified, every "
                                                                                "vertex within one voxel of its level set (diff_recon_hip.smooth_fused), and print its "
                                                                                "displacement, surface distance and normal consistency to the soup, and its topology")
+    ap.add_argument("--fill-holes", type=int, default=None, metavar="N", help="with --extract-mesh: close the boundary loops of the fused mesh of at most N edges with centroid "
+                                                                              "fans (diff_recon_hip.fill_fused) before it is smoothed or simplified, and print the loops, "
+                                                                              "the filled ones, the open half-edges and the topology before and after")
     a = ap.parse_args()
+    if a.fill_holes is not None and a.extract_mesh is None:
+        ap.error("--fill-holes fills the holes of the mesh of --extract-mesh")
+    if a.fill_holes is not None and a.fill_holes < 0:
+        ap.error("--fill-holes needs a number of edges >= 0")
     if a.smooth_mesh is not None and a.extract_mesh is None:
         ap.error("--smooth-mesh smooths the mesh of --extract-mesh")
     if a.smooth_mesh is not None and a.smooth_mesh < 0:
@@ -606,7 +631,7 @@ if __name__ == "__main__":
     if a.eval_mesh:
         res = mesh_scores(m, a.rasterizer, a.iters, a.triangles, views=a.views, refine=a.refine_mesh, weld=a.weld_mesh, geometry=a.eval_geometry,
                           surface=a.eval_surface, visible=a.eval_visible, extract=a.extract_mesh, extract_color=a.extract_color, simplify=a.simplify_mesh,
-                          min_piece=a.min_piece, smooth=a.smooth_mesh)
+                          min_piece=a.min_piece, smooth=a.smooth_mesh, fill=a.fill_holes)
         for v, (p_, s_) in enumerate(zip(res["psnr"], res["ssim"])):
             print(f"  opaque mesh, view {v}: PSNR {p_:.2f} dB  SSIM {s_:.4f}")
         print(f"opaque mesh of {m._vertex.shape[0]} triangles: mean PSNR {res['mean_psnr']:.2f} dB, mean SSIM {res['mean_ssim']:.4f} over {len(res['psnr'])} views")
@@ -628,6 +653,9 @@ if __name__ == "__main__":
                 print(line)
             if a.extract_color:
                 for line in fused_color_report(res["fused"]["color"]):
+                    print(line)
+            if "filled" in res["fused"]:
+                for line in filled_report(res["fused"]):
                     print(line)
             if "smoothed" in res["fused"]:
                 for line in smoothed_report(res["fused"]):

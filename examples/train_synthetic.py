@@ -50,6 +50,11 @@ A "ground truth" is rendered from a hidden set of triangles from several cameras
                                                         (diff_recon_hip.simplify_mesh) and drop the pieces below N faces (drop_small_pieces);
                                                         prints the simplified mesh's faces, topology and surface distance to the soup, and with
                                                         --extract-color its PSNR / SSIM
+    python examples/train_synthetic.py --eval-mesh --extract-mesh RES [--simplify-mesh K] [--fill-holes N] --split-nonmanifold
+                                                        give every extra fan of a vertex a vertex of its own (diff_recon_hip.manifold_fused), after
+                                                        --simplify-mesh / --min-piece and before --fill-holes (which then closes the simplified, split
+                                                        mesh); prints the fans, the split and new vertices, the non-manifold edges before -> after
+                                                        and the same-direction edges
     python examples/train_synthetic.py --eval-mesh --eval-surface N --eval-visible
                                                         those scores over the OBSERVED samples only: the ones that a training camera's centre sees
                                                         past their own mesh (ray casts, diff_recon_hip.point_visibility); prints the hidden counts
@@ -225,7 +230,7 @@ def train(rasterizer="2D", iters=200, triangles=20000, width=256, height=192, se
 
 
 def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, height=192, seed=0, views=2, refine=False, weld=None, geometry=None, surface=None,
-                visible=False, extract=None, extract_color=False, simplify=None, min_piece=0, smooth=None, fill=None):
+                visible=False, extract=None, extract_color=False, simplify=None, min_piece=0, smooth=None, fill=None, split=False):
     """PSNR / SSIM of the model's opaque mesh -- mesh_from_triangles: one colour per face from the DC coefficients, back faces as reversed
     twins, the soup saveGLB writes -- against the hidden targets of train() called with the same arguments (diff_recon_hip.evaluate_mesh).
     refine: the result also holds "refined", the same scores (plus "kept" and "triangles") of the mesh after a census over these views
@@ -255,7 +260,11 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
     "topology", "to_soup" and "normals" = diff_recon_hip.mesh_normal_consistency to the soup, with "normals_before", the same of the mesh as fused.
     fill = N (with extract): the boundary loops of the fused mesh of at most N edges are closed with centroid fans (diff_recon_hip.fill_fused)
     BEFORE it is smoothed or simplified, and "fused" also holds "filled": fill_holes' stats and the "topology" of the filled mesh; "topology",
-    "to_soup" and "to_target" stay those of the mesh as fused."""
+    "to_soup" and "to_target" stay those of the mesh as fused.
+    split (with extract): every extra fan of a vertex gets a vertex of its own (diff_recon_hip.manifold_fused), on the simplified mesh when
+    simplify / min_piece is given and on the fused mesh otherwise, and "fused" also holds "manifold": split_nonmanifold's stats, the "topology"
+    of the split mesh and "before", the topology of the mesh it split.  It runs BEFORE the fill: with simplify / min_piece the fill moves behind
+    the split, onto the simplified mesh, and "filled" then holds its own "before"."""
     _, _, cams, gts, kw, _, _ = _setup(rasterizer, iters, triangles, width, height, seed, views, 0.0, False, False)
     for cam, gt in zip(cams, gts):
         cam.gt_image = gt
@@ -312,9 +321,16 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
             res["fused"]["color"] = dict(D.evaluate_vertex_colors(cams, fused.vertices, fused.faces, fused.vertex_color, bg_color=kw["bg_color"]),
                                          vertices=int(fused.vertices.shape[0]), coloured=int(fused.color_valid.sum()),
                                          soup={k: res[k] for k in ("mean_psnr", "mean_ssim")})
-        if fill is not None:
+        topology_of = lambda mesh: D.mesh_topology(mesh.vertices.shape[0], mesh.faces)
+        if split and not simplified:
+            before = res["fused"]["topology"]
+            fused = D.manifold_fused(fused)
+            res["fused"]["manifold"] = dict(fused.stats["manifold"], before=before, topology=topology_of(fused))
+        if fill is not None and not (split and simplified):
             fused = D.fill_fused(fused, int(fill))
             res["fused"]["filled"] = dict(fused.stats["fill"], max_loop_edges=int(fill), topology=D.mesh_topology(fused.vertices.shape[0], fused.faces))
+            if split:
+                res["fused"]["filled"]["before"] = res["fused"]["manifold"]["topology"]
         if smooth is not None:
             plain = fused
             fused = D.smooth_fused(plain, volume, iterations=int(smooth))
@@ -331,13 +347,22 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
             if extract_color:
                 res["fused"]["simplified"]["color"] = dict(D.evaluate_vertex_colors(cams, sv, sf, small.vertex_color, bg_color=kw["bg_color"]),
                                                            vertices=int(sv.shape[0]), coloured=int(small.color_valid.sum()))
+            if split:
+                small = D.manifold_fused(small)
+                res["fused"]["manifold"] = dict(small.stats["manifold"], before=res["fused"]["simplified"]["topology"], topology=topology_of(small))
+                if fill is not None:
+                    small = D.fill_fused(small, int(fill))
+                    res["fused"]["filled"] = dict(small.stats["fill"], max_loop_edges=int(fill), before=res["fused"]["manifold"]["topology"],
+                                                  topology=topology_of(small))
     return res
 
 
 def smoothed_report(f):
     """The line --smooth-mesh prints for mesh_scores(...)["fused"]: the smoothed mesh of ["smoothed"] beside the fused one."""
     s, t = f["smoothed"], f["smoothed"]["topology"]
-    same = "unchanged" if t == (f["filled"]["topology"] if "filled" in f else f["topology"]) else "CHANGED"
+    late = "manifold" in f and "simplified" in f  # the split and the fill then follow the simplification: neither comes before the smoothing
+    ahead = f["topology"] if late else f.get("filled", f.get("manifold", f))["topology"]
+    same = "unchanged" if t == ahead else "CHANGED"
     if s["to_soup"] is None:
         return [f"smoothed mesh, {s['iterations']} Taubin iterations: no surface was extracted"]
     g, n, b = s["to_soup"], s["normals"], s["normals_before"]
@@ -349,10 +374,17 @@ def smoothed_report(f):
 
 def filled_report(f):
     """The line --fill-holes prints for mesh_scores(...)["fused"]: the filled mesh of ["filled"] beside the fused one."""
-    s, b, a = f["filled"], f["topology"], f["filled"]["topology"]
+    s, b, a = f["filled"], f["filled"].get("before", f["topology"]), f["filled"]["topology"]
     return [f"filled mesh, loops of up to {s['max_loop_edges']} edges: {s['loops']} loops, {s['filled_loops']} filled ({s['new_vertices']} vertices and "
             f"{s['new_faces']} faces added), {s['open_half_edges']} open half-edges; {b['boundary']} -> {a['boundary']} boundary edges, "
             f"{b['pieces']} -> {a['pieces']} pieces, Euler characteristic {b['euler']} -> {a['euler']}"]
+
+
+def manifold_report(f):
+    """The line --split-nonmanifold prints for mesh_scores(...)["fused"]: the split mesh of ["manifold"] beside the mesh it split."""
+    s, b, a = f["manifold"], f["manifold"]["before"], f["manifold"]["topology"]
+    return [f"manifold mesh: {s['fans']} fans, {s['split_vertices']} vertices split, {s['new_vertices']} new vertices; {b['nonmanifold']} -> "
+            f"{a['nonmanifold']} non-manifold edges, {s['same_direction_edges']} same-direction edges"]
 
 
 def simplified_report(f):
@@ -582,7 +614,13 @@ if __name__ == "__main__":
     ap.add_argument("--fill-holes", type=int, default=None, metavar="N", help="with --extract-mesh: close the boundary loops of the fused mesh of at most N edges with centroid "
                                                                               "fans (diff_recon_hip.fill_fused) before it is smoothed or simplified, and print the loops, "
                                                                               "the filled ones, the open half-edges and the topology before and after")
+    ap.add_argument("--split-nonmanifold", action="store_true", help="with --extract-mesh: give every extra fan of a vertex a vertex of its own "
+                                                                     "(diff_recon_hip.manifold_fused) after --simplify-mesh / --min-piece and before --fill-holes, "
+                                                                     "and print the fans, the split and new vertices, the non-manifold edges before and after and the "
+                                                                     "same-direction edges")
     a = ap.parse_args()
+    if a.split_nonmanifold and a.extract_mesh is None:
+        ap.error("--split-nonmanifold splits the vertices of the mesh of --extract-mesh")
     if a.fill_holes is not None and a.extract_mesh is None:
         ap.error("--fill-holes fills the holes of the mesh of --extract-mesh")
     if a.fill_holes is not None and a.fill_holes < 0:
@@ -631,7 +669,7 @@ if __name__ == "__main__":
     if a.eval_mesh:
         res = mesh_scores(m, a.rasterizer, a.iters, a.triangles, views=a.views, refine=a.refine_mesh, weld=a.weld_mesh, geometry=a.eval_geometry,
                           surface=a.eval_surface, visible=a.eval_visible, extract=a.extract_mesh, extract_color=a.extract_color, simplify=a.simplify_mesh,
-                          min_piece=a.min_piece, smooth=a.smooth_mesh, fill=a.fill_holes)
+                          min_piece=a.min_piece, smooth=a.smooth_mesh, fill=a.fill_holes, split=a.split_nonmanifold)
         for v, (p_, s_) in enumerate(zip(res["psnr"], res["ssim"])):
             print(f"  opaque mesh, view {v}: PSNR {p_:.2f} dB  SSIM {s_:.4f}")
         print(f"opaque mesh of {m._vertex.shape[0]} triangles: mean PSNR {res['mean_psnr']:.2f} dB, mean SSIM {res['mean_ssim']:.4f} over {len(res['psnr'])} views")
@@ -654,7 +692,11 @@ if __name__ == "__main__":
             if a.extract_color:
                 for line in fused_color_report(res["fused"]["color"]):
                     print(line)
-            if "filled" in res["fused"]:
+            late = "manifold" in res["fused"] and "simplified" in res["fused"]  # the split, and the fill behind it, follow the simplification
+            if "manifold" in res["fused"] and not late:
+                for line in manifold_report(res["fused"]):
+                    print(line)
+            if "filled" in res["fused"] and not late:
                 for line in filled_report(res["fused"]):
                     print(line)
             if "smoothed" in res["fused"]:
@@ -663,3 +705,9 @@ if __name__ == "__main__":
             if "simplified" in res["fused"]:
                 for line in simplified_report(res["fused"]["simplified"]):
                     print(line)
+            if late:
+                for line in manifold_report(res["fused"]):
+                    print(line)
+                if "filled" in res["fused"]:
+                    for line in filled_report(res["fused"]):
+                        print(line)

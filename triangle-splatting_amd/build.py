@@ -6,12 +6,13 @@ libts_volume.so (include/ts_volume.h: the TSDF volume and the marching tetrahedr
 libts_color.so (include/ts_color.h: the colour volume, the grid sampler and the vertex-attribute pass of diff_recon_hip/color_volume.py, COLOR_SOURCES alone) and
 libts_simplify.so (include/ts_simplify.h: the vertex clustering, the quadric placement and the duplicate-face sweep of diff_recon_hip/mesh_simplify.py, SIMPLIFY_SOURCES + the radix_sort object) and
 libts_smooth.so (include/ts_smooth.h: the one-ring adjacency, the Taubin smoothing and the face / vertex normals of diff_recon_hip/mesh_smooth.py, SMOOTH_SOURCES + the radix_sort object) and
-libts_holes.so (include/ts_holes.h: the boundary loops and the centroid fans of diff_recon_hip/mesh_holes.py, HOLES_SOURCES alone).
+libts_holes.so (include/ts_holes.h: the boundary loops and the centroid fans of diff_recon_hip/mesh_holes.py, HOLES_SOURCES alone) and
+libts_manifold.so (include/ts_manifold.h: the vertex fans and the non-manifold split of diff_recon_hip/mesh_manifold.py, MANIFOLD_SOURCES + the radix_sort object).
 
     python triangle-splatting_amd/build.py [--force] [--verbose] [--lab]
     python triangle-splatting_amd/build.py --variant TAG [--lab] [--all "FLAGS"] [--unit NAME="FLAGS" ...]
 
-Output: triangle-splatting_amd/diff_triangle_rasterization_2D/libts2d.so, triangle-splatting_amd/diff_recon_hip/libts_geom.so, libts_bvh.so, libts_ray.so, libts_volume.so, libts_color.so, libts_simplify.so, libts_smooth.so and libts_holes.so, and the torch extension bindings/_ts2d_torch_C.so (bindings/
+Output: triangle-splatting_amd/diff_triangle_rasterization_2D/libts2d.so, triangle-splatting_amd/diff_recon_hip/libts_geom.so, libts_bvh.so, libts_ray.so, libts_volume.so, libts_color.so, libts_simplify.so, libts_smooth.so, libts_holes.so and libts_manifold.so, and the torch extension bindings/_ts2d_torch_C.so (bindings/
 ts2d_torch_ext.cpp, linked -lts2d with an $ORIGIN-relative runpath), both git-ignored.  Every library carries the soname libts2d.so, so the
 extension's dependency on libts2d.so is met by whichever of them _C.py loaded first (TS2D_LIBRARY_PATH).
 --lab builds tools/bin/libts2d_lab.so as well: the same objects + the test hooks of tools/lab/lab_hooks.hip and api.hip compiled with
@@ -130,10 +131,16 @@ HOLES_SOURCES = {  # libts_holes.so only (include/ts_holes.h): a ninth product l
     "api_holes.hip": [],                      # its C ABI and its own error text
 }
 HOLES_LIB = os.path.join(HERE, "diff_recon_hip", "libts_holes.so")  # it links no product object: there is no HOLES_SHARED
+MANIFOLD_SOURCES = {  # libts_manifold.so only (include/ts_manifold.h): a tenth product library, the export lists of the other nine are closed
+    "mesh_manifold.hip": [],  # vertex fans by sort and union-find, the split: integers only, so no floating-point flag is needed
+    "api_manifold.hip": [],   # its C ABI and its own error text
+}
+MANIFOLD_SHARED = ["radix_sort"]  # the two sorts of the half-edge records
+MANIFOLD_LIB = os.path.join(HERE, "diff_recon_hip", "libts_manifold.so")
 BIN_DIR = os.path.join(os.path.dirname(HERE), "tools", "bin")
 LAB_LIB = os.path.join(BIN_DIR, "libts2d_lab.so")
 LAB_SRC = os.path.join(os.path.dirname(HERE), "tools", "lab")  # lab_hooks.hip: the test hooks, outside the product's csrc/; it includes csrc's headers (-I)
-HEADERS = ["ts2d_common.h", "ts2d_radix.h", "ts2d_api.h", "ts_knn_front.h", "ts_weld_launch.h", "ts_geom_launch.h", "ts_bvh_launch.h", "ts_bvh_layout.h", "ts_ray_launch.h", "ts_volume_launch.h", "ts_color_launch.h", "ts_simplify_launch.h", "ts_smooth_launch.h", "ts_holes_launch.h", "ts2d_lab.h", "ts2d_math.h", "ts2d_wave.h", "ts2d_group.h", "ts2d_support.h", "ts2d_sh.h", "ts2d_stage.h", "ts2d_preprocess_launch.h", "ts2d_imgops.h", "ts2d_select.h", "ts2d_tri.h", os.path.join("..", "..", "include", "ts2d.h"),
+HEADERS = ["ts2d_common.h", "ts2d_radix.h", "ts2d_api.h", "ts_knn_front.h", "ts_weld_launch.h", "ts_geom_launch.h", "ts_bvh_launch.h", "ts_bvh_layout.h", "ts_ray_launch.h", "ts_volume_launch.h", "ts_color_launch.h", "ts_simplify_launch.h", "ts_smooth_launch.h", "ts_holes_launch.h", "ts_manifold_launch.h", "ts_union_find.h", "ts2d_lab.h", "ts2d_math.h", "ts2d_wave.h", "ts2d_group.h", "ts2d_support.h", "ts2d_sh.h", "ts2d_stage.h", "ts2d_preprocess_launch.h", "ts2d_imgops.h", "ts2d_select.h", "ts2d_tri.h", os.path.join("..", "..", "include", "ts2d.h"),
            os.path.join("..", "..", "include", "ts_loss.h"),
            os.path.join("..", "..", "include", "ts_knn.h"),
            os.path.join("..", "..", "include", "ts_model.h"),
@@ -147,7 +154,8 @@ HEADERS = ["ts2d_common.h", "ts2d_radix.h", "ts2d_api.h", "ts_knn_front.h", "ts_
            os.path.join("..", "..", "include", "ts_color.h"),
            os.path.join("..", "..", "include", "ts_simplify.h"),
            os.path.join("..", "..", "include", "ts_smooth.h"),
-           os.path.join("..", "..", "include", "ts_holes.h")]
+           os.path.join("..", "..", "include", "ts_holes.h"),
+           os.path.join("..", "..", "include", "ts_manifold.h")]
 
 
 def hipcc() -> str:
@@ -362,6 +370,24 @@ def holes_objects() -> list:
     return [_object(u) for u in holes_units()]
 
 
+def manifold_units() -> list:
+    """The translation units of libts_manifold.so that are its own (MANIFOLD_SOURCES); it links the objects of MANIFOLD_SHARED besides."""
+    return [_unit(k) for k in MANIFOLD_SOURCES]
+
+
+def manifold_command(unit: str, cc: str = "hipcc") -> list:
+    """The compile command of one unit of MANIFOLD_SOURCES: COMMON + its flags, like command()."""
+    table = {_unit(k): (k, v) for k, v in MANIFOLD_SOURCES.items()}
+    if unit not in table:
+        raise ValueError(f"unknown unit {unit!r}; the units of libts_manifold.so are {', '.join(table)}")
+    key, flags = table[unit]
+    return [cc, *COMMON, *flags, "-c", os.path.join(CSRC, key), "-o", _object(unit)]
+
+
+def manifold_objects() -> list:
+    return [_object(u) for u in manifold_units()] + [_object(u) for u in MANIFOLD_SHARED]
+
+
 def ext_command(cc: str = "hipcc") -> list:
     """The build command of the torch extension (the reference's ext.cpp signatures plus the package's *_ex entry points over the C ABI)."""
     import sysconfig
@@ -400,11 +426,11 @@ def build(force: bool = False, verbose: bool = False, lab: bool = False, variant
     hdr_t = max(_newest_header(), os.path.getmtime(me))
     jobs = []
     cmds = [command(u, extra.get(u, ()), variant, cc) for u in known]
-    if variant is None:  # the other eight product libraries: include/ts_geom.h, ts_bvh.h, ts_ray.h, ts_volume.h, ts_color.h, ts_simplify.h, ts_smooth.h, ts_holes.h
+    if variant is None:  # the other nine product libraries: include/ts_geom.h, ts_bvh.h, ts_ray.h, ts_volume.h, ts_color.h, ts_simplify.h, ts_smooth.h, ts_holes.h, ts_manifold.h
         cmds += [geom_command(u, cc) for u in geom_units()] + [bvh_command(u, cc) for u in bvh_units()] + [ray_command(u, cc) for u in ray_units()]
         cmds += [volume_command(u, cc) for u in volume_units()] + [color_command(u, cc) for u in color_units()]
         cmds += [simplify_command(u, cc) for u in simplify_units()] + [smooth_command(u, cc) for u in smooth_units()]
-        cmds += [holes_command(u, cc) for u in holes_units()]
+        cmds += [holes_command(u, cc) for u in holes_units()] + [manifold_command(u, cc) for u in manifold_units()]
     for cmd in cmds:
         s, o = cmd[-3], cmd[-1]
         os.makedirs(os.path.dirname(o), exist_ok=True)
@@ -441,7 +467,8 @@ def build(force: bool = False, verbose: bool = False, lab: bool = False, variant
                               (COLOR_LIB, "libts_color.so", color_objects()),
                               (SIMPLIFY_LIB, "libts_simplify.so", simplify_objects()),
                               (SMOOTH_LIB, "libts_smooth.so", smooth_objects()),
-                              (HOLES_LIB, "libts_holes.so", holes_objects())) if variant is None else ():
+                              (HOLES_LIB, "libts_holes.so", holes_objects()),
+                              (MANIFOLD_LIB, "libts_manifold.so", manifold_objects())) if variant is None else ():
         cmd = [cc, "-shared", "-fPIC", f"--offload-arch={ARCH}", f"-Wl,-soname,{soname}", "-o", out, *objs]
         key = tool + "\n" + " ".join(cmd)
         if force or compiled.intersection(objs) or not _fresh(out, key, max(os.path.getmtime(o) for o in objs)):

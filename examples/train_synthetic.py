@@ -55,6 +55,10 @@ A "ground truth" is rendered from a hidden set of triangles from several cameras
                                                         --simplify-mesh / --min-piece and before --fill-holes (which then closes the simplified, split
                                                         mesh); prints the fans, the split and new vertices, the non-manifold edges before -> after
                                                         and the same-direction edges
+    python examples/train_synthetic.py --eval-mesh {--extract-mesh RES [--split-nonmanifold] [--fill-holes N] | --weld-mesh EPS} --orient-faces {anchor,majority,volume}
+                                                        make every orientable piece of the mesh wind one way (diff_recon_hip.orient_fused): after
+                                                        --split-nonmanifold and before --fill-holes, or on the welded mesh; prints the pieces, the
+                                                        non-orientable ones, the same-direction edges before -> after and the faces flipped
     python examples/train_synthetic.py --eval-mesh --eval-surface N --eval-visible
                                                         those scores over the OBSERVED samples only: the ones that a training camera's centre sees
                                                         past their own mesh (ray casts, diff_recon_hip.point_visibility); prints the hidden counts
@@ -230,7 +234,7 @@ def train(rasterizer="2D", iters=200, triangles=20000, width=256, height=192, se
 
 
 def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, height=192, seed=0, views=2, refine=False, weld=None, geometry=None, surface=None,
-                visible=False, extract=None, extract_color=False, simplify=None, min_piece=0, smooth=None, fill=None, split=False):
+                visible=False, extract=None, extract_color=False, simplify=None, min_piece=0, smooth=None, fill=None, split=False, orient=None):
     """PSNR / SSIM of the model's opaque mesh -- mesh_from_triangles: one colour per face from the DC coefficients, back faces as reversed
     twins, the soup saveGLB writes -- against the hidden targets of train() called with the same arguments (diff_recon_hip.evaluate_mesh).
     refine: the result also holds "refined", the same scores (plus "kept" and "triangles") of the mesh after a census over these views
@@ -264,7 +268,10 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
     split (with extract): every extra fan of a vertex gets a vertex of its own (diff_recon_hip.manifold_fused), on the simplified mesh when
     simplify / min_piece is given and on the fused mesh otherwise, and "fused" also holds "manifold": split_nonmanifold's stats, the "topology"
     of the split mesh and "before", the topology of the mesh it split.  It runs BEFORE the fill: with simplify / min_piece the fill moves behind
-    the split, onto the simplified mesh, and "filled" then holds its own "before"."""
+    the split, onto the simplified mesh, and "filled" then holds its own "before".
+    orient = "anchor" / "majority" / "volume": the faces of every orientable piece are made to wind one way (diff_recon_hip.orient_fused).  With
+    extract it runs where the fill runs, behind the split and before the fill, and "fused" also holds "oriented": orient_faces' stats; with weld
+    it runs on the welded mesh and "welded" also holds "oriented".  No other entry changes."""
     _, _, cams, gts, kw, _, _ = _setup(rasterizer, iters, triangles, width, height, seed, views, 0.0, False, False)
     for cam, gt in zip(cams, gts):
         cam.gt_image = gt
@@ -284,6 +291,8 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
         res["welded"] = dict(D.evaluate_mesh(cams, w.vertices, w.faces, w.faces_color, bg_color=kw["bg_color"]), stats=w.stats,
                              topology=D.mesh_topology(w.stats["num_vertices"], w.faces), eps=float(weld),
                              soup={k: soup[k] for k in ("mean_psnr", "mean_ssim")})
+        if orient is not None:
+            res["welded"]["oriented"] = D.orient_fused(w, orient).stats["orient"]
     if geometry is not None or surface is not None:
         target = torch.from_numpy(np.ascontiguousarray(synthetic.scene(triangles, width, height, 2, seed=seed, edge_px=10.0)["vertex"])).to(m._vertex.device)
         edges = (target - target.roll(1, dims=1)).norm(dim=2)  # the hidden scene of _setup: every draw comes from the seeded generator
@@ -326,6 +335,9 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
             before = res["fused"]["topology"]
             fused = D.manifold_fused(fused)
             res["fused"]["manifold"] = dict(fused.stats["manifold"], before=before, topology=topology_of(fused))
+        if orient is not None and not (split and simplified):
+            fused = D.orient_fused(fused, orient)
+            res["fused"]["oriented"] = fused.stats["orient"]
         if fill is not None and not (split and simplified):
             fused = D.fill_fused(fused, int(fill))
             res["fused"]["filled"] = dict(fused.stats["fill"], max_loop_edges=int(fill), topology=D.mesh_topology(fused.vertices.shape[0], fused.faces))
@@ -350,6 +362,9 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
             if split:
                 small = D.manifold_fused(small)
                 res["fused"]["manifold"] = dict(small.stats["manifold"], before=res["fused"]["simplified"]["topology"], topology=topology_of(small))
+                if orient is not None:
+                    small = D.orient_fused(small, orient)
+                    res["fused"]["oriented"] = small.stats["orient"]
                 if fill is not None:
                     small = D.fill_fused(small, int(fill))
                     res["fused"]["filled"] = dict(small.stats["fill"], max_loop_edges=int(fill), before=res["fused"]["manifold"]["topology"],
@@ -385,6 +400,12 @@ def manifold_report(f):
     s, b, a = f["manifold"], f["manifold"]["before"], f["manifold"]["topology"]
     return [f"manifold mesh: {s['fans']} fans, {s['split_vertices']} vertices split, {s['new_vertices']} new vertices; {b['nonmanifold']} -> "
             f"{a['nonmanifold']} non-manifold edges, {s['same_direction_edges']} same-direction edges"]
+
+
+def oriented_report(s, what="fused"):
+    """The line --orient-faces prints for mesh_scores(...)["fused"]["oriented"] or ["welded"]["oriented"]."""
+    return [f"oriented {what} mesh, outward by {s['outward']}: {s['pieces']} pieces, {s['nonorientable_pieces']} non-orientable; "
+            f"{s['same_direction_before']} -> {s['same_direction_after']} same-direction edges, {s['faces_flipped']} of {s['faces']} faces flipped"]
 
 
 def simplified_report(f):
@@ -618,7 +639,13 @@ if __name__ == "__main__":
                                                                      "(diff_recon_hip.manifold_fused) after --simplify-mesh / --min-piece and before --fill-holes, "
                                                                      "and print the fans, the split and new vertices, the non-manifold edges before and after and the "
                                                                      "same-direction edges")
+    ap.add_argument("--orient-faces", choices=("anchor", "majority", "volume"), default=None,
+                    help="with --extract-mesh: make every orientable piece of the mesh wind one way (diff_recon_hip.orient_fused) after --split-nonmanifold "
+                         "and before --fill-holes; with --weld-mesh: the same on the welded mesh; print the pieces, the non-orientable ones, the "
+                         "same-direction edges before and after and the faces flipped")
     a = ap.parse_args()
+    if a.orient_faces is not None and a.extract_mesh is None and a.weld_mesh is None:
+        ap.error("--orient-faces orients the mesh of --extract-mesh or of --weld-mesh")
     if a.split_nonmanifold and a.extract_mesh is None:
         ap.error("--split-nonmanifold splits the vertices of the mesh of --extract-mesh")
     if a.fill_holes is not None and a.extract_mesh is None:
@@ -669,7 +696,7 @@ if __name__ == "__main__":
     if a.eval_mesh:
         res = mesh_scores(m, a.rasterizer, a.iters, a.triangles, views=a.views, refine=a.refine_mesh, weld=a.weld_mesh, geometry=a.eval_geometry,
                           surface=a.eval_surface, visible=a.eval_visible, extract=a.extract_mesh, extract_color=a.extract_color, simplify=a.simplify_mesh,
-                          min_piece=a.min_piece, smooth=a.smooth_mesh, fill=a.fill_holes, split=a.split_nonmanifold)
+                          min_piece=a.min_piece, smooth=a.smooth_mesh, fill=a.fill_holes, split=a.split_nonmanifold, orient=a.orient_faces)
         for v, (p_, s_) in enumerate(zip(res["psnr"], res["ssim"])):
             print(f"  opaque mesh, view {v}: PSNR {p_:.2f} dB  SSIM {s_:.4f}")
         print(f"opaque mesh of {m._vertex.shape[0]} triangles: mean PSNR {res['mean_psnr']:.2f} dB, mean SSIM {res['mean_ssim']:.4f} over {len(res['psnr'])} views")
@@ -680,6 +707,9 @@ if __name__ == "__main__":
         if a.weld_mesh is not None:
             for line in weld_report(res["welded"]):
                 print(line)
+            if "oriented" in res["welded"]:
+                for line in oriented_report(res["welded"]["oriented"], "welded"):
+                    print(line)
         if a.eval_geometry is not None:
             for line in geometry_report(res["geometry"]):
                 print(line)
@@ -696,6 +726,9 @@ if __name__ == "__main__":
             if "manifold" in res["fused"] and not late:
                 for line in manifold_report(res["fused"]):
                     print(line)
+            if "oriented" in res["fused"] and not late:
+                for line in oriented_report(res["fused"]["oriented"]):
+                    print(line)
             if "filled" in res["fused"] and not late:
                 for line in filled_report(res["fused"]):
                     print(line)
@@ -708,6 +741,9 @@ if __name__ == "__main__":
             if late:
                 for line in manifold_report(res["fused"]):
                     print(line)
+                if "oriented" in res["fused"]:
+                    for line in oriented_report(res["fused"]["oriented"]):
+                        print(line)
                 if "filled" in res["fused"]:
                     for line in filled_report(res["fused"]):
                         print(line)

@@ -75,6 +75,11 @@
                           split_nonmanifold / manifold_fused (every extra fan of a vertex gets a vertex of its own: the result is
                           edge-manifold and vertex-manifold, positions and attributes copied bit for bit; bit-equal to a numpy reference)
                           -- the pass between simplify_mesh and fill_holes; no counterpart in the reference; loaded on first use
+    mesh_orient.py        orient_faces / orient_fused (every orientable piece of an indexed mesh made to wind one way: the faces linked through
+                          edges that exactly two of them use, pieces and flip parities by a lock-free union-find over the doubled graph,
+                          non-orientable pieces reported and left alone; the piece faces by its anchor, by majority or by the sign of its
+                          quantised volume; bit-equal to a numpy reference) -- the pass between split_nonmanifold and fill_holes; no
+                          counterpart in the reference; loaded on first use
     metrics.py           psnr, ssim (= 1 - SSIMLoss), evaluate_mesh and evaluate_vertex_colors: PSNR / SSIM of a mesh's opaque render (one
                           colour per face, or per vertex) against each view's gt_image
                           (reference: src/diff_recon/trainers/trainer_utils.py:331-336, VanillaTS_trainer.py:156-190)
@@ -82,7 +87,7 @@
                           replayed with one launch -- no counterpart in the reference, whose forward reads num_rendered back every step
 
 Native code: libts2d.so (include/ts_loss.h, include/ts_model.h, include/ts_optim.h, include/ts2d.h, include/ts_mesh.h, include/ts_weld.h) and, for
-mesh_distance.py, libts_geom.so beside this file (include/ts_geom.h), for mesh_surface.py, libts_bvh.so (include/ts_bvh.h), for mesh_ray.py, libts_ray.so (include/ts_ray.h), for volume.py, libts_volume.so (include/ts_volume.h), for color_volume.py, libts_color.so (include/ts_color.h), for mesh_simplify.py, libts_simplify.so (include/ts_simplify.h), for mesh_smooth.py, libts_smooth.so (include/ts_smooth.h), for mesh_holes.py, libts_holes.so (include/ts_holes.h), for mesh_manifold.py, libts_manifold.so (include/ts_manifold.h).  No CPU / eager fallback anywhere.
+mesh_distance.py, libts_geom.so beside this file (include/ts_geom.h), for mesh_surface.py, libts_bvh.so (include/ts_bvh.h), for mesh_ray.py, libts_ray.so (include/ts_ray.h), for volume.py, libts_volume.so (include/ts_volume.h), for color_volume.py, libts_color.so (include/ts_color.h), for mesh_simplify.py, libts_simplify.so (include/ts_simplify.h), for mesh_smooth.py, libts_smooth.so (include/ts_smooth.h), for mesh_holes.py, libts_holes.so (include/ts_holes.h), for mesh_manifold.py, libts_manifold.so (include/ts_manifold.h), for mesh_orient.py, libts_orient.so (include/ts_orient.h).  No CPU / eager fallback anywhere.
 """
 from .losses import L1, SSIMLoss, ssimLoss, PhotometricLoss, photometric_loss, DepthNormalLoss, DoGLoss, SmoothnessLoss, dogLoss, smoothnessLoss, downsample_bilinear, downsample_bilinear_many  # noqa: F401
 from .triangle_renderer import TriangleRenderer  # noqa: F401
@@ -113,6 +118,7 @@ _SMOOTH_NAMES = ("MeshAdjacency", "SmoothedMesh", "vertex_adjacency", "smooth_me
                  "mesh_normal_consistency", "save_glb_shaded_mesh")
 _HOLES_NAMES = ("BoundaryLoops", "FilledMesh", "boundary_loops", "loop_vertices", "fill_holes", "fill_fused")
 _MANIFOLD_NAMES = ("VertexFans", "ManifoldMesh", "vertex_fans", "split_nonmanifold", "manifold_fused")
+_ORIENT_NAMES = ("OrientedMesh", "orient_faces", "orient_fused")
 
 
 def __getattr__(name):
@@ -145,4 +151,8 @@ def __getattr__(name):
         import importlib
         module = importlib.import_module(".mesh_manifold", __name__)
         return module if name == "mesh_manifold" else getattr(module, name)
+    if name in _ORIENT_NAMES or name == "mesh_orient":  # mesh_orient.py and libts_orient.so likewise
+        import importlib
+        module = importlib.import_module(".mesh_orient", __name__)
+        return module if name == "mesh_orient" else getattr(module, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,5 +1,5 @@
 """The C ABI of libts2d.so as ctypes sees it, declared once: the mirrors of the structs of include/*.h and the signature of every function
-they declare (and of the lab library's additions, csrc/ts2d_lab.h, and of the other nine product libraries: libts_geom.so, include/ts_geom.h, libts_bvh.so, include/ts_bvh.h, libts_ray.so, include/ts_ray.h, libts_volume.so, include/ts_volume.h, libts_color.so, include/ts_color.h, libts_simplify.so, include/ts_simplify.h, libts_smooth.so, include/ts_smooth.h, libts_holes.so, include/ts_holes.h, and libts_manifold.so, include/ts_manifold.h).  Pure ctypes: no torch, no library is loaded here -- `_C.py` binds the
+they declare (and of the lab library's additions, csrc/ts2d_lab.h, and of the other ten product libraries: libts_geom.so, include/ts_geom.h, libts_bvh.so, include/ts_bvh.h, libts_ray.so, include/ts_ray.h, libts_volume.so, include/ts_volume.h, libts_color.so, include/ts_color.h, libts_simplify.so, include/ts_simplify.h, libts_smooth.so, include/ts_smooth.h, libts_holes.so, include/ts_holes.h, libts_manifold.so, include/ts_manifold.h, and libts_orient.so, include/ts_orient.h).  Pure ctypes: no torch, no library is loaded here -- `_C.py` binds the
 library the package loads, the CPU tests bind a CDLL of their own.  tests/test_cabi_cpu.py holds both tables against the headers: the structs
 by sizeof / offsetof, the functions prototype by prototype.
 
@@ -383,6 +383,26 @@ def bind_manifold(lib):
     if missing:
         raise ImportError(f"{getattr(lib, '_name', lib)} does not export {', '.join(missing)}: rebuild it with `python triangle-splatting_amd/build.py`")
     for name, (restype, argtypes) in MANIFOLD_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return lib
+
+
+# include/ts_orient.h: the whole C ABI of diff_recon_hip/libts_orient.so, the eleventh library (diff_recon_hip/mesh_orient.py loads and binds it)
+ORIENT_SIGNATURES = {
+    "tsw_last_error": (C.c_char_p, []),
+    "tsw_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "tsw_orient": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+}
+
+
+def bind_orient(lib):
+    """Sets restype and argtypes of every function of include/ts_orient.h on `lib` (a ctypes.CDLL of libts_orient.so); a library that
+    lacks one is refused."""
+    missing = [name for name in ORIENT_SIGNATURES if not hasattr(lib, name)]
+    if missing:
+        raise ImportError(f"{getattr(lib, '_name', lib)} does not export {', '.join(missing)}: rebuild it with `python triangle-splatting_amd/build.py`")
+    for name, (restype, argtypes) in ORIENT_SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     return lib

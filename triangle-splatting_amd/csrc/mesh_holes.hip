@@ -11,128 +11,26 @@
 // previous round; after ceil(log2(n)) rounds, n a bound on the longest chain, a half-edge on a cycle holds the cycle's smallest half-edge and
 // one on a path holds the open flag.  The bound is min(3 F, V + 1): the tails along a chain are distinct vertices.  A second doubling pass
 // (Wyllie) counts the hops to the half-edge in front of the head, the cycle cut there, which gives the rank and, at the head, the length.
-// Heads and lengths are ranked by a prefix sum in the form of ts2d_weld_compact: per-block sums, one workgroup turns them into offsets, then
-// every block ranks its own behind the sum in front of it (nobody waits for anybody).  One scatter writes the CSR.
+// Heads and lengths are ranked by the block-sum prefix sum of two columns (scan_columns<2>, csrc/ts_mesh_scan.h).  One scatter
+// writes the CSR.
 //
 // Fill.  One thread per loop decides its status (the length, the lone face, the finiteness of its vertices), a prefix sum of the same form
 // numbers the new vertices and faces, one thread per loop sums its members' coordinates and attributes in member order, one thread per member
 // finds its loop by a search in loop_offsets and writes its face.
-#include "ts2d_common.h"
 #include "ts_holes_launch.h"
-
-#include <algorithm>
+#include "ts_mesh_scan.h"
 
 namespace
 {
-constexpr int SCAN_PER = 8, SCAN_TILE = 256 * SCAN_PER;
 constexpr uint32_t OPEN = 0x80000000u, LABEL = 0x7FFFFFFFu; // the second word of a label state: the smallest label and the open flag
 constexpr int32_t NOT_BOUNDARY = -2, NO_SUCCESSOR = -1;     // succ[h] otherwise: the successor
 constexpr uint8_t FILLED = 0, TOO_LONG = 1, LONE_FACE = 2, DEAD = 3; // TSH_FILLED .. TSH_DEAD
-
-inline unsigned blocks256(size_t n) { return (unsigned)((n + 255) / 256); }
 
 int doubling_rounds(size_t n) // ceil(log2(max(n, 2)))
 {
     int r = 1;
     while (r < 31 && ((size_t)1 << r) < n) r++;
     return r;
-}
-
-__device__ __forceinline__ bool finite32(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
-
-// exclusive scan of one value per lane over the 256-lane workgroup; returns the lane's offset, *total the sum
-__device__ __forceinline__ uint32_t block_scan256(uint32_t v, uint32_t *lds, uint32_t *total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1)
-    {
-        const uint32_t t = __shfl_up(incl, d);
-        if (lane >= d) incl += t;
-    }
-    __syncthreads();
-    if (lane == 63) lds[wave] = incl;
-    __syncthreads();
-    uint32_t base = 0, all = 0;
-    for (int w = 0; w < 4; w++) { const uint32_t t = lds[w]; if (w < wave) base += t; all += t; }
-    *total = all;
-    return base + incl - v;
-}
-
-// the wave's sum of n, added to *counter by its first lane
-__device__ __forceinline__ void count_into(unsigned long long *counter, uint32_t n)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
-    if ((threadIdx.x & 63) == 0 && n) __hip_atomic_fetch_add(counter, (unsigned long long)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// ---- the prefix sum of two columns, block-sum form ------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) scan2_count_kernel(size_t n, const uint32_t *__restrict__ a, const uint32_t *__restrict__ b,
-                                                           uint32_t *__restrict__ block_sum)
-{
-    __shared__ uint32_t lds[4];
-    uint32_t sa = 0, sb = 0;
-    const size_t base = (size_t)blockIdx.x * SCAN_TILE + (size_t)threadIdx.x * SCAN_PER;
-#pragma unroll
-    for (int k = 0; k < SCAN_PER; k++)
-        if (base + k < n) { sa += a[base + k]; sb += b[base + k]; }
-    uint32_t ta, tb;
-    block_scan256(sa, lds, &ta);
-    block_scan256(sb, lds, &tb);
-    if (threadIdx.x == 0) { block_sum[2 * (size_t)blockIdx.x] = ta; block_sum[2 * (size_t)blockIdx.x + 1] = tb; }
-}
-
-// one workgroup: block_sum -> exclusive offsets in place, the two totals to total[0], total[1]
-__global__ void __launch_bounds__(256) scan2_offsets_kernel(int nb, uint32_t *block_sum, uint32_t *__restrict__ total)
-{
-    __shared__ uint32_t lds[4];
-    const int span = (nb + 255) / 256, lo = min(nb, (int)threadIdx.x * span), hi = min(nb, lo + span);
-    uint32_t sa = 0, sb = 0;
-    for (int i = lo; i < hi; i++) { sa += block_sum[2 * (size_t)i]; sb += block_sum[2 * (size_t)i + 1]; }
-    uint32_t ta, tb;
-    uint32_t ra = block_scan256(sa, lds, &ta);
-    uint32_t rb = block_scan256(sb, lds, &tb);
-    for (int i = lo; i < hi; i++)
-    {
-        const uint32_t xa = block_sum[2 * (size_t)i], xb = block_sum[2 * (size_t)i + 1];
-        block_sum[2 * (size_t)i] = ra; block_sum[2 * (size_t)i + 1] = rb;
-        ra += xa; rb += xb;
-    }
-    if (threadIdx.x == 0) { total[0] = ta; total[1] = tb; }
-}
-
-// a and b become their exclusive prefix sums, in place: a thread reads its own eight elements before it writes them, nobody else's
-__global__ void __launch_bounds__(256) scan2_apply_kernel(size_t n, uint32_t *a, uint32_t *b, const uint32_t *__restrict__ block_offset)
-{
-    __shared__ uint32_t lds[4];
-    uint32_t va[SCAN_PER], vb[SCAN_PER], sa = 0, sb = 0;
-    const size_t base = (size_t)blockIdx.x * SCAN_TILE + (size_t)threadIdx.x * SCAN_PER;
-#pragma unroll
-    for (int k = 0; k < SCAN_PER; k++)
-    {
-        va[k] = base + k < n ? a[base + k] : 0u;
-        vb[k] = base + k < n ? b[base + k] : 0u;
-        sa += va[k]; sb += vb[k];
-    }
-    uint32_t ta, tb;
-    uint32_t ra = block_offset[2 * (size_t)blockIdx.x] + block_scan256(sa, lds, &ta);
-    uint32_t rb = block_offset[2 * (size_t)blockIdx.x + 1] + block_scan256(sb, lds, &tb);
-#pragma unroll
-    for (int k = 0; k < SCAN_PER; k++)
-    {
-        if (base + k < n) { a[base + k] = ra; b[base + k] = rb; }
-        ra += va[k]; rb += vb[k];
-    }
-}
-
-void scan2(size_t n, uint32_t *a, uint32_t *b, uint32_t *block_sum, uint32_t *total, hipStream_t s)
-{
-    const unsigned nb = (unsigned)((n + SCAN_TILE - 1) / SCAN_TILE);
-    hipLaunchKernelGGL(scan2_count_kernel, dim3(nb), dim3(256), 0, s, n, a, b, block_sum);
-    hipLaunchKernelGGL(scan2_offsets_kernel, dim3(1), dim3(256), 0, s, (int)nb, block_sum, total);
-    hipLaunchKernelGGL(scan2_apply_kernel, dim3(nb), dim3(256), 0, s, n, a, b, block_sum);
 }
 
 // ---- loops -------------------------------------------------------------------------------------------------------------------------------
@@ -146,14 +44,8 @@ __global__ void __launch_bounds__(256) classify_kernel(int V, int F, const int32
     uint32_t nb = 0;
     if (f < F)
     {
-        int32_t v[3] = {0, 0, 0};
-        bool ok = !(keep && !keep[f]);
-        if (ok)
-        {
-            v[0] = faces[3 * (size_t)f]; v[1] = faces[3 * (size_t)f + 1]; v[2] = faces[3 * (size_t)f + 2];
-            ok = (uint32_t)v[0] < (uint32_t)V && (uint32_t)v[1] < (uint32_t)V && (uint32_t)v[2] < (uint32_t)V && v[0] != v[1] && v[1] != v[2] &&
-                 v[0] != v[2];
-        }
+        int32_t v[3];
+        const bool ok = face_takes_part(V, (size_t)f, faces, keep, v);
 #pragma unroll
         for (int k = 0; k < 3; k++)
         {
@@ -449,15 +341,6 @@ __global__ void __launch_bounds__(256) fill_finish_kernel(const uint32_t *__rest
 }
 
 // ---- workspace ---------------------------------------------------------------------------------------------------------------------------
-struct Carver // addresses as integers: the size queries carve from a null workspace, where pointer arithmetic would be undefined
-{
-    size_t p, base;
-    explicit Carver(void *ws) : p(ts_align_up((size_t)ws)), base((size_t)ws) {}
-    uint32_t *words(size_t n) { return (uint32_t *)bytes(n * 4); }
-    void *bytes(size_t n) { const size_t q = p; p += ts_align_up(n); return (void *)q; }
-    size_t used() const { return p - base; }
-};
-
 struct LoopsCarve
 {
     uint32_t *census; // out_count, in_count, out_min: 3 x V words
@@ -475,7 +358,7 @@ LoopsCarve loops_carve(void *ws, size_t V, size_t F)
     c.succ = (int32_t *)w.words(N); c.lab = (int32_t *)w.words(N);
     c.state[0] = (uint2 *)w.words(2 * N); c.state[1] = (uint2 *)w.words(2 * N);
     c.head_flag = w.words(N); c.head_len = w.words(N);
-    c.block_sum = w.words(2 * ((N + SCAN_TILE - 1) / SCAN_TILE));
+    c.block_sum = w.words(2 * scan_blocks(N));
     c.total = w.words(2);
     c.bytes = w.used();
     return c;
@@ -491,7 +374,7 @@ FillCarve fill_carve(void *ws, size_t loops)
     FillCarve c;
     Carver w(ws);
     c.vertex_flag = w.words(loops); c.face_count = w.words(loops);
-    c.block_sum = w.words(2 * ((loops + SCAN_TILE - 1) / SCAN_TILE));
+    c.block_sum = w.words(2 * scan_blocks(loops));
     c.total = w.words(2);
     c.bytes = w.used();
     return c;
@@ -536,7 +419,7 @@ hipError_t ts_holes_loops(int V, int F, const int32_t *faces, const uint8_t *kee
     for (int r = 0; r < rounds; r++, at ^= 1) hipLaunchKernelGGL(rank_round_kernel, dim3(nh), dim3(256), 0, s, N, c.state[at], c.state[at ^ 1]);
     const uint2 *rank = c.state[at];
     hipLaunchKernelGGL(head_values_kernel, dim3(nh), dim3(256), 0, s, N, c.lab, rank, c.head_flag, c.head_len);
-    scan2(N, c.head_flag, c.head_len, c.block_sum, c.total, s);
+    scan_columns<2>(N, {{c.head_flag, c.head_len}}, c.block_sum, c.total, s); // head_index, head_start
     hipLaunchKernelGGL(scatter_kernel, dim3(nh), dim3(256), 0, s, N, F, c.lab, rank, c.head_flag, c.head_len, half_edge_loop, loop_offsets,
                        loop_half_edges);
     hipLaunchKernelGGL(loops_finish_kernel, dim3(blocks256(f + 1)), dim3(256), 0, s, F, c.total, loop_offsets, counts);
@@ -572,7 +455,7 @@ hipError_t ts_holes_fill(int V, int F, const float *vertices, const int32_t *fac
     const unsigned nl = blocks256(loops);
     hipLaunchKernelGGL(fill_status_kernel, dim3(nl), dim3(256), 0, s, V, F, vertices, faces, num_loops, loop_offsets, loop_half_edges, num_members,
                        max_loop_edges, loop_status, c.vertex_flag, c.face_count, totals);
-    scan2(loops, c.vertex_flag, c.face_count, c.block_sum, c.total, s);
+    scan_columns<2>(loops, {{c.vertex_flag, c.face_count}}, c.block_sum, c.total, s); // vertex_index, face_start
     hipLaunchKernelGGL(fill_vertices_kernel, dim3(nl), dim3(256), 0, s, V, F, vertices, faces, num_loops, loop_offsets, loop_half_edges,
                        num_members, attributes, attr_valid, channels, loop_status, c.vertex_flag, new_vertices, new_attributes, new_attr_valid);
     if (members)

@@ -4,128 +4,26 @@
 // No floating-point arithmetic anywhere, so the unit needs no floating-point flags.  The atomics are integer: the compare-exchange and the
 // minimum of the union-find (csrc/ts_union_find.h), the minimum that elects a vertex's keeper, the adds of the counters.
 //
-// Fans.  One thread per face writes its three half-edge records: key max(tail, head), value the half-edge; the sentinel key V for a face
-// that does not take part, which sorts behind every real one.  A stable LSD sort by the larger end, a gather of the smaller end in that
-// order, and a second stable sort by the smaller end (the product's radix passes, only the bits V needs) leave the half-edges in (min, max)
-// order, ascending half-edge inside a run.  One thread per sorted position gathers the larger end again, then one thread per position looks
-// at most two positions ahead: the head of a run of exactly two unites the two corners at either end of the edge in a parent array over
+// Fans.  The sort-by-edge front shared with mesh_orient.hip (csrc/ts_mesh_edges.h) leaves the half-edges of the faces that take part in
+// (min, max) order, ascending half-edge inside a run; the records kernel is this unit's own: it also sets the three parent words of a face
+// and counts the corners.  One thread per sorted position classifies its run (edge_run_head, csrc/ts_mesh_common.h), looking at most two
+// positions ahead: the head of a run of exactly two unites the two corners at either end of the edge in a parent array over
 // the 3 F corners (uf_union; nobody waits for anybody) and counts the pair if both half-edges leave the same vertex; the head of a longer
 // run counts a non-manifold edge and links nothing.  A flatten pass writes corner_fan[c] = root(c), the smallest corner of the fan whatever
 // the order of the unions, and every root adds 1 to its vertex; a vertex pass takes the two vertex counts.
 //
 // Split.  One thread per corner validates its entry of corner_fan (in [0, 3 F), on a face that takes part, on the same vertex), marks the
 // label as used and lowers the vertex's keeper to it.  A used label that is not its vertex's keeper is flagged; one exclusive prefix sum of
-// the 3 F flags in the form of ts2d_weld_compact -- per-block sums, one workgroup turns them into offsets, every block ranks its own behind
-// the sum in front of it -- numbers the new vertices in ascending label.  One thread per label writes the source and the label of a flagged
+// the 3 F flags (scan_columns, csrc/ts_mesh_scan.h: per-block sums, one workgroup turns them into offsets, every block ranks its own behind
+// the sum in front of it) numbers the new vertices in ascending label.  One thread per label writes the source and the label of a flagged
 // one, one thread per corner writes out_faces.
-#include "ts2d_common.h"
 #include "ts_manifold_launch.h"
+#include "ts_mesh_edges.h"
+#include "ts_mesh_scan.h"
 #include "ts_union_find.h"
-
-#include <algorithm>
 
 namespace
 {
-constexpr int SCAN_PER = 8, SCAN_TILE = 256 * SCAN_PER;
-
-inline unsigned blocks256(size_t n) { return (unsigned)((n + 255) / 256); }
-
-int bit_length(uint32_t v)
-{
-    int n = 1; // at least one pass bit
-    while (n < 32 && (v >> n)) n++;
-    return n;
-}
-
-// exclusive scan of one value per lane over the 256-lane workgroup; returns the lane's offset, *total the sum
-__device__ __forceinline__ uint32_t block_scan256(uint32_t v, uint32_t *lds, uint32_t *total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1)
-    {
-        const uint32_t t = __shfl_up(incl, d);
-        if (lane >= d) incl += t;
-    }
-    __syncthreads();
-    if (lane == 63) lds[wave] = incl;
-    __syncthreads();
-    uint32_t base = 0, all = 0;
-    for (int w = 0; w < 4; w++) { const uint32_t t = lds[w]; if (w < wave) base += t; all += t; }
-    *total = all;
-    return base + incl - v;
-}
-
-// the wave's sum of n, added to *counter by its first lane
-__device__ __forceinline__ void count_into(unsigned long long *counter, uint32_t n)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
-    if ((threadIdx.x & 63) == 0 && n) __hip_atomic_fetch_add(counter, (unsigned long long)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// ts_smooth.h's rule: kept, the three indices in [0, V) and pairwise distinct.  f < F.
-__device__ __forceinline__ bool takes_part(int V, size_t f, const int32_t *__restrict__ faces, const uint8_t *__restrict__ keep, int32_t (&v)[3])
-{
-    v[0] = v[1] = v[2] = 0;
-    if (keep && !keep[f]) return false;
-    v[0] = faces[3 * f]; v[1] = faces[3 * f + 1]; v[2] = faces[3 * f + 2];
-    return (uint32_t)v[0] < (uint32_t)V && (uint32_t)v[1] < (uint32_t)V && (uint32_t)v[2] < (uint32_t)V && v[0] != v[1] && v[1] != v[2] &&
-           v[0] != v[2];
-}
-
-__device__ __forceinline__ uint32_t next_corner(uint32_t c) { return c % 3u == 2u ? c - 2u : c + 1u; }
-
-// ---- the prefix sum of one column, block-sum form ---------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) scan_count_kernel(size_t n, const uint32_t *__restrict__ a, uint32_t *__restrict__ block_sum)
-{
-    __shared__ uint32_t lds[4];
-    uint32_t sa = 0;
-    const size_t base = (size_t)blockIdx.x * SCAN_TILE + (size_t)threadIdx.x * SCAN_PER;
-#pragma unroll
-    for (int k = 0; k < SCAN_PER; k++)
-        if (base + k < n) sa += a[base + k];
-    uint32_t ta;
-    block_scan256(sa, lds, &ta);
-    if (threadIdx.x == 0) block_sum[blockIdx.x] = ta;
-}
-
-// one workgroup: block_sum -> exclusive offsets in place, the total to *total
-__global__ void __launch_bounds__(256) scan_offsets_kernel(int nb, uint32_t *block_sum, uint32_t *__restrict__ total)
-{
-    __shared__ uint32_t lds[4];
-    const int span = (nb + 255) / 256, lo = min(nb, (int)threadIdx.x * span), hi = min(nb, lo + span);
-    uint32_t sa = 0;
-    for (int i = lo; i < hi; i++) sa += block_sum[i];
-    uint32_t ta;
-    uint32_t ra = block_scan256(sa, lds, &ta);
-    for (int i = lo; i < hi; i++) { const uint32_t x = block_sum[i]; block_sum[i] = ra; ra += x; }
-    if (threadIdx.x == 0) *total = ta;
-}
-
-// a becomes its exclusive prefix sum, in place: a thread reads its own eight elements before it writes them, nobody else's
-__global__ void __launch_bounds__(256) scan_apply_kernel(size_t n, uint32_t *a, const uint32_t *__restrict__ block_offset)
-{
-    __shared__ uint32_t lds[4];
-    uint32_t va[SCAN_PER], sa = 0;
-    const size_t base = (size_t)blockIdx.x * SCAN_TILE + (size_t)threadIdx.x * SCAN_PER;
-#pragma unroll
-    for (int k = 0; k < SCAN_PER; k++)
-    {
-        va[k] = base + k < n ? a[base + k] : 0u;
-        sa += va[k];
-    }
-    uint32_t ta;
-    uint32_t ra = block_offset[blockIdx.x] + block_scan256(sa, lds, &ta);
-#pragma unroll
-    for (int k = 0; k < SCAN_PER; k++)
-    {
-        if (base + k < n) a[base + k] = ra;
-        ra += va[k];
-    }
-}
-
 // ---- fans --------------------------------------------------------------------------------------------------------------------------------
 // One thread = one face: its three records and the identity of its three parent words.
 __global__ void __launch_bounds__(256) records_kernel(int V, int F, const int32_t *__restrict__ faces, const uint8_t *__restrict__ keep,
@@ -137,69 +35,38 @@ __global__ void __launch_bounds__(256) records_kernel(int V, int F, const int32_
     if (f < F)
     {
         int32_t v[3];
-        const bool ok = takes_part(V, (size_t)f, faces, keep, v);
+        const bool ok = face_takes_part(V, (size_t)f, faces, keep, v);
+        half_edge_records(V, (size_t)f, ok, v, key, val);
 #pragma unroll
-        for (int k = 0; k < 3; k++)
-        {
-            const size_t c = 3 * (size_t)f + k;
-            key[c] = ok ? (uint32_t)max(v[k], v[(k + 1) % 3]) : (uint32_t)V;
-            val[c] = (uint32_t)c;
-            parent[c] = (uint32_t)c;
-        }
+        for (int k = 0; k < 3; k++) parent[3 * (size_t)f + k] = 3u * (uint32_t)f + k;
         n = ok ? 3u : 0u;
     }
     count_into(counts + 0, n);
 }
 
-// The sentinel keys sort last, so a position whose first key is V holds a half-edge that does not take part: its other end is V too.  A
-// real half-edge's face took part when the records were written, so both ends are in [0, V); val < N by construction.
-__global__ void __launch_bounds__(256) other_end_kernel(int V, size_t N, const int32_t *__restrict__ faces, const uint32_t *__restrict__ skey,
-                                                         const uint32_t *__restrict__ sval, bool smaller, uint32_t *__restrict__ out)
-{
-    const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (j >= N) return;
-    uint32_t r = (uint32_t)V;
-    if (skey[j] < (uint32_t)V)
-    {
-        const uint32_t h = sval[j];
-        const int32_t a = faces[h], b = faces[next_corner(h)];
-        r = (uint32_t)(smaller ? min(a, b) : max(a, b));
-    }
-    out[j] = r;
-}
-
-// One thread = one sorted position.  Every index read is j, j - 1, j + 1 or j + 2 checked against N; the half-edges are below N and their
-// corners' parent words with them.
+// One thread = one sorted position.  The half-edges are below N and their corners' parent words with them.
 __global__ void __launch_bounds__(256) link_kernel(int V, size_t N, const int32_t *__restrict__ faces, const uint32_t *__restrict__ smin,
                                                     const uint32_t *__restrict__ smax, const uint32_t *__restrict__ sval, uint32_t *parent,
                                                     unsigned long long *counts)
 {
     const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
     uint32_t nonmanifold = 0, same = 0;
-    if (j < N)
+    const int run = edge_run_head(V, N, j, smin, smax);
+    if (run == 3) nonmanifold = 1;
+    else if (run == 2) // j + 1 < N
     {
-        const uint32_t a = smin[j], b = smax[j];
-        if (a < (uint32_t)V && (j == 0 || smin[j - 1] != a || smax[j - 1] != b))
+        const uint32_t h0 = sval[j], h1 = sval[j + 1];
+        const uint32_t n0 = next_corner(h0), n1 = next_corner(h1);
+        if (faces[h0] == faces[h1]) // both leave the same vertex: an orientation conflict, linked all the same
         {
-            const bool two = j + 1 < N && smin[j + 1] == a && smax[j + 1] == b;
-            const bool three = two && j + 2 < N && smin[j + 2] == a && smax[j + 2] == b;
-            if (three) nonmanifold = 1;
-            else if (two)
-            {
-                const uint32_t h0 = sval[j], h1 = sval[j + 1];
-                const uint32_t n0 = next_corner(h0), n1 = next_corner(h1);
-                if (faces[h0] == faces[h1]) // both leave the same vertex: an orientation conflict, linked all the same
-                {
-                    same = 1;
-                    uf_union(parent, h0, h1);
-                    uf_union(parent, n0, n1);
-                }
-                else
-                {
-                    uf_union(parent, h0, n1);
-                    uf_union(parent, n0, h1);
-                }
-            }
+            same = 1;
+            uf_union(parent, h0, h1);
+            uf_union(parent, n0, n1);
+        }
+        else
+        {
+            uf_union(parent, h0, n1);
+            uf_union(parent, n0, h1);
         }
     }
     count_into(counts + 4, nonmanifold);
@@ -216,7 +83,7 @@ __global__ void __launch_bounds__(256) flatten_kernel(int V, int F, const int32_
     if (f < F)
     {
         int32_t v[3];
-        const bool ok = takes_part(V, (size_t)f, faces, keep, v);
+        const bool ok = face_takes_part(V, (size_t)f, faces, keep, v);
 #pragma unroll
         for (int k = 0; k < 3; k++)
         {
@@ -255,7 +122,7 @@ __global__ void __launch_bounds__(256) labels_kernel(int V, int F, const int32_t
     const int f = blockIdx.x * 256 + threadIdx.x;
     if (f >= F) return;
     int32_t v[3];
-    const bool ok = takes_part(V, (size_t)f, faces, keep, v);
+    const bool ok = face_takes_part(V, (size_t)f, faces, keep, v);
 #pragma unroll
     for (int k = 0; k < 3; k++)
     {
@@ -267,7 +134,7 @@ __global__ void __launch_bounds__(256) labels_kernel(int V, int F, const int32_t
             if (e >= 0 && (size_t)e < 3 * (size_t)F)
             {
                 int32_t w[3];
-                if (takes_part(V, (size_t)e / 3, faces, keep, w) && faces[e] == v[k]) l = e;
+                if (face_takes_part(V, (size_t)e / 3, faces, keep, w) && faces[e] == v[k]) l = e;
             }
         }
         lab[c] = l;
@@ -331,38 +198,18 @@ __global__ void __launch_bounds__(256) split_finish_kernel(const uint32_t *__res
 }
 
 // ---- workspace ---------------------------------------------------------------------------------------------------------------------------
-// the radix sort's tables shrink where its chunk length grows (TS_RS_SMALL_BELOW): never less than just below that size
-size_t sort_scratch_bytes(size_t n)
-{
-    size_t b = ts_radix_scratch_bytes(n);
-    if (n > (size_t)TS_RS_SMALL_BELOW) b = std::max(b, ts_radix_scratch_bytes((size_t)TS_RS_SMALL_BELOW));
-    return b;
-}
-
-struct Carver // addresses as integers: the size queries carve from a null workspace, where pointer arithmetic would be undefined
-{
-    size_t p, base;
-    explicit Carver(void *ws) : p(ts_align_up((size_t)ws)), base((size_t)ws) {}
-    uint32_t *words(size_t n) { return (uint32_t *)bytes(n * 4); }
-    void *bytes(size_t n) { const size_t q = p; p += ts_align_up(n); return (void *)q; }
-    size_t used() const { return p - base; }
-};
-
 struct FansCarve
 {
-    uint32_t *k[2], *v[2], *other, *parent;
-    void *scratch;
+    EdgeSortCarve sort;
+    uint32_t *parent;
     size_t bytes;
 };
 FansCarve fans_carve(void *ws, size_t F)
 {
     FansCarve c;
     Carver w(ws);
-    const size_t N = 3 * F;
-    c.k[0] = w.words(N); c.k[1] = w.words(N); c.v[0] = w.words(N); c.v[1] = w.words(N);
-    c.other = w.words(N);
-    c.parent = w.words(N);
-    c.scratch = w.bytes(sort_scratch_bytes(N));
+    c.sort = edge_sort_carve(w, 3 * F);
+    c.parent = w.words(3 * F);
     c.bytes = w.used();
     return c;
 }
@@ -371,18 +218,17 @@ struct SplitCarve
 {
     uint32_t *keeper, *flag, *block_sum, *total;
     int32_t *lab;
-    size_t nb, bytes;
+    size_t bytes;
 };
 SplitCarve split_carve(void *ws, size_t V, size_t F)
 {
     SplitCarve c;
     Carver w(ws);
     const size_t N = 3 * F;
-    c.nb = (N + SCAN_TILE - 1) / SCAN_TILE;
     c.keeper = w.words(V);
     c.lab = (int32_t *)w.words(N);
     c.flag = w.words(N);
-    c.block_sum = w.words(c.nb);
+    c.block_sum = w.words(scan_blocks(N));
     c.total = w.words(1);
     c.bytes = w.used();
     return c;
@@ -409,16 +255,10 @@ hipError_t ts_manifold_fans(int V, int F, const int32_t *faces, const uint8_t *k
     if (N == 0) return hipSuccess;
     if (V <= 0) return hipMemsetAsync(corner_fan, 0xFF, N * sizeof(int32_t), s); // nothing takes part
     const FansCarve c = fans_carve(ws, f);
-    const int bits = bit_length((uint32_t)V); // the sentinel V included
     const unsigned nf = blocks256(f), nh = blocks256(N);
-    hipLaunchKernelGGL(records_kernel, dim3(nf), dim3(256), 0, s, V, F, faces, keep, c.k[0], c.v[0], c.parent, counts);
-    const int at = ts_radix_sort_pairs(c.k, c.v, N, bits, c.scratch, s); // by the larger end, stable
-    hipLaunchKernelGGL(other_end_kernel, dim3(nh), dim3(256), 0, s, V, N, faces, c.k[at], c.v[at], true, c.k[at ^ 1]);
-    uint32_t *const k2[2] = {c.k[at ^ 1], c.k[at]}, *const v2[2] = {c.v[at], c.v[at ^ 1]};
-    const int at2 = ts_radix_sort_pairs(k2, v2, N, bits, c.scratch, s); // then by the smaller end, stable: (min, max, half-edge) order
-    const uint32_t *smin = k2[at2], *sval = v2[at2];
-    hipLaunchKernelGGL(other_end_kernel, dim3(nh), dim3(256), 0, s, V, N, faces, smin, sval, false, c.other);
-    hipLaunchKernelGGL(link_kernel, dim3(nh), dim3(256), 0, s, V, N, faces, smin, c.other, sval, c.parent, counts);
+    hipLaunchKernelGGL(records_kernel, dim3(nf), dim3(256), 0, s, V, F, faces, keep, c.sort.k[0], c.sort.v[0], c.parent, counts);
+    const SortedEdges edges = sort_half_edges(V, N, faces, c.sort, s);
+    hipLaunchKernelGGL(link_kernel, dim3(nh), dim3(256), 0, s, V, N, faces, edges.smin, edges.smax, edges.sval, c.parent, counts);
     hipLaunchKernelGGL(flatten_kernel, dim3(nf), dim3(256), 0, s, V, F, faces, keep, c.parent, corner_fan, (uint32_t *)vertex_fans, counts);
     hipLaunchKernelGGL(vertex_census_kernel, dim3(blocks256((size_t)V)), dim3(256), 0, s, V, (const uint32_t *)vertex_fans, counts);
     return hipGetLastError();
@@ -445,12 +285,10 @@ hipError_t ts_manifold_split(int V, int F, const int32_t *faces, const uint8_t *
     if (e != hipSuccess) return e;
     e = hipMemsetAsync(c.flag, 0, N * sizeof(uint32_t), s);
     if (e != hipSuccess) return e;
-    const unsigned nf = blocks256(f), nh = blocks256(N), nb = (unsigned)c.nb;
+    const unsigned nf = blocks256(f), nh = blocks256(N);
     hipLaunchKernelGGL(labels_kernel, dim3(nf), dim3(256), 0, s, V, F, faces, keep, corner_fan, c.lab, c.flag, c.keeper);
     hipLaunchKernelGGL(flag_kernel, dim3(nh), dim3(256), 0, s, N, faces, c.keeper, c.flag);
-    hipLaunchKernelGGL(scan_count_kernel, dim3(nb), dim3(256), 0, s, N, c.flag, c.block_sum);
-    hipLaunchKernelGGL(scan_offsets_kernel, dim3(1), dim3(256), 0, s, (int)nb, c.block_sum, c.total);
-    hipLaunchKernelGGL(scan_apply_kernel, dim3(nb), dim3(256), 0, s, N, c.flag, c.block_sum);
+    scan_columns<1>(N, {{c.flag}}, c.block_sum, c.total, s); // the flags become their indices
     if (capacity > 0)
         hipLaunchKernelGGL(sources_kernel, dim3(nh), dim3(256), 0, s, N, faces, c.flag, c.total, capacity, new_vertex_source, new_vertex_fan);
     hipLaunchKernelGGL(rewrite_kernel, dim3(nh), dim3(256), 0, s, V, N, faces, c.lab, c.keeper, c.flag, out_faces, totals);

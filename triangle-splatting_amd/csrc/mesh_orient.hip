@@ -5,10 +5,8 @@
 // tests/ref_mesh_orient.py.  The atomics are integer: the compare-exchange and the minimum of the union-find (csrc/ts_union_find.h), the
 // 64-bit maximum of a piece's largest difference, the 32- and 64-bit adds of the per-piece sums and of the counters.
 //
-// Front.  mesh_manifold.hip's: one thread per face writes its three half-edge records (key max(tail, head), value the half-edge, the
-// sentinel key V for a face that does not take part), a stable LSD sort by the larger end, a gather of the smaller end, a second stable
-// sort by the smaller end, a gather of the larger end: the half-edges in (min, max, half-edge) order.  The three units that sort by edge
-// (mesh_smooth.hip, mesh_manifold.hip, this one) each carry their own front; existing tests pin the text of the other two.
+// Front.  The sort-by-edge front shared with mesh_manifold.hip (csrc/ts_mesh_edges.h): the half-edges of the faces that take part in
+// (min, max, half-edge) order.  The records kernel is this unit's own: it also sets the two parent words of a face and counts the faces.
 //
 // Links.  One thread per sorted position; the head of a run of exactly two unites two pairs of nodes of the doubled graph over 2 F nodes
 // (2 f: f as given, 2 f + 1: f reversed): straight for half-edges that run in opposite directions, crosswise for two that leave the same
@@ -16,32 +14,13 @@
 // r0 == r1, the consistency flip is r0 & 1 otherwise.  The flip and the non-orientable bit wait in face_flip until the deciding pass
 // overwrites them.  Per-piece sums (faces, flips; for mode 2 the largest difference, then the quantised volume) are indexed by the anchor
 // face; by_label reduces equal labels within the wave first, so that a mesh that is one piece sends one add per wave, not per face.
-#include "ts2d_common.h"
+#include "ts_mesh_edges.h"
 #include "ts_orient_launch.h"
 #include "ts_union_find.h"
-
-#include <algorithm>
 
 namespace
 {
 constexpr int LABEL_ROUNDS = 4; // distinct labels of a wave that are reduced before the rest of its lanes add one by one
-
-inline unsigned blocks256(size_t n) { return (unsigned)((n + 255) / 256); }
-
-int bit_length(uint32_t v)
-{
-    int n = 1; // at least one pass bit
-    while (n < 32 && (v >> n)) n++;
-    return n;
-}
-
-// the wave's sum of n, added to *counter by its first lane
-__device__ __forceinline__ void count_into(unsigned long long *counter, uint32_t n)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
-    if ((threadIdx.x & 63) == 0 && n) __hip_atomic_fetch_add(counter, (unsigned long long)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // Every active lane hands (label, value) to commit, equal labels combined first: up to LABEL_ROUNDS times the first lane still waiting
 // names its label, the lanes with that label are combined over the wave and the leader commits once; who is left commits its own.  All 64
@@ -66,19 +45,7 @@ __device__ __forceinline__ void by_label(bool active, uint32_t label, T value, T
     if ((todo >> lane) & 1) commit(label, value);
 }
 
-// ts_smooth.h's rule: kept, the three indices in [0, V) and pairwise distinct.  f < F.
-__device__ __forceinline__ bool takes_part(int V, size_t f, const int32_t *__restrict__ faces, const uint8_t *__restrict__ keep, int32_t (&v)[3])
-{
-    v[0] = v[1] = v[2] = 0;
-    if (keep && !keep[f]) return false;
-    v[0] = faces[3 * f]; v[1] = faces[3 * f + 1]; v[2] = faces[3 * f + 2];
-    return (uint32_t)v[0] < (uint32_t)V && (uint32_t)v[1] < (uint32_t)V && (uint32_t)v[2] < (uint32_t)V && v[0] != v[1] && v[1] != v[2] &&
-           v[0] != v[2];
-}
-
-__device__ __forceinline__ uint32_t next_corner(uint32_t c) { return c % 3u == 2u ? c - 2u : c + 1u; }
-
-// ---- the sort-by-edge front ----------------------------------------------------------------------------------------------------------------
+// ---- the records of the front ----------------------------------------------------------------------------------------------------------------
 // One thread = one face: its three records and the identity of its two parent words.
 __global__ void __launch_bounds__(256) records_kernel(int V, int F, const int32_t *__restrict__ faces, const uint8_t *__restrict__ keep,
                                                        uint32_t *__restrict__ key, uint32_t *__restrict__ val, uint32_t *__restrict__ parent,
@@ -89,47 +56,13 @@ __global__ void __launch_bounds__(256) records_kernel(int V, int F, const int32_
     if (f < F)
     {
         int32_t v[3];
-        const bool ok = takes_part(V, (size_t)f, faces, keep, v);
-#pragma unroll
-        for (int k = 0; k < 3; k++)
-        {
-            const size_t c = 3 * (size_t)f + k;
-            key[c] = ok ? (uint32_t)max(v[k], v[(k + 1) % 3]) : (uint32_t)V;
-            val[c] = (uint32_t)c;
-        }
+        const bool ok = face_takes_part(V, (size_t)f, faces, keep, v);
+        half_edge_records(V, (size_t)f, ok, v, key, val);
         parent[2 * (size_t)f] = 2u * (uint32_t)f;
         parent[2 * (size_t)f + 1] = 2u * (uint32_t)f + 1u;
         n = ok ? 1u : 0u;
     }
     count_into(counts + 0, n);
-}
-
-// The sentinel keys sort last, so a position whose first key is V holds a half-edge that does not take part: its other end is V too.  A
-// real half-edge's face took part when the records were written, so both ends are in [0, V); val < N by construction.
-__global__ void __launch_bounds__(256) other_end_kernel(int V, size_t N, const int32_t *__restrict__ faces, const uint32_t *__restrict__ skey,
-                                                         const uint32_t *__restrict__ sval, bool smaller, uint32_t *__restrict__ out)
-{
-    const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (j >= N) return;
-    uint32_t r = (uint32_t)V;
-    if (skey[j] < (uint32_t)V)
-    {
-        const uint32_t h = sval[j];
-        const int32_t a = faces[h], b = faces[next_corner(h)];
-        r = (uint32_t)(smaller ? min(a, b) : max(a, b));
-    }
-    out[j] = r;
-}
-
-// Position j heads a run of exactly two: a linking edge.  Every index read is j, j - 1, j + 1 or j + 2 checked against N.
-__device__ __forceinline__ bool heads_a_pair(int V, size_t N, size_t j, const uint32_t *__restrict__ smin, const uint32_t *__restrict__ smax)
-{
-    if (j >= N) return false;
-    const uint32_t a = smin[j], b = smax[j];
-    if (a >= (uint32_t)V || (j > 0 && smin[j - 1] == a && smax[j - 1] == b)) return false;
-    const bool two = j + 1 < N && smin[j + 1] == a && smax[j + 1] == b;
-    const bool three = two && j + 2 < N && smin[j + 2] == a && smax[j + 2] == b;
-    return two && !three;
 }
 
 // ---- links, pieces -----------------------------------------------------------------------------------------------------------------------
@@ -140,7 +73,7 @@ __global__ void __launch_bounds__(256) link_kernel(int V, size_t N, const int32_
 {
     const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
     uint32_t linking = 0, same = 0;
-    if (heads_a_pair(V, N, j, smin, smax))
+    if (edge_run_head(V, N, j, smin, smax) == 2) // a linking edge: j + 1 < N
     {
         const uint32_t h0 = sval[j], h1 = sval[j + 1];
         const uint32_t f = h0 / 3u, g = h1 / 3u;
@@ -164,7 +97,7 @@ __global__ void __launch_bounds__(256) flatten_kernel(int V, int F, const int32_
     if (f < F)
     {
         int32_t v[3];
-        ok = takes_part(V, (size_t)f, faces, keep, v);
+        ok = face_takes_part(V, (size_t)f, faces, keep, v);
         if (ok)
         {
             const uint32_t r0 = uf_find(parent, 2u * (uint32_t)f, false), r1 = uf_find(parent, 2u * (uint32_t)f + 1u, false);
@@ -306,7 +239,7 @@ __global__ void __launch_bounds__(256) after_kernel(int V, size_t N, const int32
 {
     const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
     uint32_t same = 0;
-    if (heads_a_pair(V, N, j, smin, smax))
+    if (edge_run_head(V, N, j, smin, smax) == 2) // a linking edge: j + 1 < N
     {
         const uint32_t h0 = sval[j], h1 = sval[j + 1];
         same = (uint32_t)(faces[h0] == faces[h1]) ^ face_flip[h0 / 3u] ^ face_flip[h1 / 3u];
@@ -315,38 +248,20 @@ __global__ void __launch_bounds__(256) after_kernel(int V, size_t N, const int32
 }
 
 // ---- workspace ---------------------------------------------------------------------------------------------------------------------------
-// the radix sort's tables shrink where its chunk length grows (TS_RS_SMALL_BELOW): never less than just below that size
-size_t sort_scratch_bytes(size_t n)
-{
-    size_t b = ts_radix_scratch_bytes(n);
-    if (n > (size_t)TS_RS_SMALL_BELOW) b = std::max(b, ts_radix_scratch_bytes((size_t)TS_RS_SMALL_BELOW));
-    return b;
-}
-
-struct Carver // addresses as integers: the size query carves from a null workspace, where pointer arithmetic would be undefined
-{
-    size_t p, base;
-    explicit Carver(void *ws) : p(ts_align_up((size_t)ws)), base((size_t)ws) {}
-    uint32_t *words(size_t n) { return (uint32_t *)bytes(n * 4); }
-    void *bytes(size_t n) { const size_t q = p; p += ts_align_up(n); return (void *)q; }
-    size_t used() const { return p - base; }
-};
-
 struct OrientCarve
 {
-    uint32_t *k[2], *v[2], *other, *parent, *piece_faces, *piece_flips;
+    EdgeSortCarve sort;
+    uint32_t *parent, *piece_faces, *piece_flips;
     unsigned long long *piece_largest;
     long long *piece_volume;
-    void *sums, *scratch;
+    void *sums;
     size_t sums_bytes, bytes;
 };
 OrientCarve orient_carve(void *ws, size_t F)
 {
     OrientCarve c;
     Carver w(ws);
-    const size_t N = 3 * F;
-    c.k[0] = w.words(N); c.k[1] = w.words(N); c.v[0] = w.words(N); c.v[1] = w.words(N);
-    c.other = w.words(N);
+    c.sort = edge_sort_carve(w, 3 * F);
     c.parent = w.words(2 * F);
     c.sums_bytes = 24 * F; // the per-piece sums in one block, cleared by one memset: the 64-bit columns first
     c.sums = w.bytes(c.sums_bytes);
@@ -354,7 +269,6 @@ OrientCarve orient_carve(void *ws, size_t F)
     c.piece_volume = (long long *)(c.piece_largest + F);
     c.piece_faces = (uint32_t *)(c.piece_volume + F);
     c.piece_flips = c.piece_faces + F;
-    c.scratch = w.bytes(sort_scratch_bytes(N));
     c.bytes = w.used();
     return c;
 }
@@ -384,16 +298,10 @@ hipError_t ts_orient_faces(int V, int F, const float *vertices, const int32_t *f
     const OrientCarve c = orient_carve(ws, f);
     e = hipMemsetAsync(c.sums, 0, c.sums_bytes, s);
     if (e != hipSuccess) return e;
-    const int bits = bit_length((uint32_t)V); // the sentinel V included
     const unsigned nf = blocks256(f), nh = blocks256(N);
-    hipLaunchKernelGGL(records_kernel, dim3(nf), dim3(256), 0, s, V, F, faces, keep, c.k[0], c.v[0], c.parent, counts);
-    const int at = ts_radix_sort_pairs(c.k, c.v, N, bits, c.scratch, s); // by the larger end, stable
-    hipLaunchKernelGGL(other_end_kernel, dim3(nh), dim3(256), 0, s, V, N, faces, c.k[at], c.v[at], true, c.k[at ^ 1]);
-    uint32_t *const k2[2] = {c.k[at ^ 1], c.k[at]}, *const v2[2] = {c.v[at], c.v[at ^ 1]};
-    const int at2 = ts_radix_sort_pairs(k2, v2, N, bits, c.scratch, s); // then by the smaller end, stable: (min, max, half-edge) order
-    const uint32_t *smin = k2[at2], *sval = v2[at2];
-    hipLaunchKernelGGL(other_end_kernel, dim3(nh), dim3(256), 0, s, V, N, faces, smin, sval, false, c.other);
-    hipLaunchKernelGGL(link_kernel, dim3(nh), dim3(256), 0, s, V, N, faces, smin, c.other, sval, c.parent, counts);
+    hipLaunchKernelGGL(records_kernel, dim3(nf), dim3(256), 0, s, V, F, faces, keep, c.sort.k[0], c.sort.v[0], c.parent, counts);
+    const SortedEdges edges = sort_half_edges(V, N, faces, c.sort, s);
+    hipLaunchKernelGGL(link_kernel, dim3(nh), dim3(256), 0, s, V, N, faces, edges.smin, edges.smax, edges.sval, c.parent, counts);
     hipLaunchKernelGGL(flatten_kernel, dim3(nf), dim3(256), 0, s, V, F, faces, keep, c.parent, face_piece, face_flip, c.piece_faces,
                        c.piece_flips, counts);
     if (mode == 2)
@@ -404,6 +312,6 @@ hipError_t ts_orient_faces(int V, int F, const float *vertices, const int32_t *f
     }
     hipLaunchKernelGGL(decide_kernel, dim3(nf), dim3(256), 0, s, F, mode, faces, face_piece, c.piece_faces, c.piece_flips, c.piece_volume,
                        face_flip, out_faces, counts);
-    hipLaunchKernelGGL(after_kernel, dim3(nh), dim3(256), 0, s, V, N, faces, smin, c.other, sval, face_flip, counts);
+    hipLaunchKernelGGL(after_kernel, dim3(nh), dim3(256), 0, s, V, N, faces, edges.smin, edges.smax, edges.sval, face_flip, counts);
     return hipGetLastError();
 }

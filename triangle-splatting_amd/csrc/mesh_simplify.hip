@@ -10,8 +10,8 @@
 // sorted keys (log2 V steps of contiguous loads): nobody waits for a neighbour and there is no scan.  Invalid vertices label themselves.
 //
 // Placement.  remap (the cluster ranks of ts2d_weld_compact) is the sort key, only the bits V needs: a stable sort of (rank, index) gives
-// each cluster's members ascending, and the head and the tail of each run write the run's bounds.  One thread per face writes up to three
-// incidence records (rank, face) into its three slots (the sentinel rank V in a slot it does not use: the face does not contribute, the
+// each cluster's members ascending, and the head and the tail of each run write the run's bounds (csrc/ts_mesh_runs.h).
+// One thread per face writes up to three incidence records (rank, face) into its three slots (the sentinel rank V in a slot it does not use: the face does not contribute, the
 // vertex is invalid, or an earlier valid vertex of the face already named the cluster); a stable sort by rank leaves each cluster's faces
 // ascending.  Then ONE thread per cluster walks its member run and its face run in order, accumulates, solves, clamps and writes: the sums
 // are sequential by definition, so the cost is linear in the largest cluster (the header says so).  A rank that no vertex holds (V' .. V - 1)
@@ -21,27 +21,13 @@
 // gathered through the order so far) put the faces in (a, b, c, face) order.  A face whose predecessor holds the same triple is a duplicate;
 // a survivor looks its reversed triple (a, c, b) up by a lower-bound search: a run of equal triples always has exactly one survivor, so the
 // triple's presence is the twin's survival.
-#include "ts2d_common.h"
+#include "ts_mesh_runs.h"
 #include "ts_simplify_launch.h"
-
-#include <algorithm>
 
 namespace
 {
 constexpr uint32_t KEY_INVALID = 0xFFFFFFFFu; // both words of an invalid vertex's key
 constexpr int MAXC = 8;                        // TSQ_MAX_CHANNELS
-
-inline unsigned blocks256(size_t n) { return (unsigned)((n + 255) / 256); }
-
-int bit_length(uint32_t v)
-{
-    int n = 1; // at least one pass bit
-    while (n < 32 && (v >> n)) n++;
-    return n;
-}
-
-__device__ __forceinline__ bool finite32(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
-__device__ __forceinline__ bool finite64(double x) { return ((unsigned long long)__double_as_longlong(x) & 0x7FF0000000000000ull) != 0x7FF0000000000000ull; }
 
 // c = floor(((double)x - (double)o) / (double)cell); false unless x is finite and 0 <= c < 2^21
 __device__ __forceinline__ bool cell_index(float x, float o, float cell, uint32_t &c)
@@ -118,24 +104,6 @@ __global__ void __launch_bounds__(256) member_keys_kernel(int V, const int32_t *
     ids[i] = (uint32_t)i;
 }
 
-// keys ascending: the head of the run of key k writes start[k], its tail end[k] (one past); keys >= limit (the sentinel) write nothing
-__global__ void __launch_bounds__(256) run_bounds_kernel(size_t n, const uint32_t *__restrict__ keys, uint32_t limit, uint32_t *__restrict__ start,
-                                                          uint32_t *__restrict__ end)
-{
-    const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (j >= n) return;
-    const uint32_t k = keys[j];
-    if (k >= limit) return;
-    if (j == 0 || keys[j - 1] != k) start[k] = (uint32_t)j;
-    if (j + 1 == n || keys[j + 1] != k) end[k] = (uint32_t)(j + 1);
-}
-
-__device__ __forceinline__ bool face_indices(int V, int f, const int32_t *__restrict__ faces, int32_t (&v)[3])
-{
-    v[0] = faces[3 * (size_t)f]; v[1] = faces[3 * (size_t)f + 1]; v[2] = faces[3 * (size_t)f + 2];
-    return (uint32_t)v[0] < (uint32_t)V && (uint32_t)v[1] < (uint32_t)V && (uint32_t)v[2] < (uint32_t)V;
-}
-
 __global__ void __launch_bounds__(256) incidence_kernel(int V, int F, const float *__restrict__ vertices, const int32_t *__restrict__ faces,
                                                          const int32_t *__restrict__ remap, float ox, float oy, float oz, float cell,
                                                          uint32_t *__restrict__ rank, uint32_t *__restrict__ face)
@@ -144,7 +112,7 @@ __global__ void __launch_bounds__(256) incidence_kernel(int V, int F, const floa
     if (f >= F) return;
     int32_t v[3];
     uint32_t r[3] = {(uint32_t)V, (uint32_t)V, (uint32_t)V};
-    if (face_indices(V, f, faces, v))
+    if (face_in_range(V, (size_t)f, faces, nullptr, v))
     {
         bool valid[3], finite = true;
 #pragma unroll
@@ -313,7 +281,7 @@ __global__ void __launch_bounds__(256) rotated_triples_kernel(int V, int F, cons
     if (f >= F) return;
     int32_t v[3];
     uint32_t a = (uint32_t)V, b = (uint32_t)V, c = (uint32_t)V;
-    if (keep[f] && face_indices(V, f, faces, v) && v[0] != v[1] && v[1] != v[2] && v[0] != v[2])
+    if (face_takes_part(V, (size_t)f, faces, keep, v)) // keep is never null here
     {
         const uint32_t x = (uint32_t)v[0], y = (uint32_t)v[1], z = (uint32_t)v[2];
         if (x < y && x < z) { a = x; b = y; c = z; }
@@ -372,23 +340,6 @@ __global__ void __launch_bounds__(256) unique_kernel(int V, int F, const uint32_
 }
 
 // ---- workspace ---------------------------------------------------------------------------------------------------------------------------
-// the radix sort's tables shrink where its chunk length grows (TS_RS_SMALL_BELOW): never less than just below that size
-size_t sort_scratch_bytes(size_t n)
-{
-    size_t b = ts_radix_scratch_bytes(n);
-    if (n > (size_t)TS_RS_SMALL_BELOW) b = std::max(b, ts_radix_scratch_bytes((size_t)TS_RS_SMALL_BELOW));
-    return b;
-}
-
-struct Carver
-{
-    char *p, *base;
-    explicit Carver(void *ws) : p((char *)ts_align_up((size_t)ws)), base((char *)ws) {}
-    uint32_t *words(size_t n) { char *q = p; p += ts_align_up(n * 4); return (uint32_t *)q; }
-    void *bytes(size_t n) { char *q = p; p += ts_align_up(n); return q; }
-    size_t used() const { return (size_t)(p - base); }
-};
-
 struct LabelCarve
 {
     uint32_t *key_lo, *key_hi, *k[2], *v[2];

@@ -5,11 +5,12 @@
 //
 // Adjacency.  One thread per face writes its six directed records (src, dst) into its six slots (the sentinel V in both words of a face that
 // does not take part).  Two stable LSD sorts with the product's radix passes -- by dst, then by src, only the bits V needs -- leave the records
-// in (src, dst) order.  A record is a HEAD iff it differs from its predecessor; the heads are ranked by a prefix sum in the form of
-// ts2d_weld_compact: per-block head counts, one workgroup turns them into offsets, then every block ranks its own heads behind the sum in
-// front of it (nobody waits for anybody).  A head writes its dst, the length of its run (found by an upper-bound search among the sorted
-// records: at most 31 halvings, no walk) and its src into row `rank` of neighbors / edge_faces / a compact src column; the row of vertex v
-// starts at the lower bound of v in that column, and one thread per vertex classifies its row.
+// in (src, dst) order.  A record is a HEAD iff it differs from its predecessor; the heads are ranked by the block-sum prefix sum of
+// csrc/ts_mesh_scan.h: per-block head counts, its one workgroup turns them into offsets, then every block ranks its own heads behind the
+// sum in front of it (nobody waits for anybody); the flags are computed on the fly, so the count and the rank pass are this unit's own.
+// A head writes its dst, the length of its run (found by an upper-bound search among the sorted records: at most 31 halvings, no walk) and
+// its src into row `rank` of neighbors / edge_faces / a compact src column; the row of vertex v starts at the lower bound of v in that
+// column, and one thread per vertex classifies its row.
 //
 // Smoothing.  The state is two V x 3 float64 buffers in the workspace; a byte per vertex holds its stencil (none / whole row / boundary entries
 // only) and whether it is live, decided once.  One launch per step: a thread gathers the previous state of its live neighbours in row order,
@@ -17,56 +18,15 @@
 //
 // Normals.  One thread per face for the face normals.  For the vertex normals one thread per face writes up to three incidence records
 // (vertex, face) (the sentinel V in a slot it does not use); a stable sort by vertex leaves each vertex's faces ascending, the head and the
-// tail of each run write the run's bounds, and ONE thread per vertex walks its run, recomputing each face's cross product.
-#include "ts2d_common.h"
+// tail of each run write the run's bounds (csrc/ts_mesh_runs.h), and ONE thread per vertex walks its run, recomputing each face's cross
+// product.
+#include "ts_mesh_runs.h"
+#include "ts_mesh_scan.h"
 #include "ts_smooth_launch.h"
-
-#include <algorithm>
 
 namespace
 {
-constexpr int SCAN_PER = 8, SCAN_TILE = 256 * SCAN_PER;
 constexpr uint8_t ST_NONE = 0, ST_ROW = 1, ST_CURVE = 2, ST_MASK = 3, LIVE = 4; // the per-vertex byte of the smoothing
-
-inline unsigned blocks256(size_t n) { return (unsigned)((n + 255) / 256); }
-
-int bit_length(uint32_t v)
-{
-    int n = 1; // at least one pass bit
-    while (n < 32 && (v >> n)) n++;
-    return n;
-}
-
-__device__ __forceinline__ bool finite32(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
-__device__ __forceinline__ bool finite64(double x) { return ((unsigned long long)__double_as_longlong(x) & 0x7FF0000000000000ull) != 0x7FF0000000000000ull; }
-
-__device__ __forceinline__ bool face_indices(int V, int f, const int32_t *__restrict__ faces, const uint8_t *__restrict__ keep, int32_t (&v)[3])
-{
-    v[0] = v[1] = v[2] = 0;
-    if (keep && !keep[f]) return false;
-    v[0] = faces[3 * (size_t)f]; v[1] = faces[3 * (size_t)f + 1]; v[2] = faces[3 * (size_t)f + 2];
-    return (uint32_t)v[0] < (uint32_t)V && (uint32_t)v[1] < (uint32_t)V && (uint32_t)v[2] < (uint32_t)V;
-}
-
-// exclusive scan of one value per lane over the 256-lane workgroup; returns the lane's offset, *total the sum
-__device__ __forceinline__ uint32_t block_scan256(uint32_t v, uint32_t *lds, uint32_t *total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1)
-    {
-        const uint32_t t = __shfl_up(incl, d);
-        if (lane >= d) incl += t;
-    }
-    __syncthreads();
-    if (lane == 63) lds[wave] = incl;
-    __syncthreads();
-    uint32_t base = 0, all = 0;
-    for (int w = 0; w < 4; w++) { const uint32_t t = lds[w]; if (w < wave) base += t; all += t; }
-    *total = all;
-    return base + incl - v;
-}
 
 // ---- adjacency -------------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) records_kernel(int V, int F, const int32_t *__restrict__ faces, const uint8_t *__restrict__ keep,
@@ -75,7 +35,7 @@ __global__ void __launch_bounds__(256) records_kernel(int V, int F, const int32_
     const int f = blockIdx.x * 256 + threadIdx.x;
     if (f >= F) return;
     int32_t v[3];
-    const bool ok = face_indices(V, f, faces, keep, v) && v[0] != v[1] && v[1] != v[2] && v[0] != v[2];
+    const bool ok = face_takes_part(V, (size_t)f, faces, keep, v);
 #pragma unroll
     for (int k = 0; k < 3; k++)
     {
@@ -107,18 +67,6 @@ __global__ void __launch_bounds__(256) head_count_kernel(int V, size_t N, const 
     if (threadIdx.x == 0) block_count[blockIdx.x] = total;
 }
 
-// one workgroup: block_count -> exclusive offsets in place, the total to *entries
-__global__ void __launch_bounds__(256) head_offsets_kernel(int nb, uint32_t *block_count, uint32_t *__restrict__ entries)
-{
-    __shared__ uint32_t lds[4];
-    const int span = (nb + 255) / 256, lo = min(nb, (int)threadIdx.x * span), hi = min(nb, lo + span);
-    uint32_t n = 0;
-    for (int i = lo; i < hi; i++) n += block_count[i];
-    uint32_t total, run = block_scan256(n, lds, &total);
-    for (int i = lo; i < hi; i++) { const uint32_t t = block_count[i]; block_count[i] = run; run += t; }
-    if (threadIdx.x == 0) *entries = total;
-}
-
 // Every head writes row `rank` of the three compact columns.  rank < the number of heads <= N, the extent of all three.
 __global__ void __launch_bounds__(256) scatter_rows_kernel(int V, size_t N, const uint32_t *__restrict__ ssrc, const uint32_t *__restrict__ sdst,
                                                             const uint32_t *__restrict__ block_offset, int32_t *__restrict__ neighbors,
@@ -126,7 +74,6 @@ __global__ void __launch_bounds__(256) scatter_rows_kernel(int V, size_t N, cons
                                                             unsigned long long *counts)
 {
     __shared__ uint32_t lds[4];
-    __shared__ uint32_t red[4][4];
     const size_t base = (size_t)blockIdx.x * SCAN_TILE + (size_t)threadIdx.x * SCAN_PER;
     bool head[SCAN_PER];
     uint32_t n = 0;
@@ -162,20 +109,7 @@ __global__ void __launch_bounds__(256) scatter_rows_kernel(int V, size_t N, cons
         run++;
         c[1] += uses == 1; c[2] += uses == 2; c[3] += uses >= 3;
     }
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-    {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) c[k] += __shfl_xor(c[k], o);
-    }
-    if ((threadIdx.x & 63) == 0)
-        for (int k = 0; k < 4; k++) red[threadIdx.x >> 6][k] = c[k];
-    __syncthreads();
-    if (threadIdx.x < 4)
-    {
-        const uint32_t t = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-        if (t) __hip_atomic_fetch_add(counts + threadIdx.x, (unsigned long long)t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    count4_into(counts, c);
 }
 
 // offsets[v] = the first row whose src is not below v, v = 0 .. V: at most 31 halvings of contiguous loads
@@ -322,7 +256,7 @@ __global__ void __launch_bounds__(256) face_normals_kernel(int V, int F, const f
     int32_t v[3];
     double n[3], u[3] = {0.0, 0.0, 0.0};
     bool valid = false;
-    if (face_indices(V, f, faces, keep, v) && face_cross(vertices, v, n)) valid = unit_normal(n, u);
+    if (face_in_range(V, (size_t)f, faces, keep, v) && face_cross(vertices, v, n)) valid = unit_normal(n, u);
     face_normal[3 * (size_t)f] = (float)u[0]; face_normal[3 * (size_t)f + 1] = (float)u[1]; face_normal[3 * (size_t)f + 2] = (float)u[2];
     face_valid[f] = valid ? 1 : 0;
 }
@@ -335,7 +269,7 @@ __global__ void __launch_bounds__(256) incidence_kernel(int V, int F, const floa
     int32_t v[3];
     double n[3];
     uint32_t r[3] = {(uint32_t)V, (uint32_t)V, (uint32_t)V};
-    if (face_indices(V, f, faces, keep, v) && face_cross(vertices, v, n))
+    if (face_in_range(V, (size_t)f, faces, keep, v) && face_cross(vertices, v, n))
     {
         r[0] = (uint32_t)v[0];
         if (v[1] != v[0]) r[1] = (uint32_t)v[1];
@@ -347,18 +281,6 @@ __global__ void __launch_bounds__(256) incidence_kernel(int V, int F, const floa
         vert[3 * (size_t)f + k] = r[k];
         face[3 * (size_t)f + k] = (uint32_t)f;
     }
-}
-
-// keys ascending: the head of the run of key k writes start[k], its tail end[k] (one past); keys >= limit (the sentinel) write nothing
-__global__ void __launch_bounds__(256) run_bounds_kernel(size_t n, const uint32_t *__restrict__ keys, uint32_t limit, uint32_t *__restrict__ start,
-                                                          uint32_t *__restrict__ end)
-{
-    const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (j >= n) return;
-    const uint32_t k = keys[j];
-    if (k >= limit) return;
-    if (j == 0 || keys[j - 1] != k) start[k] = (uint32_t)j;
-    if (j + 1 == n || keys[j + 1] != k) end[k] = (uint32_t)(j + 1);
 }
 
 // One thread = one vertex.  Its run's positions are bounded by 3 F, the face ids there by the incidence records (< F, their indices checked
@@ -393,23 +315,6 @@ __global__ void __launch_bounds__(256) vertex_normals_kernel(int V, int F, const
 }
 
 // ---- workspace ---------------------------------------------------------------------------------------------------------------------------
-// the radix sort's tables shrink where its chunk length grows (TS_RS_SMALL_BELOW): never less than just below that size
-size_t sort_scratch_bytes(size_t n)
-{
-    size_t b = ts_radix_scratch_bytes(n);
-    if (n > (size_t)TS_RS_SMALL_BELOW) b = std::max(b, ts_radix_scratch_bytes((size_t)TS_RS_SMALL_BELOW));
-    return b;
-}
-
-struct Carver // addresses as integers: the size queries carve from a null workspace, where pointer arithmetic would be undefined
-{
-    size_t p, base;
-    explicit Carver(void *ws) : p(ts_align_up((size_t)ws)), base((size_t)ws) {}
-    uint32_t *words(size_t n) { return (uint32_t *)bytes(n * 4); }
-    void *bytes(size_t n) { const size_t q = p; p += ts_align_up(n); return (void *)q; }
-    size_t used() const { return p - base; }
-};
-
 struct AdjacencyCarve
 {
     uint32_t *k[2], *v[2], *block_count, *entries;
@@ -421,7 +326,7 @@ AdjacencyCarve adjacency_carve(void *ws, size_t F)
     AdjacencyCarve c;
     Carver w(ws);
     const size_t N = 6 * F;
-    c.nb = (N + SCAN_TILE - 1) / SCAN_TILE;
+    c.nb = scan_blocks(N);
     c.k[0] = w.words(N); c.k[1] = w.words(N); c.v[0] = w.words(N); c.v[1] = w.words(N);
     c.block_count = w.words(c.nb);
     c.entries = w.words(1);
@@ -497,7 +402,7 @@ hipError_t ts_smooth_adjacency(int V, int F, const int32_t *faces, const uint8_t
     uint32_t *row_src = k2[at2 ^ 1]; // the partner of the sorted src column is free now
     const unsigned nb = (unsigned)c.nb;
     hipLaunchKernelGGL(head_count_kernel, dim3(nb), dim3(256), 0, s, V, N, ssrc, sdst, c.block_count);
-    hipLaunchKernelGGL(head_offsets_kernel, dim3(1), dim3(256), 0, s, (int)nb, c.block_count, c.entries);
+    hipLaunchKernelGGL(scan_offsets_kernel<1>, dim3(1), dim3(256), 0, s, (int)nb, c.block_count, c.entries);
     hipLaunchKernelGGL(scatter_rows_kernel, dim3(nb), dim3(256), 0, s, V, N, ssrc, sdst, c.block_count, neighbors, edge_faces, row_src, counts);
     hipLaunchKernelGGL(row_offsets_kernel, dim3(blocks256((size_t)V + 1)), dim3(256), 0, s, V, N, row_src, c.entries, offsets);
     hipLaunchKernelGGL(classify_kernel, dim3(blocks256((size_t)V)), dim3(256), 0, s, V, N, offsets, edge_faces, vertex_class);

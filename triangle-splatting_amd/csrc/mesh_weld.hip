@@ -12,22 +12,24 @@
 // is monotonic, so a bound is never above the value of a pair it covers: pruning drops no pair that passes, and the result is exact.
 // Every passing pair is handed to the union-find below.  The labels are its roots: the smallest index of every cluster.
 //
-// Union-find (uf_find / uf_union, csrc/ts_union_find.h, shared with mesh_manifold.hip; also the core of ts_weld_face_components): its
-// invariants and its termination argument are stated there.  The flatten (label[i] = root(i)) is a launch of its own after all unions.
+// Union-find (uf_find / uf_union, csrc/ts_union_find.h, shared with mesh_manifold.hip and mesh_orient.hip; also the core of
+// ts_weld_face_components): its invariants and its termination argument are stated there.  The flatten (label[i] = root(i)) is a launch
+// of its own after all unions.
 //
 // Compaction.  A vertex is a root iff label[i] == i; an exclusive scan of the root flags ranks the clusters by ascending label (block
-// counts, one block scanning them, block-local scan again).  "first" copies the root's position bits.  "mean" sorts 0..V-1 stably by label
-// (ts_radix_sort_pairs), so a cluster's members are contiguous in ascending index order, and one lane walks one cluster summing in float64
+// counts, one block scanning them, block-local scan again: csrc/ts_mesh_scan.h; the count and the rank pass, which compute the flag, are
+// this unit's).  "first" copies the root's position bits.  "mean" sorts 0..V-1 stably by label (ts_radix_sort_pairs), so a cluster's members are contiguous in ascending index order, and one lane walks one cluster summing in float64
 // in that order.  No float atomics.
 //
 // Edge census.  Every kept face with three indices in [0, V) gives three (min, max) pairs; every other face gives three (V, V) sentinels.
 // Two stable 32-bit sorts (by max, then by min) order the 64-bit keys; a run-length pass classifies the head of every run by looking at
-// most two elements ahead, reduces inside the workgroup and adds to the four 64-bit counters with integer atomics.
+// most two elements ahead (edge_run_head, csrc/ts_mesh_common.h), reduces inside the workgroup and adds to the four 64-bit counters with
+// integer atomics.  A face with a repeated index takes part here and yields an edge (a, a): the keys are this unit's own, not the
+// half-edge records of csrc/ts_mesh_edges.h.
 #include "ts_knn_front.h"
+#include "ts_mesh_scan.h"
 #include "ts_union_find.h"
 #include "ts_weld_launch.h"
-
-#include <algorithm>
 
 namespace
 {
@@ -117,19 +119,12 @@ __global__ void __launch_bounds__(TPB) weld_search_kernel(int P, int nboxes, flo
 }
 
 // ---- faces ----------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool face_ok(int V, int f, const int32_t *__restrict__ faces, const uint8_t *__restrict__ keep, int32_t (&v)[3])
-{
-    if (keep && !keep[f]) return false;
-    v[0] = faces[3 * (size_t)f]; v[1] = faces[3 * (size_t)f + 1]; v[2] = faces[3 * (size_t)f + 2];
-    return (uint32_t)v[0] < (uint32_t)V && (uint32_t)v[1] < (uint32_t)V && (uint32_t)v[2] < (uint32_t)V;
-}
-
 __global__ void __launch_bounds__(256) face_union_kernel(int V, int F, const int32_t *__restrict__ faces, const uint8_t *__restrict__ keep,
                                                          uint32_t *parent)
 {
     const int f = blockIdx.x * 256 + threadIdx.x;
     int32_t v[3];
-    if (f >= F || !face_ok(V, f, faces, keep, v)) return;
+    if (f >= F || !face_in_range(V, (size_t)f, faces, keep, v)) return;
     uf_union(parent, (uint32_t)v[0], (uint32_t)v[1]);
     uf_union(parent, (uint32_t)v[1], (uint32_t)v[2]);
 }
@@ -140,35 +135,13 @@ __global__ void __launch_bounds__(256) remap_faces_kernel(int V, int F, const in
     const int f = blockIdx.x * 256 + threadIdx.x;
     if (f >= F) return;
     int32_t v[3], w[3] = {-1, -1, -1};
-    const bool ok = face_ok(V, f, faces, nullptr, v);
+    const bool ok = face_in_range(V, (size_t)f, faces, nullptr, v);
     if (ok) { w[0] = remap[v[0]]; w[1] = remap[v[1]]; w[2] = remap[v[2]]; }
     out_faces[3 * (size_t)f] = w[0]; out_faces[3 * (size_t)f + 1] = w[1]; out_faces[3 * (size_t)f + 2] = w[2];
     keep[f] = ok && w[0] != w[1] && w[1] != w[2] && w[0] != w[2];
 }
 
 // ---- compaction ------------------------------------------------------------------------------------------------------------------------
-constexpr int SCAN_PER = 8, SCAN_TILE = 256 * SCAN_PER;
-
-// exclusive scan of one value per lane over the 256-lane workgroup; returns the lane's offset, *total the sum
-__device__ __forceinline__ uint32_t block_scan256(uint32_t v, uint32_t *lds, uint32_t *total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1)
-    {
-        const uint32_t t = __shfl_up(incl, d);
-        if (lane >= d) incl += t;
-    }
-    __syncthreads();
-    if (lane == 63) lds[wave] = incl;
-    __syncthreads();
-    uint32_t base = 0, all = 0;
-    for (int w = 0; w < 4; w++) { const uint32_t t = lds[w]; if (w < wave) base += t; all += t; }
-    *total = all;
-    return base + incl - v;
-}
-
 __global__ void __launch_bounds__(256) root_count_kernel(int V, const uint32_t *__restrict__ label, uint32_t *__restrict__ block_count)
 {
     __shared__ uint32_t lds[4];
@@ -180,18 +153,6 @@ __global__ void __launch_bounds__(256) root_count_kernel(int V, const uint32_t *
     uint32_t total;
     block_scan256(n, lds, &total);
     if (threadIdx.x == 0) block_count[blockIdx.x] = total;
-}
-
-// one workgroup: block_count -> exclusive offsets in place, the total to *count
-__global__ void __launch_bounds__(256) root_offsets_kernel(int nb, uint32_t *block_count, int32_t *__restrict__ count)
-{
-    __shared__ uint32_t lds[4];
-    const int span = (nb + 255) / 256, lo = min(nb, (int)threadIdx.x * span), hi = min(nb, lo + span);
-    uint32_t n = 0;
-    for (int i = lo; i < hi; i++) n += block_count[i];
-    uint32_t total, run = block_scan256(n, lds, &total);
-    for (int i = lo; i < hi; i++) { const uint32_t t = block_count[i]; block_count[i] = run; run += t; }
-    if (threadIdx.x == 0) *count = (int32_t)total;
 }
 
 __global__ void __launch_bounds__(256) root_rank_kernel(int V, const uint32_t *__restrict__ label, const uint32_t *__restrict__ block_offset,
@@ -272,7 +233,7 @@ __global__ void __launch_bounds__(256) edge_keys_kernel(int V, int F, const int3
     const int f = blockIdx.x * 256 + threadIdx.x;
     if (f >= F) return;
     int32_t v[3];
-    const bool ok = face_ok(V, f, faces, keep, v);
+    const bool ok = face_in_range(V, (size_t)f, faces, keep, v);
 #pragma unroll
     for (int k = 0; k < 3; k++)
     {
@@ -285,58 +246,23 @@ __global__ void __launch_bounds__(256) edge_keys_kernel(int V, int F, const int3
 __global__ void __launch_bounds__(256) edge_runs_kernel(int V, size_t E, const uint32_t *__restrict__ lo, const uint32_t *__restrict__ hi,
                                                         unsigned long long *counts)
 {
-    __shared__ uint32_t red[4][4];
     const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
-    uint32_t c[4] = {0, 0, 0, 0}; // edges, boundary, manifold, nonmanifold
-    if (j < E)
-    {
-        const uint32_t l = lo[j], h = hi[j];
-        if (l < (uint32_t)V && (j == 0 || lo[j - 1] != l || hi[j - 1] != h))
-        {
-            const bool two = j + 1 < E && lo[j + 1] == l && hi[j + 1] == h;
-            const bool three = two && j + 2 < E && lo[j + 2] == l && hi[j + 2] == h;
-            c[0] = 1; c[1] = !two; c[2] = two && !three; c[3] = three;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-    {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) c[k] += __shfl_xor(c[k], o);
-    }
-    if ((threadIdx.x & 63) == 0)
-        for (int k = 0; k < 4; k++) red[threadIdx.x >> 6][k] = c[k];
-    __syncthreads();
-    if (threadIdx.x < 4)
-    {
-        const uint32_t t = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-        if (t) __hip_atomic_fetch_add(counts + threadIdx.x, (unsigned long long)t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
-int bit_length(uint32_t v)
-{
-    int n = 1; // at least one pass bit
-    while (n < 32 && (v >> n)) n++;
-    return n;
+    const uint32_t run = (uint32_t)edge_run_head(V, E, j, lo, hi);
+    uint32_t c[4] = {run > 0, run == 1, run == 2, run == 3}; // edges, boundary, manifold, nonmanifold
+    count4_into(counts, c);
 }
 
 struct SortCarve
 {
     uint32_t *a[2], *b[2]; // two ping-pong pairs of n words each
     void *scratch;
-    size_t bytes;
 };
 
-SortCarve sort_carve(char *p, size_t n)
+SortCarve sort_carve(Carver &w, size_t n)
 {
     SortCarve c;
-    char *const base = p;
-    auto take = [&](size_t bytes) { char *q = p; p += ts_align_up(bytes); return q; };
-    c.a[0] = (uint32_t *)take(n * 4); c.a[1] = (uint32_t *)take(n * 4);
-    c.b[0] = (uint32_t *)take(n * 4); c.b[1] = (uint32_t *)take(n * 4);
-    c.scratch = take(ts_radix_scratch_bytes(n));
-    c.bytes = (size_t)(p - base);
+    c.a[0] = w.words(n); c.a[1] = w.words(n); c.b[0] = w.words(n); c.b[1] = w.words(n);
+    c.scratch = w.bytes(ts_radix_scratch_bytes(n)); // without the floor of sort_scratch_bytes: this unit's sizes stay as they were
     return c;
 }
 
@@ -351,24 +277,29 @@ struct CompactCarve
 CompactCarve compact_carve(void *ws, int V)
 {
     CompactCarve c;
+    Carver w(ws);
     const size_t n = (size_t)(V > 0 ? V : 0);
-    c.nb = (int)((n + SCAN_TILE - 1) / SCAN_TILE);
-    char *p = (char *)ts_align_up((size_t)ws);
-    c.root_rank = (uint32_t *)p; p += ts_align_up(n * 4);
-    c.block_count = (uint32_t *)p; p += ts_align_up((size_t)c.nb * 4);
-    c.sort = sort_carve(p, n);
-    c.bytes = (size_t)(p - (char *)ws) + c.sort.bytes;
+    c.nb = (int)scan_blocks(n);
+    c.root_rank = w.words(n);
+    c.block_count = w.words((size_t)c.nb);
+    c.sort = sort_carve(w, n);
+    c.bytes = w.used();
     return c;
 }
 
-inline unsigned blocks256(size_t n) { return (unsigned)((n + 255) / 256); }
+size_t census_bytes(size_t E)
+{
+    Carver w(nullptr);
+    sort_carve(w, E);
+    return w.used();
+}
 } // namespace
 
 size_t ts_weld_workspace_bytes(int V, int F)
 {
     const size_t labels = knn_carve(nullptr, V).bytes;
     const size_t compact = compact_carve(nullptr, V).bytes;
-    const size_t census = sort_carve(nullptr, 3 * (size_t)(F > 0 ? F : 0)).bytes;
+    const size_t census = census_bytes(3 * (size_t)(F > 0 ? F : 0));
     return std::max(labels, std::max(compact, census)) + 2 * TS_ALIGN;
 }
 
@@ -405,7 +336,7 @@ hipError_t ts_weld_compact(int V, const uint32_t *label, const float *vertices, 
     e = hipMemsetAsync(c.root_rank, 0, (size_t)V * sizeof(uint32_t), s); // a foreign label that names a non-root then ranks 0: always a row of out_vertices
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(root_count_kernel, dim3(c.nb), dim3(256), 0, s, V, label, c.block_count);
-    hipLaunchKernelGGL(root_offsets_kernel, dim3(1), dim3(256), 0, s, c.nb, c.block_count, count);
+    hipLaunchKernelGGL(scan_offsets_kernel<1>, dim3(1), dim3(256), 0, s, c.nb, c.block_count, (uint32_t *)count);
     hipLaunchKernelGGL(root_rank_kernel, dim3(c.nb), dim3(256), 0, s, V, label, c.block_count, c.root_rank);
     hipLaunchKernelGGL(remap_kernel, dim3(nv), dim3(256), 0, s, V, label, c.root_rank, (const uint32_t *)vertices, mode == 0 ? 1 : 0, remap,
                        (uint32_t *)out_vertices);
@@ -429,7 +360,8 @@ hipError_t ts_weld_edge_census(int V, int F, const int32_t *faces, const uint8_t
 {
     if (F <= 0) return hipSuccess;
     const size_t E = 3 * (size_t)F;
-    const SortCarve c = sort_carve((char *)ts_align_up((size_t)ws), E);
+    Carver w(ws);
+    const SortCarve c = sort_carve(w, E);
     hipError_t e = hipMemsetAsync(counts, 0, 4 * sizeof(unsigned long long), s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(edge_keys_kernel, dim3(blocks256((size_t)F)), dim3(256), 0, s, V, F, faces, keep, c.a[0], c.b[0]);

@@ -37,6 +37,10 @@ A "ground truth" is rendered from a hidden set of triangles from several cameras
     python examples/train_synthetic.py --eval-mesh --extract-mesh RES --extract-color
                                                         fuse the training targets' colour in the same volume (diff_recon_hip.fuse_colored_mesh) and
                                                         print the PSNR / SSIM of the vertex-coloured fused mesh beside the soup's own
+    python examples/train_synthetic.py --eval-mesh --extract-mesh RES --bake-texture R [--out PATH]
+                                                        bake a texture atlas of R texels per face edge for the fused mesh from the training targets
+                                                        (diff_recon_hip.bake_texture) and print the PSNR / SSIM of the textured fused mesh beside the
+                                                        vertex-coloured one; with --out, write it as a GLB with the atlas as an embedded PNG
     python examples/train_synthetic.py --eval-mesh --extract-mesh RES --fill-holes N
                                                         close the boundary loops of the fused mesh of at most N edges with centroid fans before anything
                                                         smooths or simplifies it (diff_recon_hip.fill_fused); prints the loops, the filled ones, the open
@@ -234,7 +238,8 @@ def train(rasterizer="2D", iters=200, triangles=20000, width=256, height=192, se
 
 
 def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, height=192, seed=0, views=2, refine=False, weld=None, geometry=None, surface=None,
-                visible=False, extract=None, extract_color=False, simplify=None, min_piece=0, smooth=None, fill=None, split=False, orient=None):
+                visible=False, extract=None, extract_color=False, simplify=None, min_piece=0, smooth=None, fill=None, split=False, orient=None, texture=None,
+                out=None):
     """PSNR / SSIM of the model's opaque mesh -- mesh_from_triangles: one colour per face from the DC coefficients, back faces as reversed
     twins, the soup saveGLB writes -- against the hidden targets of train() called with the same arguments (diff_recon_hip.evaluate_mesh).
     refine: the result also holds "refined", the same scores (plus "kept" and "triangles") of the mesh after a census over these views
@@ -256,6 +261,9 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
     extract_color (with extract): the views' targets are fused as colour in the same volume (diff_recon_hip.fuse_colored_mesh; the mesh is the
     same) and "fused" also holds "color": diff_recon_hip.evaluate_vertex_colors of the vertex-coloured fused mesh on these views, "vertices"
     and "coloured", the number of vertices that found a colour.
+    texture = R (with extract): "fused" also holds "texture": diff_recon_hip.evaluate_textured of the fused mesh with an atlas of R texels per face
+    edge baked from these views' targets (diff_recon_hip.bake_texture), the atlas' "width" and "height", "texels" and "observed", the texels that
+    a pixel of some view fell into; the others take their face's mean.  out (with texture): the path of the GLB that save_glb_textured_mesh writes.
     simplify = K and / or min_piece = N (with extract): "fused" also holds "simplified": the fused mesh after diff_recon_hip.simplify_mesh on the
     volume's grid in cells of K voxels and drop_small_pieces(N) (diff_recon_hip.simplify_fused) -- its "topology", "to_soup", the "stats" of the two steps and, with
     extract_color, "color" (the vertex colours averaged per cluster).
@@ -330,6 +338,14 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
             res["fused"]["color"] = dict(D.evaluate_vertex_colors(cams, fused.vertices, fused.faces, fused.vertex_color, bg_color=kw["bg_color"]),
                                          vertices=int(fused.vertices.shape[0]), coloured=int(fused.color_valid.sum()),
                                          soup={k: res[k] for k in ("mean_psnr", "mean_ssim")})
+        if texture is not None:
+            baked = D.bake_texture(cams, fused.vertices, fused.faces, int(texture))
+            res["fused"]["texture"] = dict(D.evaluate_textured(cams, fused.vertices, fused.faces, baked, bg_color=kw["bg_color"]), res=int(texture),
+                                           width=baked.layout.width, height=baked.layout.height, faces=int(fused.faces.shape[0]),
+                                           texels=int(fused.faces.shape[0]) * baked.layout.texels_per_face, observed=int((baked.state == 3).sum()))
+            if out is not None:
+                D.save_glb_textured_mesh(out, fused.vertices, fused.faces, baked)
+                res["fused"]["texture"]["out"] = str(out)
         topology_of = lambda mesh: D.mesh_topology(mesh.vertices.shape[0], mesh.faces)
         if split and not simplified:
             before = res["fused"]["topology"]
@@ -443,6 +459,13 @@ def fused_color_report(c):
     return [f"fused mesh, colours fused from the {len(c['psnr'])} training views ({c['coloured']} of {c['vertices']} vertices coloured): "
             f"mean PSNR {c['mean_psnr']:.2f} dB, mean SSIM {c['mean_ssim']:.4f}",
             f"the soup, one colour per face: mean PSNR {c['soup']['mean_psnr']:.2f} dB, mean SSIM {c['soup']['mean_ssim']:.4f}"]
+
+
+def fused_texture_report(t):
+    """The lines --bake-texture prints for mesh_scores(...)["fused"]["texture"]."""
+    lines = [f"fused mesh, a {t['width']} x {t['height']} atlas of {t['res']} texels per face edge baked from the {len(t['psnr'])} training views "
+             f"({t['observed']} of {t['texels']} texels observed): mean PSNR {t['mean_psnr']:.2f} dB, mean SSIM {t['mean_ssim']:.4f}"]
+    return lines + ([f"textured mesh written to {t['out']}"] if "out" in t else [])
 
 
 def geometry_report(g, title="mesh geometry"):
@@ -643,7 +666,17 @@ if __name__ == "__main__":
                     help="with --extract-mesh: make every orientable piece of the mesh wind one way (diff_recon_hip.orient_fused) after --split-nonmanifold "
                          "and before --fill-holes; with --weld-mesh: the same on the welded mesh; print the pieces, the non-orientable ones, the "
                          "same-direction edges before and after and the faces flipped")
+    ap.add_argument("--bake-texture", type=int, default=None, metavar="R", help="with --extract-mesh: bake a texture atlas of R texels per face edge (1 .. 64) for the fused "
+                                                                                "mesh from the training targets (diff_recon_hip.bake_texture) and print the PSNR / SSIM "
+                                                                                "of the textured mesh")
+    ap.add_argument("--out", default=None, metavar="PATH", help="with --bake-texture: write the textured fused mesh as a GLB (diff_recon_hip.save_glb_textured_mesh)")
     a = ap.parse_args()
+    if a.bake_texture is not None and a.extract_mesh is None:
+        ap.error("--bake-texture textures the mesh of --extract-mesh")
+    if a.bake_texture is not None and not 1 <= a.bake_texture <= 64:
+        ap.error("--bake-texture needs 1 .. 64 texels per face edge")
+    if a.out is not None and a.bake_texture is None:
+        ap.error("--out writes the mesh of --bake-texture")
     if a.orient_faces is not None and a.extract_mesh is None and a.weld_mesh is None:
         ap.error("--orient-faces orients the mesh of --extract-mesh or of --weld-mesh")
     if a.split_nonmanifold and a.extract_mesh is None:
@@ -696,7 +729,8 @@ if __name__ == "__main__":
     if a.eval_mesh:
         res = mesh_scores(m, a.rasterizer, a.iters, a.triangles, views=a.views, refine=a.refine_mesh, weld=a.weld_mesh, geometry=a.eval_geometry,
                           surface=a.eval_surface, visible=a.eval_visible, extract=a.extract_mesh, extract_color=a.extract_color, simplify=a.simplify_mesh,
-                          min_piece=a.min_piece, smooth=a.smooth_mesh, fill=a.fill_holes, split=a.split_nonmanifold, orient=a.orient_faces)
+                          min_piece=a.min_piece, smooth=a.smooth_mesh, fill=a.fill_holes, split=a.split_nonmanifold, orient=a.orient_faces,
+                          texture=a.bake_texture, out=a.out)
         for v, (p_, s_) in enumerate(zip(res["psnr"], res["ssim"])):
             print(f"  opaque mesh, view {v}: PSNR {p_:.2f} dB  SSIM {s_:.4f}")
         print(f"opaque mesh of {m._vertex.shape[0]} triangles: mean PSNR {res['mean_psnr']:.2f} dB, mean SSIM {res['mean_ssim']:.4f} over {len(res['psnr'])} views")
@@ -721,6 +755,9 @@ if __name__ == "__main__":
                 print(line)
             if a.extract_color:
                 for line in fused_color_report(res["fused"]["color"]):
+                    print(line)
+            if a.bake_texture is not None:
+                for line in fused_texture_report(res["fused"]["texture"]):
                     print(line)
             late = "manifold" in res["fused"] and "simplified" in res["fused"]  # the split, and the fill behind it, follow the simplification
             if "manifold" in res["fused"] and not late:

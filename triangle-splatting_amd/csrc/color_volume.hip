@@ -9,8 +9,10 @@
 // three image loads are issued only for lanes inside the band, and a sample that is not coloured touches neither state array; a coloured one
 // reads and writes its 28 bytes.
 // Field, sampler and interpolation: one item (sample, point, pixel) per lane.  The sampler unrolls its eight corners at compile time and
-// loops over the channels, so nothing is indexed at run time and no kernel here uses scratch.
+// loops over the channels, so nothing is indexed at run time and no kernel here uses scratch.  The barycentrics of the interpolation are
+// csrc/ts_mesh_bary.h's, which mesh_atlas.hip (libts_atlas.so) includes as well.
 #include "ts_color_launch.h"
+#include "ts_mesh_bary.h" // the barycentrics of a pixel, shared with mesh_atlas.hip
 
 #include <float.h>
 
@@ -176,20 +178,6 @@ __global__ void __launch_bounds__(TPB) sample_kernel(int nx, int ny, int nz, flo
     valid[i] = ok ? 1 : 0;
 }
 
-__device__ __forceinline__ double ray_dot_cross(double r0, double r1, const double x[3], const double y[3])
-{
-    const double n0 = x[1] * y[2] - x[2] * y[1], n1 = x[2] * y[0] - x[0] * y[2], n2 = x[0] * y[1] - x[1] * y[0];
-    return (r0 * n0 + r1 * n1) + n2;
-}
-
-__device__ __forceinline__ void to_view(const float *__restrict__ view, const float *__restrict__ p, double v[3])
-{
-    const double p0 = (double)p[0], p1 = (double)p[1], p2 = (double)p[2];
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-        v[k] = ((p0 * (double)view[k] + p1 * (double)view[4 + k]) + p2 * (double)view[8 + k]) + (double)view[12 + k];
-}
-
 __global__ void __launch_bounds__(TPB) interpolate_kernel(const float *__restrict__ view, float tan_fovx, float tan_fovy, int W, int H, int V,
                                                            const float *__restrict__ vertices, int F, const int32_t *__restrict__ faces,
                                                            const int32_t *__restrict__ face_idx, int C, const float *__restrict__ attributes,
@@ -197,45 +185,15 @@ __global__ void __launch_bounds__(TPB) interpolate_kernel(const float *__restric
 {
     const size_t plane = (size_t)W * (size_t)H, p = (size_t)blockIdx.x * TPB + threadIdx.x;
     if (p >= plane) return;
-    const int f = face_idx[p];
-    int ia = -1, ib = -1, ic = -1;
-    if (f >= 0 && f < F)
-    {
-        ia = faces[3 * (size_t)f];
-        ib = faces[3 * (size_t)f + 1];
-        ic = faces[3 * (size_t)f + 2];
-    }
-    if (!(ia >= 0 && ia < V && ib >= 0 && ib < V && ic >= 0 && ic < V)) // not drawn
+    int ia, ib, ic;
+    if (!drawn_face(face_idx[p], F, V, faces, ia, ib, ic)) // not drawn
     {
         for (int ch = 0; ch < C; ++ch) out[(size_t)ch * plane + p] = background[ch];
         if (bary) bary[p] = bary[plane + p] = bary[2 * plane + p] = 0.0f;
         return;
     }
-    const int col = (int)(p % (size_t)W), row = (int)(p / (size_t)W);
-    double a[3], b[3], c[3];
-    to_view(view, vertices + 3 * (size_t)ia, a);
-    to_view(view, vertices + 3 * (size_t)ib, b);
-    to_view(view, vertices + 3 * (size_t)ic, c);
-    const double r0 = (((double)col + 0.5) / (0.5 * (double)W) - 1.0) * (double)tan_fovx;
-    const double r1 = (((double)row + 0.5) / (0.5 * (double)H) - 1.0) * (double)tan_fovy;
-    double wa = ray_dot_cross(r0, r1, b, c), wb = ray_dot_cross(r0, r1, c, a), wc = ray_dot_cross(r0, r1, a, b);
-    if ((wa + wb) + wc < 0.0)
-    {
-        wa = -wa;
-        wb = -wb;
-        wc = -wc;
-    }
-    wa = wa >= 0.0 ? wa : 0.0; // negative or NaN
-    wb = wb >= 0.0 ? wb : 0.0;
-    wc = wc >= 0.0 ? wc : 0.0;
-    const double s = (wa + wb) + wc;
-    double alpha = 1.0 / 3.0, beta = 1.0 / 3.0, gamma = 1.0 / 3.0;
-    if (finite_d(s) && s > 0.0)
-    {
-        alpha = wa / s;
-        beta = wb / s;
-        gamma = wc / s;
-    }
+    double alpha, beta, gamma;
+    pixel_barycentrics(view, tan_fovx, tan_fovy, W, H, (int)(p % (size_t)W), (int)(p / (size_t)W), vertices, ia, ib, ic, alpha, beta, gamma);
     const float *A = attributes + (size_t)ia * (size_t)C, *B = attributes + (size_t)ib * (size_t)C, *G = attributes + (size_t)ic * (size_t)C;
     for (int ch = 0; ch < C; ++ch)
         out[(size_t)ch * plane + p] = (float)((alpha * (double)A[ch] + beta * (double)B[ch]) + gamma * (double)G[ch]);

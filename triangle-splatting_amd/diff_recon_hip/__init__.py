@@ -80,6 +80,12 @@
                           non-orientable pieces reported and left alone; the piece faces by its anchor, by majority or by the sign of its
                           quantised volume; bit-equal to a numpy reference) -- the pass between split_nonmanifold and fill_holes; no
                           counterpart in the reference; loaded on first use
+    mesh_texture.py       atlas_layout / face_uvs (res x res half-cells, two faces to a cell: every face gets res (res + 1) / 2 texels of its own),
+                          texel_index (the texel of every pixel, from interpolate_vertex_attributes' barycentrics), TextureAtlas (a MeshCensus
+                          over the texels: bit-identical in any view order, atlases add; resolve falls back texel -> face -> caller -> fill),
+                          render_textured, bake_texture, evaluate_textured and save_glb_textured_mesh (a GLB with TEXCOORD_0 and the atlas as
+                          an embedded PNG, exact under NEAREST) -- colour resolution that does not depend on the face count; no counterpart
+                          in the reference; loaded on first use
     metrics.py           psnr, ssim (= 1 - SSIMLoss), evaluate_mesh and evaluate_vertex_colors: PSNR / SSIM of a mesh's opaque render (one
                           colour per face, or per vertex) against each view's gt_image
                           (reference: src/diff_recon/trainers/trainer_utils.py:331-336, VanillaTS_trainer.py:156-190)
@@ -87,7 +93,7 @@
                           replayed with one launch -- no counterpart in the reference, whose forward reads num_rendered back every step
 
 Native code: libts2d.so (include/ts_loss.h, include/ts_model.h, include/ts_optim.h, include/ts2d.h, include/ts_mesh.h, include/ts_weld.h) and, for
-mesh_distance.py, libts_geom.so beside this file (include/ts_geom.h), for mesh_surface.py, libts_bvh.so (include/ts_bvh.h), for mesh_ray.py, libts_ray.so (include/ts_ray.h), for volume.py, libts_volume.so (include/ts_volume.h), for color_volume.py, libts_color.so (include/ts_color.h), for mesh_simplify.py, libts_simplify.so (include/ts_simplify.h), for mesh_smooth.py, libts_smooth.so (include/ts_smooth.h), for mesh_holes.py, libts_holes.so (include/ts_holes.h), for mesh_manifold.py, libts_manifold.so (include/ts_manifold.h), for mesh_orient.py, libts_orient.so (include/ts_orient.h).  No CPU / eager fallback anywhere.
+mesh_distance.py, libts_geom.so beside this file (include/ts_geom.h), for mesh_surface.py, libts_bvh.so (include/ts_bvh.h), for mesh_ray.py, libts_ray.so (include/ts_ray.h), for volume.py, libts_volume.so (include/ts_volume.h), for color_volume.py, libts_color.so (include/ts_color.h), for mesh_simplify.py, libts_simplify.so (include/ts_simplify.h), for mesh_smooth.py, libts_smooth.so (include/ts_smooth.h), for mesh_holes.py, libts_holes.so (include/ts_holes.h), for mesh_manifold.py, libts_manifold.so (include/ts_manifold.h), for mesh_orient.py, libts_orient.so (include/ts_orient.h), for mesh_texture.py, libts_atlas.so (include/ts_atlas.h).  No CPU / eager fallback anywhere.
 """
 from .losses import L1, SSIMLoss, ssimLoss, PhotometricLoss, photometric_loss, DepthNormalLoss, DoGLoss, SmoothnessLoss, dogLoss, smoothnessLoss, downsample_bilinear, downsample_bilinear_many  # noqa: F401
 from .triangle_renderer import TriangleRenderer  # noqa: F401
@@ -119,6 +125,8 @@ _SMOOTH_NAMES = ("MeshAdjacency", "SmoothedMesh", "vertex_adjacency", "smooth_me
 _HOLES_NAMES = ("BoundaryLoops", "FilledMesh", "boundary_loops", "loop_vertices", "fill_holes", "fill_fused")
 _MANIFOLD_NAMES = ("VertexFans", "ManifoldMesh", "vertex_fans", "split_nonmanifold", "manifold_fused")
 _ORIENT_NAMES = ("OrientedMesh", "orient_faces", "orient_fused")
+_TEXTURE_NAMES = ("AtlasLayout", "BakedTexture", "TextureAtlas", "atlas_layout", "face_uvs", "texel_index", "render_textured", "bake_texture",
+                  "evaluate_textured", "encode_png", "save_glb_textured_mesh")
 
 
 def __getattr__(name):
@@ -155,4 +163,8 @@ def __getattr__(name):
         import importlib
         module = importlib.import_module(".mesh_orient", __name__)
         return module if name == "mesh_orient" else getattr(module, name)
+    if name in _TEXTURE_NAMES or name == "mesh_texture":  # mesh_texture.py and libts_atlas.so likewise
+        import importlib
+        module = importlib.import_module(".mesh_texture", __name__)
+        return module if name == "mesh_texture" else getattr(module, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

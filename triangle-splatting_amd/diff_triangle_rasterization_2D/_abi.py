@@ -1,5 +1,5 @@
 """The C ABI of libts2d.so as ctypes sees it, declared once: the mirrors of the structs of include/*.h and the signature of every function
-they declare (and of the lab library's additions, csrc/ts2d_lab.h, and of the other ten product libraries: libts_geom.so, include/ts_geom.h, libts_bvh.so, include/ts_bvh.h, libts_ray.so, include/ts_ray.h, libts_volume.so, include/ts_volume.h, libts_color.so, include/ts_color.h, libts_simplify.so, include/ts_simplify.h, libts_smooth.so, include/ts_smooth.h, libts_holes.so, include/ts_holes.h, libts_manifold.so, include/ts_manifold.h, and libts_orient.so, include/ts_orient.h).  Pure ctypes: no torch, no library is loaded here -- `_C.py` binds the
+they declare (and of the lab library's additions, csrc/ts2d_lab.h, and of the other eleven product libraries: libts_geom.so, include/ts_geom.h, libts_bvh.so, include/ts_bvh.h, libts_ray.so, include/ts_ray.h, libts_volume.so, include/ts_volume.h, libts_color.so, include/ts_color.h, libts_simplify.so, include/ts_simplify.h, libts_smooth.so, include/ts_smooth.h, libts_holes.so, include/ts_holes.h, libts_manifold.so, include/ts_manifold.h, libts_orient.so, include/ts_orient.h, and libts_atlas.so, include/ts_atlas.h).  Pure ctypes: no torch, no library is loaded here -- `_C.py` binds the
 library the package loads, the CPU tests bind a CDLL of their own.  tests/test_cabi_cpu.py holds both tables against the headers: the structs
 by sizeof / offsetof, the functions prototype by prototype.
 
@@ -403,6 +403,29 @@ def bind_orient(lib):
     if missing:
         raise ImportError(f"{getattr(lib, '_name', lib)} does not export {', '.join(missing)}: rebuild it with `python triangle-splatting_amd/build.py`")
     for name, (restype, argtypes) in ORIENT_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return lib
+
+
+# include/ts_atlas.h: the whole C ABI of diff_recon_hip/libts_atlas.so, the twelfth library (diff_recon_hip/mesh_texture.py loads and binds it)
+ATLAS_SIGNATURES = {
+    "tsa_last_error": (C.c_char_p, []),
+    "tsa_texel_index": (C.c_int, [_vp, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, _vp,
+                                  _vp, _vp, _vp]),
+    "tsa_face_totals": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    "tsa_resolve": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, C.c_int32, _vp, C.POINTER(C.c_float), _vp, _vp, _vp, _vp]),
+    "tsa_render": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
+}
+
+
+def bind_atlas(lib):
+    """Sets restype and argtypes of every function of include/ts_atlas.h on `lib` (a ctypes.CDLL of libts_atlas.so); a library that
+    lacks one is refused."""
+    missing = [name for name in ATLAS_SIGNATURES if not hasattr(lib, name)]
+    if missing:
+        raise ImportError(f"{getattr(lib, '_name', lib)} does not export {', '.join(missing)}: rebuild it with `python triangle-splatting_amd/build.py`")
+    for name, (restype, argtypes) in ATLAS_SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     return lib

@@ -2,6 +2,7 @@
 // (csrc/ts_bvh_layout.h).
 //
 // Built with -ffp-contract=off: the slab interval, the watertight triangle test and the reported t' round every operation (the header's text).
+// The two tests are csrc/ts_ray_tests.h, shared with mesh_inside.hip (include/ts_inside.h), which counts all hits where this unit keeps the first.
 //
 // The rays go through the front half of the box searches (ts_knn_front.h): the bounding box of the finite ORIGINS, a Morton sort, a float4
 // gather that carries the original index; a ray with a non-finite origin is stored as NaNs.  The key is the origin alone: the rays of one
@@ -19,6 +20,7 @@
 // Stack: STACK entries per wave in LDS, whatever the data (ts_bvh_layout.h).
 #include "ts_bvh_layout.h"
 #include "ts_ray_launch.h"
+#include "ts_ray_tests.h"
 
 #include <algorithm>
 
@@ -32,39 +34,6 @@ size_t ray_carve_bytes(int n)
     const size_t b = knn_carve(nullptr, n).bytes;
     return n > TS_RS_SMALL_BELOW ? std::max(b, knn_carve(nullptr, TS_RS_SMALL_BELOW).bytes) : b;
 }
-
-// min and max of the header: of two equal values (+0 and -0) the first stays
-__device__ __forceinline__ double min2(double x, double y) { return y < x ? y : x; }
-__device__ __forceinline__ double max2(double x, double y) { return y > x ? y : x; }
-
-__device__ __forceinline__ bool finite_f(float x) { return fabsf(x) <= FLT_MAX; }
-
-// one axis of the slab interval: false when the direction is zero and the origin lies outside [lo, hi]
-__device__ __forceinline__ bool slab_axis(double lo, double hi, double o, double d, double &tn, double &tf)
-{
-    if (d == 0.0) return lo <= o && o <= hi; // contributes (-inf, +inf)
-    const double ta = (lo - o) / d, tb = (hi - o) / d;
-    const double near = min2(ta, tb), far = max2(ta, tb);
-    const double near_p = near - fabs(near) * 0x1p-40, far_p = far + fabs(far) * 0x1p-40;
-    tn = max2(tn, near_p);
-    tf = min2(tf, far_p);
-    return true;
-}
-
-// the slab interval of the header: false when a zero-direction axis fails or tn > tf; tmin and the upper limit are the caller's
-__device__ __forceinline__ bool slab(double ox, double oy, double oz, double dx, double dy, double dz, float mnx, float mny, float mnz, float mxx,
-                                     float mxy, float mxz, double &tn, double &tf)
-{
-    const double inf = __longlong_as_double(0x7FF0000000000000ll);
-    tn = -inf; tf = inf; // max2(-inf, x) = x and min2(+inf, x) = x, bit for bit: a zero axis, and this start, contribute nothing
-    bool ok = slab_axis((double)mnx, (double)mxx, ox, dx, tn, tf);
-    ok &= slab_axis((double)mny, (double)mxy, oy, dy, tn, tf);
-    ok &= slab_axis((double)mnz, (double)mxz, oz, dz, tn, tf);
-    return ok && tn <= tf;
-}
-
-__device__ __forceinline__ double sel3(int k, double x, double y, double z) { return k == 0 ? x : (k == 1 ? y : z); }
-__device__ __forceinline__ float sel3f(int k, float x, float y, float z) { return k == 0 ? x : (k == 1 ? y : z); }
 
 __global__ void __launch_bounds__(TPB) cast_kernel(int Q, int nleaves, int nlevels, const float4 *__restrict__ osp, const float *__restrict__ directions,
                                                     const float *__restrict__ t_limit, double tmin, double tmax, int cull_back,
@@ -110,18 +79,7 @@ __global__ void __launch_bounds__(TPB) cast_kernel(int Q, int nleaves, int nleve
     const double ox = live ? (double)p.x : 0.0, oy = live ? (double)p.y : 0.0, oz = live ? (double)p.z : 0.0;
     const double dx = live ? (double)fdx : 1.0, dy = live ? (double)fdy : 0.0, dz = live ? (double)fdz : 0.0;
 
-    // the dominant axis and the shear of the watertight test, once per ray
-    int kz = 0;
-    if (fabs(dy) > fabs(dx)) kz = 1;
-    if (fabs(dz) > fabs(kz ? dy : dx)) kz = 2;
-    int kx = kz == 2 ? 0 : kz + 1, ky = kx == 2 ? 0 : kx + 1;
-    const double dkz = sel3(kz, dx, dy, dz);
-    if (dkz < 0.0)
-    {
-        const int s = kx; kx = ky; ky = s;
-    }
-    const double Sx = sel3(kx, dx, dy, dz) / dkz, Sy = sel3(ky, dx, dy, dz) / dkz, Sz = 1.0 / dkz;
-    const double okx = sel3(kx, ox, oy, oz), oky = sel3(ky, ox, oy, oz), okz = sel3(kz, ox, oy, oz);
+    const RayShear sh = ray_shear(ox, oy, oz, dx, dy, dz); // the dominant axis and the shear of the watertight test, once per ray
 
     double best = hi;
     uint32_t bestid = 0xFFFFFFFFu;
@@ -156,26 +114,18 @@ __global__ void __launch_bounds__(TPB) cast_kernel(int Q, int nleaves, int nleve
                 const float ax = lf.v[j][0], ay = lf.v[j][1], az = lf.v[j][2], bx = lf.v[j][3], by = lf.v[j][4], bz = lf.v[j][5], cx = lf.v[j][6],
                             cy = lf.v[j][7], cz = lf.v[j][8];
                 double tn, tf;
-                const bool crossed = slab(ox, oy, oz, dx, dy, dz, fminf(fminf(ax, bx), cx), fminf(fminf(ay, by), cy), fminf(fminf(az, bz), cz),
-                                          fmaxf(fmaxf(ax, bx), cx), fmaxf(fmaxf(ay, by), cy), fmaxf(fmaxf(az, bz), cz), tn, tf);
+                const bool crossed = face_slab(ox, oy, oz, dx, dy, dz, ax, ay, az, bx, by, bz, cx, cy, cz, tn, tf);
                 if (!live || !crossed || !(tf >= tmin) || tn > best) continue; // t' >= tn(AABB(T)) > best: neither a gain nor a tie
-                const double Akz = (double)sel3f(kz, ax, ay, az) - okz, Bkz = (double)sel3f(kz, bx, by, bz) - okz, Ckz = (double)sel3f(kz, cx, cy, cz) - okz;
-                const double Ax = ((double)sel3f(kx, ax, ay, az) - okx) - Sx * Akz, Ay = ((double)sel3f(ky, ax, ay, az) - oky) - Sy * Akz;
-                const double Bx = ((double)sel3f(kx, bx, by, bz) - okx) - Sx * Bkz, By = ((double)sel3f(ky, bx, by, bz) - oky) - Sy * Bkz;
-                const double Cx = ((double)sel3f(kx, cx, cy, cz) - okx) - Sx * Ckz, Cy = ((double)sel3f(ky, cx, cy, cz) - oky) - Sy * Ckz;
-                const double U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
-                const double det = (U + V) + W;
-                const bool neg = U < 0.0 || V < 0.0 || W < 0.0, pos = U > 0.0 || V > 0.0 || W > 0.0;
-                if (det == 0.0 || (neg && pos) || (cull_back && !(det > 0.0))) continue;
-                const double Az = Sz * Akz, Bz = Sz * Bkz, Cz = Sz * Ckz;
-                const double tt = ((U * Az + V * Bz) + W * Cz) / det;
+                const FaceEdges e = face_edges(sh, ax, ay, az, bx, by, bz, cx, cy, cz);
+                if (!face_candidate(e) || (cull_back && !(e.det > 0.0))) continue;
+                const double tt = face_t(sh, e);
                 const double tp = max2(tt, tn);
                 if (!(tp >= tmin && tp <= hi)) continue;
                 if (tp < best || (tp == best && (uint32_t)id < bestid))
                 {
                     best = tp; bestid = (uint32_t)id;
-                    b0 = (float)(U / det); b1 = (float)(V / det); b2 = (float)(W / det);
-                    bside = det > 0.0 ? 1 : -1;
+                    b0 = (float)(e.U / e.det); b1 = (float)(e.V / e.det); b2 = (float)(e.W / e.det);
+                    bside = e.det > 0.0 ? 1 : -1;
                 }
             }
         };

@@ -1,5 +1,6 @@
 // ts_bvh_layout.h -- the layout of the triangle index that the build of mesh_bvh.hip writes (include/ts_bvh.h), as the queries read it: the
-// closest-point query of mesh_bvh.hip and the ray query of mesh_ray.hip (include/ts_ray.h, a library of its own).  Every translation unit
+// closest-point query of mesh_bvh.hip, the ray query of mesh_ray.hip (include/ts_ray.h, a library of its own) and the crossing counts of
+// mesh_inside.hip (include/ts_inside.h, another).  Every translation unit
 // that includes it gets its own internal copy.
 //
 // Leaves of LEAF consecutive Morton-sorted faces with their nine fp32 coordinates gathered (slot id -1: ineligible or padding, never

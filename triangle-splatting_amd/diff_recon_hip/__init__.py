@@ -86,6 +86,11 @@
                           render_textured, bake_texture, evaluate_textured and save_glb_textured_mesh (a GLB with TEXCOORD_0 and the atlas as
                           an embedded PNG, exact under NEAREST) -- colour resolution that does not depend on the face count; no counterpart
                           in the reference; loaded on first use
+    mesh_inside.py        ray_crossings (ALL hits of every ray on a MeshBVH, counted in half crossings so that a ray through a shared edge
+                          counts one crossing; equal to brute force bit for bit), winding_number / contains_points / signed_distance (the
+                          first clean ray of three fixed directions decides), mesh_to_sdf (the signed distance on a grid: the way back from
+                          a mesh to a volume), remesh (its level set: one uniform closed surface, or an offset surface) and mesh_volume_iou
+                          -- the counterpart of trimesh's contains / signed_distance; loaded on first use
     metrics.py           psnr, ssim (= 1 - SSIMLoss), evaluate_mesh and evaluate_vertex_colors: PSNR / SSIM of a mesh's opaque render (one
                           colour per face, or per vertex) against each view's gt_image
                           (reference: src/diff_recon/trainers/trainer_utils.py:331-336, VanillaTS_trainer.py:156-190)
@@ -93,7 +98,7 @@
                           replayed with one launch -- no counterpart in the reference, whose forward reads num_rendered back every step
 
 Native code: libts2d.so (include/ts_loss.h, include/ts_model.h, include/ts_optim.h, include/ts2d.h, include/ts_mesh.h, include/ts_weld.h) and, for
-mesh_distance.py, libts_geom.so beside this file (include/ts_geom.h), for mesh_surface.py, libts_bvh.so (include/ts_bvh.h), for mesh_ray.py, libts_ray.so (include/ts_ray.h), for volume.py, libts_volume.so (include/ts_volume.h), for color_volume.py, libts_color.so (include/ts_color.h), for mesh_simplify.py, libts_simplify.so (include/ts_simplify.h), for mesh_smooth.py, libts_smooth.so (include/ts_smooth.h), for mesh_holes.py, libts_holes.so (include/ts_holes.h), for mesh_manifold.py, libts_manifold.so (include/ts_manifold.h), for mesh_orient.py, libts_orient.so (include/ts_orient.h), for mesh_texture.py, libts_atlas.so (include/ts_atlas.h).  No CPU / eager fallback anywhere.
+mesh_distance.py, libts_geom.so beside this file (include/ts_geom.h), for mesh_surface.py, libts_bvh.so (include/ts_bvh.h), for mesh_ray.py, libts_ray.so (include/ts_ray.h), for volume.py, libts_volume.so (include/ts_volume.h), for color_volume.py, libts_color.so (include/ts_color.h), for mesh_simplify.py, libts_simplify.so (include/ts_simplify.h), for mesh_smooth.py, libts_smooth.so (include/ts_smooth.h), for mesh_holes.py, libts_holes.so (include/ts_holes.h), for mesh_manifold.py, libts_manifold.so (include/ts_manifold.h), for mesh_orient.py, libts_orient.so (include/ts_orient.h), for mesh_texture.py, libts_atlas.so (include/ts_atlas.h), for mesh_inside.py, libts_inside.so (include/ts_inside.h).  No CPU / eager fallback anywhere.
 """
 from .losses import L1, SSIMLoss, ssimLoss, PhotometricLoss, photometric_loss, DepthNormalLoss, DoGLoss, SmoothnessLoss, dogLoss, smoothnessLoss, downsample_bilinear, downsample_bilinear_many  # noqa: F401
 from .triangle_renderer import TriangleRenderer  # noqa: F401
@@ -127,6 +132,8 @@ _MANIFOLD_NAMES = ("VertexFans", "ManifoldMesh", "vertex_fans", "split_nonmanifo
 _ORIENT_NAMES = ("OrientedMesh", "orient_faces", "orient_fused")
 _TEXTURE_NAMES = ("AtlasLayout", "BakedTexture", "TextureAtlas", "atlas_layout", "face_uvs", "texel_index", "render_textured", "bake_texture",
                   "evaluate_textured", "encode_png", "save_glb_textured_mesh")
+_INSIDE_NAMES = ("INSIDE_DIRECTIONS", "RayCrossings", "ray_crossings", "winding_number", "contains_points", "signed_distance", "mesh_to_sdf",
+                 "remesh", "mesh_volume_iou")
 
 
 def __getattr__(name):
@@ -167,4 +174,8 @@ def __getattr__(name):
         import importlib
         module = importlib.import_module(".mesh_texture", __name__)
         return module if name == "mesh_texture" else getattr(module, name)
+    if name in _INSIDE_NAMES or name == "mesh_inside":  # mesh_inside.py and libts_inside.so likewise
+        import importlib
+        module = importlib.import_module(".mesh_inside", __name__)
+        return module if name == "mesh_inside" else getattr(module, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,7 +1,8 @@
 """Exact point-to-SURFACE distance on the device: a bounding-volume hierarchy over the triangles of a mesh, and the scores built on it.
 
     MeshBVH(vertices, faces, keep=None)                 the index of a mesh, built once; .closest(queries) -> (face, dist2, point);
-                                                        .ray_cast(origins, directions) -> the first hit of every ray (mesh_ray.py)
+                                                        .ray_cast(origins, directions) -> the first hit of every ray (mesh_ray.py);
+                                                        .ray_crossings(origins, directions) -> all hits, counted (mesh_inside.py)
     point_to_mesh_distance(points, (vertices, faces))   the same in one call
     mesh_surface_distance((va, fa), (vb, fb), samples, seed=0, thresholds=(), visible_from=None)
                                                         accuracy / completeness / Chamfer / Hausdorff / precision / recall / F-score, sample to surface;
@@ -121,6 +122,12 @@ class MeshBVH:
         loaded here, on the first call: `closest` needs neither."""
         from .mesh_ray import ray_cast
         return ray_cast(self, origins, directions, **kwargs)
+
+    def ray_crossings(self, origins: torch.Tensor, directions: torch.Tensor, **kwargs):
+        """mesh_inside.ray_crossings(self, origins, directions, ...): all hits of every ray, counted in half crossings.  The module and its
+        library (libts_inside.so) are loaded here, on the first call."""
+        from .mesh_inside import ray_crossings
+        return ray_crossings(self, origins, directions, **kwargs)
 
 
 def point_to_mesh_distance(points: torch.Tensor, mesh) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:

@@ -429,3 +429,25 @@ def bind_atlas(lib):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     return lib
+
+
+# include/ts_inside.h: the whole C ABI of diff_recon_hip/libts_inside.so, the thirteenth library (diff_recon_hip/mesh_inside.py loads and binds it)
+INSIDE_SIGNATURES = {
+    "tsi_last_error": (C.c_char_p, []),
+    "tsi_crossings_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "tsi_crossings": (C.c_int, [C.c_int32, _vp, _vp, C.c_int32, _vp, C.c_double, C.c_double, C.c_int32, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp,
+                                C.c_size_t, _vp]),
+    "tsi_signed_distance": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+}
+
+
+def bind_inside(lib):
+    """Sets restype and argtypes of every function of include/ts_inside.h on `lib` (a ctypes.CDLL of libts_inside.so); a library that
+    lacks one is refused."""
+    missing = [name for name in INSIDE_SIGNATURES if not hasattr(lib, name)]
+    if missing:
+        raise ImportError(f"{getattr(lib, '_name', lib)} does not export {', '.join(missing)}: rebuild it with `python triangle-splatting_amd/build.py`")
+    for name, (restype, argtypes) in INSIDE_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return lib

@@ -46,7 +46,9 @@ A "ground truth" is rendered from a hidden set of triangles from several cameras
                                                         side (crossing counts on the mesh's own index decide the sign) and extract it again
                                                         (diff_recon_hip.remesh); print its faces, pieces, boundary edges, Euler characteristic, the
                                                         undecided samples and the surface distance to the mesh it came from.  The sign means
-                                                        something on a closed mesh: an open sheet shadows what lies behind it
+                                                        something on a closed mesh: an open sheet shadows what lies behind it.  With
+                                                        --remesh-method winding the generalised winding number decides the sign instead
+                                                        (diff_recon_hip.remesh_winding), which holds for a mesh with holes too
     python examples/train_synthetic.py --eval-mesh --extract-mesh RES --fill-holes N
                                                         close the boundary loops of the fused mesh of at most N edges with centroid fans before anything
                                                         smooths or simplifies it (diff_recon_hip.fill_fused); prints the loops, the filled ones, the open
@@ -245,7 +247,7 @@ def train(rasterizer="2D", iters=200, triangles=20000, width=256, height=192, se
 
 def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, height=192, seed=0, views=2, refine=False, weld=None, geometry=None, surface=None,
                 visible=False, extract=None, extract_color=False, simplify=None, min_piece=0, smooth=None, fill=None, split=False, orient=None, texture=None,
-                out=None, remesh=None):
+                out=None, remesh=None, remesh_method="rays"):
     """PSNR / SSIM of the model's opaque mesh -- mesh_from_triangles: one colour per face from the DC coefficients, back faces as reversed
     twins, the soup saveGLB writes -- against the hidden targets of train() called with the same arguments (diff_recon_hip.evaluate_mesh).
     refine: the result also holds "refined", the same scores (plus "kept" and "triangles") of the mesh after a census over these views
@@ -289,7 +291,9 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
     remesh = RES (with extract): the finished fused mesh, behind every step above, is turned into a signed distance volume of RES samples along
     its longest side and extracted again (diff_recon_hip.remesh: crossing counts on the mesh's own index decide the sign), and "fused" also holds
     "remeshed": the grid's "dims", "voxel_size", "samples", "undecided" and "inside", the "topology" of the new mesh and "to_fused" =
-    mesh_surface_distance to the mesh it came from (None for a fused mesh without faces)."""
+    mesh_surface_distance to the mesh it came from (None for a fused mesh without faces).  remesh_method = "winding": the generalised
+    winding number decides the sign instead (diff_recon_hip.remesh_winding), which also holds for a fused mesh with holes; "remeshed" then
+    also holds "method"."""
     _, _, cams, gts, kw, _, _ = _setup(rasterizer, iters, triangles, width, height, seed, views, 0.0, False, False)
     for cam, gt in zip(cams, gts):
         cam.gt_image = gt
@@ -398,8 +402,12 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
         if remesh is not None:
             done = small if simplified else fused  # the finished mesh: behind every step asked for above
             if done.faces.shape[0]:
-                again = D.remesh((done.vertices, done.faces), int(remesh))
+                if remesh_method not in ("rays", "winding"):
+                    raise ValueError(f"remesh_method must be 'rays' or 'winding', not {remesh_method!r}")
+                again = (D.remesh_winding if remesh_method == "winding" else D.remesh)((done.vertices, done.faces), int(remesh))
                 grid = {k: again.stats[k] for k in ("dims", "voxel_size", "samples", "undecided", "inside")}
+                if remesh_method == "winding":
+                    grid["method"] = "winding"
                 res["fused"]["remeshed"] = dict(grid, resolution=int(remesh), topology=topology_of(again),
                                                 to_fused=D.mesh_surface_distance((again.vertices, again.faces), (done.vertices, done.faces), samples, seed=seed)
                                                 if again.faces.shape[0] else None)
@@ -415,7 +423,8 @@ def remeshed_report(r):
     t, g = r["topology"], r["to_fused"]
     dist = (f"accuracy {g['accuracy']:.4g}, completeness {g['completeness']:.4g}, Chamfer {g['chamfer']:.4g}, Hausdorff {g['hausdorff']:.4g}"
             if g is not None else "no surface was extracted")
-    return [f"remeshed mesh, resolution {r['resolution']} ({r['dims'][0]} x {r['dims'][1]} x {r['dims'][2]} samples, {r['inside']} inside, "
+    how = ", signed by the generalised winding number" if r.get("method") == "winding" else ""
+    return [f"remeshed mesh{how}, resolution {r['resolution']} ({r['dims'][0]} x {r['dims'][1]} x {r['dims'][2]} samples, {r['inside']} inside, "
             f"{r['undecided']} undecided): {t['faces']} faces, {t['pieces']} pieces, {t['boundary']} boundary edges, Euler characteristic {t['euler']}",
             f"remeshed mesh against the mesh it came from: {dist}"]
 
@@ -704,6 +713,9 @@ if __name__ == "__main__":
     ap.add_argument("--remesh", type=int, default=None, metavar="RES", help="with --extract-mesh: turn the finished fused mesh into a signed distance volume of RES samples along "
                                                                             "its longest side and extract it again (diff_recon_hip.remesh); print faces, pieces, boundary "
                                                                             "edges, Euler characteristic, undecided samples and the surface distance to the mesh it came from")
+    ap.add_argument("--remesh-method", choices=("rays", "winding"), default="rays", help="with --remesh: what decides the sign of the distance volume: crossing counts of rays "
+                                                                                          "(closed meshes) or the generalised winding number (diff_recon_hip.remesh_winding: "
+                                                                                          "open meshes too)")
     ap.add_argument("--out", default=None, metavar="PATH", help="with --bake-texture: write the textured fused mesh as a GLB (diff_recon_hip.save_glb_textured_mesh)")
     a = ap.parse_args()
     if a.remesh is not None and a.extract_mesh is None:
@@ -769,7 +781,7 @@ if __name__ == "__main__":
         res = mesh_scores(m, a.rasterizer, a.iters, a.triangles, views=a.views, refine=a.refine_mesh, weld=a.weld_mesh, geometry=a.eval_geometry,
                           surface=a.eval_surface, visible=a.eval_visible, extract=a.extract_mesh, extract_color=a.extract_color, simplify=a.simplify_mesh,
                           min_piece=a.min_piece, smooth=a.smooth_mesh, fill=a.fill_holes, split=a.split_nonmanifold, orient=a.orient_faces,
-                          texture=a.bake_texture, out=a.out, remesh=a.remesh)
+                          texture=a.bake_texture, out=a.out, remesh=a.remesh, remesh_method=a.remesh_method)
         for v, (p_, s_) in enumerate(zip(res["psnr"], res["ssim"])):
             print(f"  opaque mesh, view {v}: PSNR {p_:.2f} dB  SSIM {s_:.4f}")
         print(f"opaque mesh of {m._vertex.shape[0]} triangles: mean PSNR {res['mean_psnr']:.2f} dB, mean SSIM {res['mean_ssim']:.4f} over {len(res['psnr'])} views")

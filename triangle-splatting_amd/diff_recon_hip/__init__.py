@@ -91,6 +91,12 @@
                           first clean ray of three fixed directions decides), mesh_to_sdf (the signed distance on a grid: the way back from
                           a mesh to a volume), remesh (its level set: one uniform closed surface, or an offset surface) and mesh_volume_iou
                           -- the counterpart of trimesh's contains / signed_distance; loaded on first use
+    mesh_winding.py       generalized_winding_number (the signed solid angle of the mesh seen from a point, over 4 pi, summed on the MeshBVH
+                          with one far-field term per node; int64 sums of quantised terms, so a pure function of the input),
+                          contains_points_winding / signed_distance_winding / mesh_to_sdf_winding / remesh_winding /
+                          mesh_volume_iou_winding: the inside test of OPEN meshes, where a ray count is wrong behind every sheet; also
+                          method="winding" of mesh_inside's contains_points, signed_distance and mesh_volume_iou -- the counterpart of
+                          libigl's fast winding number; loaded on first use
     metrics.py           psnr, ssim (= 1 - SSIMLoss), evaluate_mesh and evaluate_vertex_colors: PSNR / SSIM of a mesh's opaque render (one
                           colour per face, or per vertex) against each view's gt_image
                           (reference: src/diff_recon/trainers/trainer_utils.py:331-336, VanillaTS_trainer.py:156-190)
@@ -98,7 +104,7 @@
                           replayed with one launch -- no counterpart in the reference, whose forward reads num_rendered back every step
 
 Native code: libts2d.so (include/ts_loss.h, include/ts_model.h, include/ts_optim.h, include/ts2d.h, include/ts_mesh.h, include/ts_weld.h) and, for
-mesh_distance.py, libts_geom.so beside this file (include/ts_geom.h), for mesh_surface.py, libts_bvh.so (include/ts_bvh.h), for mesh_ray.py, libts_ray.so (include/ts_ray.h), for volume.py, libts_volume.so (include/ts_volume.h), for color_volume.py, libts_color.so (include/ts_color.h), for mesh_simplify.py, libts_simplify.so (include/ts_simplify.h), for mesh_smooth.py, libts_smooth.so (include/ts_smooth.h), for mesh_holes.py, libts_holes.so (include/ts_holes.h), for mesh_manifold.py, libts_manifold.so (include/ts_manifold.h), for mesh_orient.py, libts_orient.so (include/ts_orient.h), for mesh_texture.py, libts_atlas.so (include/ts_atlas.h), for mesh_inside.py, libts_inside.so (include/ts_inside.h).  No CPU / eager fallback anywhere.
+mesh_distance.py, libts_geom.so beside this file (include/ts_geom.h), for mesh_surface.py, libts_bvh.so (include/ts_bvh.h), for mesh_ray.py, libts_ray.so (include/ts_ray.h), for volume.py, libts_volume.so (include/ts_volume.h), for color_volume.py, libts_color.so (include/ts_color.h), for mesh_simplify.py, libts_simplify.so (include/ts_simplify.h), for mesh_smooth.py, libts_smooth.so (include/ts_smooth.h), for mesh_holes.py, libts_holes.so (include/ts_holes.h), for mesh_manifold.py, libts_manifold.so (include/ts_manifold.h), for mesh_orient.py, libts_orient.so (include/ts_orient.h), for mesh_texture.py, libts_atlas.so (include/ts_atlas.h), for mesh_inside.py, libts_inside.so (include/ts_inside.h), for mesh_winding.py, libts_winding.so (include/ts_winding.h).  No CPU / eager fallback anywhere.
 """
 from .losses import L1, SSIMLoss, ssimLoss, PhotometricLoss, photometric_loss, DepthNormalLoss, DoGLoss, SmoothnessLoss, dogLoss, smoothnessLoss, downsample_bilinear, downsample_bilinear_many  # noqa: F401
 from .triangle_renderer import TriangleRenderer  # noqa: F401
@@ -134,6 +140,8 @@ _TEXTURE_NAMES = ("AtlasLayout", "BakedTexture", "TextureAtlas", "atlas_layout",
                   "evaluate_textured", "encode_png", "save_glb_textured_mesh")
 _INSIDE_NAMES = ("INSIDE_DIRECTIONS", "RayCrossings", "ray_crossings", "winding_number", "contains_points", "signed_distance", "mesh_to_sdf",
                  "remesh", "mesh_volume_iou")
+_WINDING_NAMES = ("UNITS_PER_TURN", "winding_moments", "leaf_faces", "generalized_winding_number", "contains_points_winding",
+                  "signed_distance_winding", "mesh_to_sdf_winding", "remesh_winding", "mesh_volume_iou_winding", "threshold_units")
 
 
 def __getattr__(name):
@@ -178,4 +186,8 @@ def __getattr__(name):
         import importlib
         module = importlib.import_module(".mesh_inside", __name__)
         return module if name == "mesh_inside" else getattr(module, name)
+    if name in _WINDING_NAMES or name == "mesh_winding":  # mesh_winding.py and libts_winding.so likewise
+        import importlib
+        module = importlib.import_module(".mesh_winding", __name__)
+        return module if name == "mesh_winding" else getattr(module, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -22,6 +22,10 @@ brute force over all faces (include/ts_inside.h):
 Every function below casts along INSIDE_DIRECTIONS in order, t in [0, inf), and takes for each point the FIRST direction whose ray is
 clean; a point without one is undecided.  Pass meshes whose faces wind consistently (mesh_orient.orient_faces) when the sign matters.
 
+All of this needs a CLOSED mesh: behind an open sheet a ray crosses the surface once.  contains_points, signed_distance and mesh_volume_iou
+take method="winding" (and beta) and then decide by the generalised winding number of mesh_winding.py, which degrades smoothly at a hole;
+mesh_to_sdf and remesh have mesh_winding.mesh_to_sdf_winding and remesh_winding beside them.  The default, method="rays", is this module.
+
 Native code: libts_inside.so beside this file (include/ts_inside.h, csrc/mesh_inside.hip), a thirteenth library because the export lists of
 the other twelve are closed; bound with ctypes.  No CPU / eager fallback: a missing library is an ImportError."""
 from __future__ import annotations
@@ -70,6 +74,19 @@ class RayCrossings(NamedTuple):
 
 def _as_bvh(bvh) -> MeshBVH:
     return bvh if isinstance(bvh, MeshBVH) else MeshBVH(*bvh)
+
+
+METHODS = ("rays", "winding")
+
+
+def _method(method: str, rule: str = "nonzero") -> bool:
+    """True for method = "winding" (mesh_winding.py: the generalised winding number decides every finite point and nothing is retried),
+    False for "rays" (the crossing counts of this module).  The winding number knows one rule, w >= 1/2."""
+    if method not in METHODS:
+        raise ValueError(f"method must be one of {list(METHODS)}, not {method!r}")
+    if method == "winding" and rule != "nonzero":
+        raise ValueError(f'method="winding" decides by w >= 1/2 and takes no rule, got rule={rule!r}')
+    return method == "winding"
 
 
 def _rule(rule: str) -> int:
@@ -134,19 +151,28 @@ def winding_number(points: torch.Tensor, mesh) -> Tuple[torch.Tensor, torch.Tens
     return w, decided
 
 
-def contains_points(points: torch.Tensor, mesh, rule: str = "nonzero") -> Tuple[torch.Tensor, torch.Tensor]:
-    """(inside (Q,) bool, decided (Q,) bool) by the winding number of every point and `rule`; an undecided point is not inside."""
+def contains_points(points: torch.Tensor, mesh, rule: str = "nonzero", method: str = "rays", beta: float = 2.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(inside (Q,) bool, decided (Q,) bool) by the winding number of every point and `rule`; an undecided point is not inside.
+    method = "winding": mesh_winding.contains_points_winding(points, mesh, beta) instead, for meshes that are not closed."""
     code = _rule(rule)
+    if _method(method, rule):
+        from .mesh_winding import contains_points_winding
+        return contains_points_winding(points, mesh, beta)
     w, decided = winding_number(points, mesh)
     inside = (w != 0) if code == 0 else ((w & 1) != 0) if code == 1 else (w > 0)
     return inside & decided, decided
 
 
-def signed_distance(points: torch.Tensor, mesh, rule: str = "nonzero") -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+def signed_distance(points: torch.Tensor, mesh, rule: str = "nonzero", method: str = "rays",
+                    beta: float = 2.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """(sdf (Q,) float32, face (Q,) int32, decided (Q,) bool): the distance to the nearest face (MeshBVH.closest), negative inside by
     `rule`.  A point ON the mesh (distance 0) is +0 and decided; a point without a clean ray keeps the unsigned distance and is not
-    decided; a point without a finite distance (a non-finite coordinate, no eligible face) is NaN and not decided."""
+    decided; a point without a finite distance (a non-finite coordinate, no eligible face) is NaN and not decided.
+    method = "winding": mesh_winding.signed_distance_winding(points, mesh, beta) instead, for meshes that are not closed."""
     code = _rule(rule)
+    if _method(method, rule):
+        from .mesh_winding import signed_distance_winding
+        return signed_distance_winding(points, mesh, beta)
     bvh = _as_bvh(mesh)
     p = _points_arg(points, "points")
     device = _device_of("signed_distance", p, bvh.bvh)
@@ -248,11 +274,16 @@ def remesh(mesh, resolution: int, offset: float = 0.0, pad_voxels: int = 2):
     return out
 
 
-def mesh_volume_iou(mesh_a, mesh_b, resolution: int, origin=None, voxel_size: Optional[float] = None, dims=None) -> Dict[str, object]:
+def mesh_volume_iou(mesh_a, mesh_b, resolution: int, origin=None, voxel_size: Optional[float] = None, dims=None, method: str = "rays",
+                    beta: float = 2.0) -> Dict[str, object]:
     """The volumetric intersection over union of two meshes: contains_points of both at the samples of ONE grid, `resolution` samples
     along the longest side of the box around both (one voxel of room), or the grid given by origin, voxel_size and dims.  Integer counts
     `inside_a`, `inside_b`, `inside_both`, `inside_either` over the samples that both meshes decide; `undecided` counts the others, which are
-    left out; `iou` = inside_both / inside_either (NaN when nothing is inside), `samples`, `origin`, `voxel_size`, `dims`."""
+    left out; `iou` = inside_both / inside_either (NaN when nothing is inside), `samples`, `origin`, `voxel_size`, `dims`.
+    method = "winding": mesh_winding.mesh_volume_iou_winding on the same grid instead, for meshes that are not closed."""
+    if _method(method):
+        from .mesh_winding import mesh_volume_iou_winding
+        return mesh_volume_iou_winding(mesh_a, mesh_b, resolution, origin, voxel_size, dims, beta)
     a, b = _as_bvh(mesh_a), _as_bvh(mesh_b)
     if origin is None:
         origin, voxel_size, dims = _bounds(torch.cat([_mesh_arrays(a)[0], _mesh_arrays(b)[0].to(a.device)]), resolution, 1)

@@ -2,7 +2,8 @@
 
     MeshBVH(vertices, faces, keep=None)                 the index of a mesh, built once; .closest(queries) -> (face, dist2, point);
                                                         .ray_cast(origins, directions) -> the first hit of every ray (mesh_ray.py);
-                                                        .ray_crossings(origins, directions) -> all hits, counted (mesh_inside.py)
+                                                        .ray_crossings(origins, directions) -> all hits, counted (mesh_inside.py);
+                                                        .winding_number(points) -> the generalised winding number (mesh_winding.py)
     point_to_mesh_distance(points, (vertices, faces))   the same in one call
     mesh_surface_distance((va, fa), (vb, fb), samples, seed=0, thresholds=(), visible_from=None)
                                                         accuracy / completeness / Chamfer / Hausdorff / precision / recall / F-score, sample to surface;
@@ -128,6 +129,13 @@ class MeshBVH:
         library (libts_inside.so) are loaded here, on the first call."""
         from .mesh_inside import ray_crossings
         return ray_crossings(self, origins, directions, **kwargs)
+
+    def winding_number(self, points: torch.Tensor, **kwargs):
+        """mesh_winding.generalized_winding_number(points, self, ...): the generalised winding number of the mesh at every point, open
+        meshes included.  The module and its library (libts_winding.so) are loaded here, on the first call; the node moments are built
+        then and kept on this object."""
+        from .mesh_winding import generalized_winding_number
+        return generalized_winding_number(points, self, **kwargs)
 
 
 def point_to_mesh_distance(points: torch.Tensor, mesh) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:

@@ -451,3 +451,27 @@ def bind_inside(lib):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     return lib
+
+
+# include/ts_winding.h: the whole C ABI of diff_recon_hip/libts_winding.so, the fourteenth library (diff_recon_hip/mesh_winding.py loads and binds it)
+WINDING_SIGNATURES = {
+    "tsn_last_error": (C.c_char_p, []),
+    "tsn_moments_bytes": (C.c_size_t, [C.c_int32]),
+    "tsn_leaf_faces_bytes": (C.c_size_t, [C.c_int32]),
+    "tsn_moments": (C.c_int, [C.c_int32, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
+    "tsn_winding_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "tsn_winding": (C.c_int, [C.c_int32, _vp, C.c_double, C.c_int32, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "tsn_sign_distance": (C.c_int, [C.c_int32, _vp, _vp, C.c_int64, _vp, _vp, _vp]),
+}
+
+
+def bind_winding(lib):
+    """Sets restype and argtypes of every function of include/ts_winding.h on `lib` (a ctypes.CDLL of libts_winding.so); a library that
+    lacks one is refused."""
+    missing = [name for name in WINDING_SIGNATURES if not hasattr(lib, name)]
+    if missing:
+        raise ImportError(f"{getattr(lib, '_name', lib)} does not export {', '.join(missing)}: rebuild it with `python triangle-splatting_amd/build.py`")
+    for name, (restype, argtypes) in WINDING_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return lib

@@ -167,7 +167,7 @@ WINDING_LIB = os.path.join(HERE, "diff_recon_hip", "libts_winding.so")
 BIN_DIR = os.path.join(os.path.dirname(HERE), "tools", "bin")
 LAB_LIB = os.path.join(BIN_DIR, "libts2d_lab.so")
 LAB_SRC = os.path.join(os.path.dirname(HERE), "tools", "lab")  # lab_hooks.hip: the test hooks, outside the product's csrc/; it includes csrc's headers (-I)
-HEADERS = ["ts2d_common.h", "ts2d_radix.h", "ts2d_api.h", "ts_knn_front.h", "ts_weld_launch.h", "ts_geom_launch.h", "ts_bvh_launch.h", "ts_bvh_layout.h", "ts_ray_launch.h", "ts_volume_launch.h", "ts_color_launch.h", "ts_simplify_launch.h", "ts_smooth_launch.h", "ts_holes_launch.h", "ts_manifold_launch.h", "ts_orient_launch.h", "ts_atlas_launch.h", "ts_inside_launch.h", "ts_winding_launch.h", "ts_ray_tests.h", "ts_mesh_bary.h", "ts_union_find.h", "ts_mesh_common.h", "ts_mesh_scan.h", "ts_mesh_runs.h", "ts_mesh_edges.h", "ts2d_lab.h", "ts2d_math.h", "ts2d_wave.h", "ts2d_group.h", "ts2d_support.h", "ts2d_sh.h", "ts2d_stage.h", "ts2d_preprocess_launch.h", "ts2d_imgops.h", "ts2d_select.h", "ts2d_tri.h", os.path.join("..", "..", "include", "ts2d.h"),
+HEADERS = ["ts2d_common.h", "ts2d_radix.h", "ts2d_api.h", "ts_knn_front.h", "ts_weld_launch.h", "ts_geom_launch.h", "ts_bvh_launch.h", "ts_bvh_layout.h", "ts_bvh_walk.h", "ts_ray_launch.h", "ts_volume_launch.h", "ts_color_launch.h", "ts_simplify_launch.h", "ts_smooth_launch.h", "ts_holes_launch.h", "ts_manifold_launch.h", "ts_orient_launch.h", "ts_atlas_launch.h", "ts_inside_launch.h", "ts_winding_launch.h", "ts_ray_tests.h", "ts_mesh_bary.h", "ts_union_find.h", "ts_mesh_common.h", "ts_mesh_scan.h", "ts_mesh_runs.h", "ts_mesh_edges.h", "ts2d_lab.h", "ts2d_math.h", "ts2d_wave.h", "ts2d_group.h", "ts2d_support.h", "ts2d_sh.h", "ts2d_stage.h", "ts2d_preprocess_launch.h", "ts2d_imgops.h", "ts2d_select.h", "ts2d_tri.h", os.path.join("..", "..", "include", "ts2d.h"),
            os.path.join("..", "..", "include", "ts_loss.h"),
            os.path.join("..", "..", "include", "ts_knn.h"),
            os.path.join("..", "..", "include", "ts_model.h"),

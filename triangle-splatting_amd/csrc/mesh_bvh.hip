@@ -11,22 +11,19 @@
 // offsets from `bvh` alone, every word of it is written by the build, and a query takes every index it follows from F, never from memory.
 //
 // Query.  The queries go through the same front half (own bounding box, Morton sort, float4 gather with the original index; a non-finite
-// query is stored as NaNs).  One wave owns 64 consecutive sorted queries, one per lane; every lane keeps (best D', face, point) of its own.
-// Control flow is wave-uniform: the wave pops a node from its stack in LDS, every lane evaluates L(q, box), and the node is entered when
-// __ballot says that some lane has L <= best -- pruning on strict `>` only, which is what makes the result the brute-force argmin, ties
-// included (see the header).  An inner node pushes its non-empty children, the one farthest from the wave's mean query first, so that the
-// nearest is popped first.  At a leaf every lane evaluates D' of the leaf's faces for its own query; the faces' words are wave-uniform loads.
-// `best` is seeded from the leaf that holds the Morton code of the wave's mean query (binary search among the sorted face codes).
-//
-// Stack bound.  STACK = 1 + (FAN - 1) (MAX_LEVELS - 1) = 71 entries, whatever the data: the argument stands with the layout, in ts_bvh_layout.h.
-#include "ts_bvh_layout.h" // LEAF, FAN, MAX_LEVELS, STACK, Leaf, BvhView, bvh_view: shared with the ray query (mesh_ray.hip)
+// query is stored as NaNs).  The walk is csrc/ts_bvh_walk.h, nearest child first.  What is this kernel's own: every lane keeps (best D',
+// face, point); a node is entered when some lane has L(q, box) <= best -- pruning on strict `>` only, which is what makes the result the
+// brute-force argmin, ties included (see the header).  The children are ordered by L of the wave's mean query.  At a leaf every lane
+// evaluates D' of the leaf's faces for its own query.  `best` is seeded from the leaf that holds the Morton code of the wave's mean query
+// (binary search among the sorted face codes); the walk passes that leaf by.
+#include "ts_bvh_layout.h" // LEAF, FAN, Leaf, BvhView, bvh_view: shared with the other queries on the index
 #include "ts_bvh_launch.h"
+#include "ts_bvh_walk.h"
 
 #include <algorithm>
 
 namespace
 {
-constexpr int WAVES = TPB / 64;
 constexpr uint32_t CODE_INELIGIBLE = 0x40000000u; // above every 30-bit Morton code
 
 struct BuildCarve
@@ -56,12 +53,6 @@ BuildCarve build_carve(void *ws, int F)
     c.sort_temp = take(sort_bytes);
     c.bytes = (size_t)(p - (char *)ws);
     return c;
-}
-
-size_t query_carve_bytes(int n)
-{
-    const size_t b = knn_carve(nullptr, n).bytes;
-    return n > TS_RS_SMALL_BELOW ? std::max(b, knn_carve(nullptr, TS_RS_SMALL_BELOW).bytes) : b;
 }
 
 // ---- build ---------------------------------------------------------------------------------------------------------------------------
@@ -244,39 +235,22 @@ __global__ void __launch_bounds__(TPB) closest_kernel(int Q, int F, int nleaves,
                                                        int32_t *__restrict__ face, double *__restrict__ dist2, float *__restrict__ point,
                                                        unsigned long long *leaf_visits)
 {
-    __shared__ uint32_t lvl_off[MAX_LEVELS], lvl_cnt[MAX_LEVELS];
-    __shared__ uint32_t stack[WAVES][STACK];
-    const int tid = threadIdx.x, wave = tid >> 6;
-    if (tid < MAX_LEVELS) // the level table follows from the leaf count alone (bvh_view)
-    {
-        uint32_t off = 0, cnt = (uint32_t)nleaves;
-        for (int l = 0; l < tid; l++)
-        {
-            off += cnt;
-            cnt = (cnt + FAN - 1) >> FAN_SHIFT;
-        }
-        lvl_off[tid] = off; lvl_cnt[tid] = cnt;
-    }
-    __syncthreads(); // the only one: from here on every wave is on its own
-
+    __shared__ WalkShared ws;
+    walk_levels(ws, nleaves);
     const float nanf_ = __uint_as_float(0x7FC00000u);
     const double inf = __longlong_as_double(0x7FF0000000000000ll), nan = __longlong_as_double(0x7FF8000000000000ll);
-    const size_t i = (size_t)blockIdx.x * TPB + tid;
-    const bool inside = i < (size_t)Q;
-    const float4 p = inside ? qsp[i] : make_float4(nanf_, nanf_, nanf_, 0.0f);
-    const uint32_t pid = __float_as_uint(p.w);
-    const bool live = inside && p.x == p.x; // a non-finite query was stored as NaNs
-    const double qx = (double)p.x, qy = (double)p.y, qz = (double)p.z;
+    const WalkQuery q = walk_query(Q, qsp);
+    const double qx = (double)q.p.x, qy = (double)q.p.y, qz = (double)q.p.z;
     double best = inf;
     uint32_t bestid = 0xFFFFFFFFu;
     float bpx = nanf_, bpy = nanf_, bpz = nanf_;
     unsigned visits = 0;
 
-    const unsigned long long alive = __ballot(live);
+    const unsigned long long alive = __ballot(q.live);
     if (alive != 0ull) // wave-uniform
     {
         // the wave's mean query: orders the children and picks the seed leaf; any value would do for the result
-        double mx = live ? qx : 0.0, my = live ? qy : 0.0, mz = live ? qz : 0.0;
+        double mx = q.live ? qx : 0.0, my = q.live ? qy : 0.0, mz = q.live ? qz : 0.0;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1)
         {
@@ -287,17 +261,10 @@ __global__ void __launch_bounds__(TPB) closest_kernel(int Q, int F, int nleaves,
 
         auto visit_leaf = [&](int leaf) {
             visits++;
-            const Leaf &lf = leaves[leaf];
-#pragma unroll 1
-            for (int j = 0; j < LEAF; j++)
-            {
-                const int32_t id = lf.id[j];
-                if (id < 0) continue; // wave-uniform: an ineligible or padding slot
-                const float ax = lf.v[j][0], ay = lf.v[j][1], az = lf.v[j][2], bx = lf.v[j][3], by = lf.v[j][4], bz = lf.v[j][5], cx = lf.v[j][6],
-                            cy = lf.v[j][7], cz = lf.v[j][8];
+            for_each_face(leaves[leaf], [&](int32_t id, float ax, float ay, float az, float bx, float by, float bz, float cx, float cy, float cz) {
                 const double lt = box_bound(qx, qy, qz, fminf(fminf(ax, bx), cx), fminf(fminf(ay, by), cy), fminf(fminf(az, bz), cz),
                                             fmaxf(fmaxf(ax, bx), cx), fmaxf(fmaxf(ay, by), cy), fmaxf(fmaxf(az, bz), cz));
-                if (!live || lt > best) continue; // D' >= L(q, AABB(T)) > best: neither a gain nor a tie
+                if (!q.live || lt > best) return; // D' >= L(q, AABB(T)) > best: neither a gain nor a tie
                 const Closest c = point_triangle(qx, qy, qz, ax, ay, az, bx, by, bz, cx, cy, cz);
                 const double d = c.d > lt ? c.d : lt;
                 if (d < best || (d == best && (uint32_t)id < bestid))
@@ -305,7 +272,7 @@ __global__ void __launch_bounds__(TPB) closest_kernel(int Q, int F, int nleaves,
                     best = d; bestid = (uint32_t)id;
                     bpx = (float)c.px; bpy = (float)c.py; bpz = (float)c.pz;
                 }
-            }
+            });
         };
 
         // seed: the leaf at the lower bound of the mean query's code among the sorted face codes
@@ -321,65 +288,28 @@ __global__ void __launch_bounds__(TPB) closest_kernel(int Q, int F, int nleaves,
         const int seed = __builtin_amdgcn_readfirstlane(min(lo, F - 1) / LEAF); // F >= 1 here: seed < nleaves
         visit_leaf(seed);
 
-        uint32_t *st = stack[wave];
-        int sp = 0;
-        st[sp++] = (uint32_t)(nlevels - 1) << 28; // the root: node 0 of the top level
-        while (sp > 0)
-        {
-            const uint32_t e = __builtin_amdgcn_readfirstlane(st[--sp]);
-            const int level = (int)(e >> 28);
-            const uint32_t k = e & 0x0FFFFFFFu; // k < lvl_cnt[level] by construction: the root is (top, 0), children are bounded below
-            const Box b = nodes[__builtin_amdgcn_readfirstlane(lvl_off[level] + k)];
-            if (b.mnx > b.mxx) continue; // no eligible face below
-            const double lq = box_bound(qx, qy, qz, b.mnx, b.mny, b.mnz, b.mxx, b.mxy, b.mxz);
-            if (__ballot(live && !(lq > best)) == 0ull) continue; // strict: an equal bound may hide a smaller face index
-            if (level == 0)
-            {
-                if ((int)k != seed) visit_leaf((int)k);
-                continue;
-            }
-            const uint32_t c0 = k * FAN, below = __builtin_amdgcn_readfirstlane(lvl_cnt[level - 1]);
-            const uint32_t base = __builtin_amdgcn_readfirstlane(lvl_off[level - 1]) + c0;
-            const int nchild = (int)min(below - c0, (uint32_t)FAN); // c0 < below: k < ceil(below / FAN)
-            float key[FAN];
-            unsigned want = 0;
-#pragma unroll
-            for (int c = 0; c < FAN; c++)
-            {
-                key[c] = 0.0f;
-                if (c < nchild)
-                {
-                    const Box cb = nodes[base + c];
-                    if (!(cb.mnx > cb.mxx))
-                    {
-                        key[c] = (float)box_bound(mx, my, mz, cb.mnx, cb.mny, cb.mnz, cb.mxx, cb.mxy, cb.mxz);
-                        want |= 1u << c;
-                    }
-                }
-            }
-            while (want) // at most FAN pushes: the farthest first (ties: the highest index first), so that pops come nearest first
-            {
-                int far = -1;
-                float far_key = 0.0f;
-#pragma unroll
-                for (int c = 0; c < FAN; c++)
-                    if (((want >> c) & 1u) && (far < 0 || key[c] >= far_key)) { far = c; far_key = key[c]; }
-                want &= ~(1u << far);
-                if (sp < STACK) st[sp++] = ((uint32_t)(level - 1) << 28) | (c0 + (uint32_t)far); // sp < STACK always (file header); the test costs nothing
-            }
-        }
+        bvh_walk<true>(
+            ws, nlevels, nodes,
+            [&](int, uint32_t, uint32_t, const Box &b) {
+                const double lq = box_bound(qx, qy, qz, b.mnx, b.mny, b.mnz, b.mxx, b.mxy, b.mxz);
+                return __ballot(q.live && !(lq > best)) != 0ull; // strict: an equal bound may hide a smaller face index
+            },
+            [&](int leaf) {
+                if (leaf != seed) visit_leaf(leaf);
+            },
+            [&](const Box &cb) { return (float)box_bound(mx, my, mz, cb.mnx, cb.mny, cb.mnz, cb.mxx, cb.mxy, cb.mxz); });
     }
 
-    if (inside)
+    if (q.inside)
     {
-        face[pid] = bestid == 0xFFFFFFFFu ? -1 : (int32_t)bestid;
-        dist2[pid] = live ? best : nan;
+        face[q.pid] = bestid == 0xFFFFFFFFu ? -1 : (int32_t)bestid;
+        dist2[q.pid] = q.live ? best : nan;
         if (point)
         {
-            point[3 * (size_t)pid] = bpx; point[3 * (size_t)pid + 1] = bpy; point[3 * (size_t)pid + 2] = bpz;
+            point[3 * (size_t)q.pid] = bpx; point[3 * (size_t)q.pid + 1] = bpy; point[3 * (size_t)q.pid + 2] = bpz;
         }
     }
-    if (leaf_visits && (tid & 63) == 0 && visits) atomicAdd(leaf_visits, (unsigned long long)visits);
+    if (leaf_visits && (threadIdx.x & 63) == 0 && visits) atomicAdd(leaf_visits, (unsigned long long)visits);
 }
 
 // F == 0: nobody has a face
@@ -428,17 +358,16 @@ hipError_t ts_bvh_closest(int Q, const float *queries, int F, const void *bvh, i
                           unsigned long long *leaf_visits, void *ws, hipStream_t s)
 {
     if (Q <= 0) return hipSuccess;
-    const unsigned qblocks = (unsigned)(((size_t)Q + TPB - 1) / TPB);
     if (F <= 0)
     {
-        hipLaunchKernelGGL(no_faces_kernel, dim3(qblocks), dim3(256), 0, s, Q, queries, face, dist2, point);
+        hipLaunchKernelGGL(no_faces_kernel, dim3((unsigned)(((size_t)Q + 255) / 256)), dim3(256), 0, s, Q, queries, face, dist2, point);
         return hipGetLastError();
     }
     const BvhView b = bvh_view(const_cast<void *>(bvh), F);
     const KnnCarve cq = knn_carve((void *)ts_align_up((size_t)ws), Q);
     const hipError_t e = knn_prepare<true>(Q, queries, cq, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(closest_kernel, dim3(qblocks), dim3(TPB), 0, s, Q, F, b.nleaves, b.nlevels, cq.sp, b.bbox, b.codes, b.leaves, b.nodes, face, dist2,
+    hipLaunchKernelGGL(closest_kernel, dim3((unsigned)(((size_t)Q + TPB - 1) / TPB)), dim3(TPB), 0, s, Q, F, b.nleaves, b.nlevels, cq.sp, b.bbox, b.codes, b.leaves, b.nodes, face, dist2,
                        point, leaf_visits);
     return hipGetLastError();
 }

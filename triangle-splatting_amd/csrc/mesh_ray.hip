@@ -17,24 +17,18 @@
 // are wave-uniform loads; every lane tests the face's own box first (not crossed, or tn > best: skip), then the triangle.  `best` starts at
 // the ray's upper limit `hi` with no face: the acceptance t' <= hi and the pruning tn > best are the same comparison from the first node on.
 //
-// Stack: STACK entries per wave in LDS, whatever the data (ts_bvh_layout.h).
+// Stack: STACK entries per wave in LDS, whatever the data (the argument stands in ts_bvh_walk.h).
+//
+// The walk below is this kernel's own text, where the other three queries on the index use csrc/ts_bvh_walk.h: on the shared walk one of
+// the five measured ray sets (one direction repeated per ray) ran 2 - 3.5 % slower at equal leaf visits, whichever way the set-up was
+// worded (profiles/bvh_walk_ab.json).  A change to the fan-out, the stack or the node packing is made there and here.
 #include "ts_bvh_layout.h"
+#include "ts_bvh_walk.h" // WAVES, query_carve_bytes
 #include "ts_ray_launch.h"
 #include "ts_ray_tests.h"
 
-#include <algorithm>
-
 namespace
 {
-constexpr int WAVES = TPB / 64;
-
-size_t ray_carve_bytes(int n)
-{
-    // the radix sort's tables shrink where its chunk length grows (TS_RS_SMALL_BELOW): never less than just below that size
-    const size_t b = knn_carve(nullptr, n).bytes;
-    return n > TS_RS_SMALL_BELOW ? std::max(b, knn_carve(nullptr, TS_RS_SMALL_BELOW).bytes) : b;
-}
-
 __global__ void __launch_bounds__(TPB) cast_kernel(int Q, int nleaves, int nlevels, const float4 *__restrict__ osp, const float *__restrict__ directions,
                                                     const float *__restrict__ t_limit, double tmin, double tmax, int cull_back,
                                                     const Leaf *__restrict__ leaves, const Box *__restrict__ nodes, int32_t *__restrict__ face,
@@ -68,7 +62,7 @@ __global__ void __launch_bounds__(TPB) cast_kernel(int Q, int nleaves, int nleve
     if (live)
     {
         fdx = directions[3 * (size_t)pid]; fdy = directions[3 * (size_t)pid + 1]; fdz = directions[3 * (size_t)pid + 2];
-        live = finite_f(fdx) && finite_f(fdy) && finite_f(fdz) && !(fdx == 0.0f && fdy == 0.0f && fdz == 0.0f);
+        live = ray_direction_valid(fdx, fdy, fdz);
         if (t_limit)
         {
             const float tl = t_limit[pid];
@@ -177,7 +171,7 @@ __global__ void __launch_bounds__(TPB) cast_kernel(int Q, int nleaves, int nleve
                 for (int c = 0; c < FAN; c++)
                     if (((want >> c) & 1u) && (far < 0 || key[c] >= far_key)) { far = c; far_key = key[c]; }
                 want &= ~(1u << far);
-                if (sp < STACK) st[sp++] = ((uint32_t)(level - 1) << 28) | (c0 + (uint32_t)far); // sp < STACK always (ts_bvh_layout.h); the test costs nothing
+                if (sp < STACK) st[sp++] = ((uint32_t)(level - 1) << 28) | (c0 + (uint32_t)far); // sp < STACK always (ts_bvh_walk.h); the test costs nothing
             }
         }
     }
@@ -204,9 +198,7 @@ __global__ void __launch_bounds__(256) no_faces_kernel(int Q, const float *__res
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= Q) return;
     const float dx = directions[3 * (size_t)i], dy = directions[3 * (size_t)i + 1], dz = directions[3 * (size_t)i + 2];
-    bool good = all_finite(origins[3 * (size_t)i], origins[3 * (size_t)i + 1], origins[3 * (size_t)i + 2]) && all_finite(dx, dy, dz) &&
-                !(dx == 0.0f && dy == 0.0f && dz == 0.0f);
-    if (t_limit && t_limit[i] != t_limit[i]) good = false;
+    const bool good = ray_valid(all_finite(origins[3 * (size_t)i], origins[3 * (size_t)i + 1], origins[3 * (size_t)i + 2]), dx, dy, dz, t_limit, i);
     const float nan = __uint_as_float(0x7FC00000u);
     face[i] = -1;
     t_out[i] = __longlong_as_double(good ? 0x7FF0000000000000ll : 0x7FF8000000000000ll);
@@ -220,23 +212,22 @@ __global__ void __launch_bounds__(256) no_faces_kernel(int Q, const float *__res
 
 size_t ts_ray_bvh_bytes(int F) { return bvh_view(nullptr, F).bytes; }
 
-size_t ts_ray_cast_workspace_bytes(int Q) { return ray_carve_bytes(Q) + TS_ALIGN; }
+size_t ts_ray_cast_workspace_bytes(int Q) { return query_carve_bytes(Q) + TS_ALIGN; }
 
 hipError_t ts_ray_cast(int Q, const float *origins, const float *directions, const float *t_limit, double tmin, double tmax, int cull_back, int F,
                        const void *bvh, int32_t *face, double *t, float *bary, int8_t *side, unsigned long long *leaf_visits, void *ws, hipStream_t s)
 {
     if (Q <= 0) return hipSuccess;
-    const unsigned qblocks = (unsigned)(((size_t)Q + TPB - 1) / TPB);
     if (F <= 0)
     {
-        hipLaunchKernelGGL(no_faces_kernel, dim3(qblocks), dim3(256), 0, s, Q, origins, directions, t_limit, face, t, bary, side);
+        hipLaunchKernelGGL(no_faces_kernel, dim3((unsigned)(((size_t)Q + 255) / 256)), dim3(256), 0, s, Q, origins, directions, t_limit, face, t, bary, side);
         return hipGetLastError();
     }
     const BvhView b = bvh_view(const_cast<void *>(bvh), F);
     const KnnCarve cq = knn_carve((void *)ts_align_up((size_t)ws), Q);
     const hipError_t e = knn_prepare<true>(Q, origins, cq, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(cast_kernel, dim3(qblocks), dim3(TPB), 0, s, Q, b.nleaves, b.nlevels, cq.sp, directions, t_limit, tmin, tmax, cull_back, b.leaves,
+    hipLaunchKernelGGL(cast_kernel, dim3((unsigned)(((size_t)Q + TPB - 1) / TPB)), dim3(TPB), 0, s, Q, b.nleaves, b.nlevels, cq.sp, directions, t_limit, tmin, tmax, cull_back, b.leaves,
                        b.nodes, face, t, bary, side, leaf_visits);
     return hipGetLastError();
 }

@@ -9,23 +9,19 @@
 // index order), then one launch over all nodes turns M into p = M / S and writes R2 from the node's box.  No atomics, no workspace.
 //
 // Query.  The points go through the front half of the box searches (ts_knn_front.h): the bounding box of the finite points, a Morton sort,
-// a float4 gather that carries the original index; a non-finite point is stored as NaNs.  One wave owns 64 consecutive sorted points, one
-// per lane; every lane keeps an int64 sum and two int32 counters.  Control flow is wave-uniform: the wave pops a node from its stack in LDS,
-// its box and its moment record are wave-uniform loads, every lane that has not accepted an ancestor tests d2 > beta2 * R2 and either takes
-// the node's term or asks for more; the node is entered when __ballot says that some lane asks.  A lane that accepted node (L, K) sits out
-// of every popped (l, k) with l < L and k >> 3 (L - l) == K: the walk is depth first, so those are popped before anything else and one
-// register pair is enough.  At a leaf the faces' words are wave-uniform loads and every asking lane evaluates the face term.
-//
-// Stack: STACK entries per wave in LDS, whatever the data (ts_bvh_layout.h).
+// a float4 gather that carries the original index; a non-finite point is stored as NaNs.  The walk is csrc/ts_bvh_walk.h, children in index
+// order.  What is this kernel's own: every lane keeps an int64 sum and two int32 counters; at a popped node, whose moment record is a
+// wave-uniform load, every lane that has not accepted an ancestor tests d2 > beta2 * R2 and either takes the node's term or asks for more;
+// the node is entered when some lane asks.  A lane that accepted node (L, K) sits out of every popped (l, k) with l < L and
+// k >> 3 (L - l) == K: the walk is depth first, so those are popped before anything else and one register pair is enough.  At a leaf every
+// asking lane evaluates the face term.
 #include "ts_bvh_layout.h"
+#include "ts_bvh_walk.h"
 #include "ts_ray_tests.h" // max2, finite_f
 #include "ts_winding_launch.h"
 
-#include <algorithm>
-
 namespace
 {
-constexpr int WAVES = TPB / 64;
 constexpr double PI = 3.141592653589793;        // 0x400921FB54442D18
 constexpr double UNITS_HALF = 137438953472.0;   // 2^37
 constexpr double UNITS_TURN = 274877906944.0;   // 2^38
@@ -35,13 +31,6 @@ struct Moment
 {
     double nx, ny, nz, px, py, pz, r2, s; // px..pz hold M until finish_moments_kernel has run
 };
-
-size_t winding_carve_bytes(int n)
-{
-    // the radix sort's tables shrink where its chunk length grows (TS_RS_SMALL_BELOW): never less than just below that size
-    const size_t b = knn_carve(nullptr, n).bytes;
-    return n > TS_RS_SMALL_BELOW ? std::max(b, knn_carve(nullptr, TS_RS_SMALL_BELOW).bytes) : b;
-}
 
 __device__ __forceinline__ double dot3(double ax, double ay, double az, double bx, double by, double bz) { return (ax * bx + ay * by) + az * bz; }
 
@@ -128,92 +117,54 @@ __global__ void __launch_bounds__(TPB) winding_kernel(int Q, int nleaves, int nl
                                                        const Leaf *__restrict__ leaves, const Box *__restrict__ nodes,
                                                        const Moment *__restrict__ mom, long long *__restrict__ wq, int32_t *__restrict__ terms)
 {
-    __shared__ uint32_t lvl_off[MAX_LEVELS], lvl_cnt[MAX_LEVELS];
-    __shared__ uint32_t stack[WAVES][STACK];
-    const int tid = threadIdx.x, wave = tid >> 6;
-    if (tid < MAX_LEVELS) // the level table follows from the leaf count alone (bvh_view)
-    {
-        uint32_t off = 0, cnt = (uint32_t)nleaves;
-        for (int l = 0; l < tid; l++)
-        {
-            off += cnt;
-            cnt = (cnt + FAN - 1) >> FAN_SHIFT;
-        }
-        lvl_off[tid] = off; lvl_cnt[tid] = cnt;
-    }
-    __syncthreads(); // the only one: from here on every wave is on its own
-
-    const float nanf_ = __uint_as_float(0x7FC00000u);
-    const size_t i = (size_t)blockIdx.x * TPB + tid;
-    const bool inside = i < (size_t)Q;
-    const float4 p = inside ? qsp[i] : make_float4(nanf_, nanf_, nanf_, 0.0f);
-    const uint32_t pid = __float_as_uint(p.w); // < Q for a lane inside: the sorted index of the front half
-    const bool live = inside && p.x == p.x;    // a non-finite point was stored as NaNs
+    __shared__ WalkShared ws;
+    walk_levels(ws, nleaves);
+    const WalkQuery q = walk_query(Q, qsp);
     // a lane that is not live walks along with a finite stand-in and never takes a term
-    const double qx = live ? (double)p.x : 0.0, qy = live ? (double)p.y : 0.0, qz = live ? (double)p.z : 0.0;
+    const double qx = q.live ? (double)q.p.x : 0.0, qy = q.live ? (double)q.p.y : 0.0, qz = q.live ? (double)q.p.z : 0.0;
 
     long long sum = 0;
     int nfaces = 0, nnodes = 0;
     int acc_level = 0;   // the node this lane accepted last: no popped node lies below level 0, so (0, 0) stands for none
     uint32_t acc_k = 0;
+    bool ask = false;    // of the node at hand: this lane wants its children, or its faces
 
-    if (__ballot(live) != 0ull) // wave-uniform
-    {
-        uint32_t *st = stack[wave];
-        int sp = 0;
-        st[sp++] = (uint32_t)(nlevels - 1) << 28; // the root: node 0 of the top level
-        while (sp > 0)
-        {
-            const uint32_t e = __builtin_amdgcn_readfirstlane(st[--sp]);
-            const int level = (int)(e >> 28);
-            const uint32_t k = e & 0x0FFFFFFFu; // k < lvl_cnt[level] by construction: the root is (top, 0), children are bounded below
-            const uint32_t at = __builtin_amdgcn_readfirstlane(lvl_off[level] + k);
-            const Box b = nodes[at];
-            if (b.mnx > b.mxx) continue; // no eligible face below
-            const Moment m = mom[at];
-            bool ask = live && !(level < acc_level && (k >> (FAN_SHIFT * (acc_level - level))) == acc_k);
-            if (ask && m.s > 0.0)
-            {
-                const double rx = m.px - qx, ry = m.py - qy, rz = m.pz - qz;
-                const double d2 = dot3(rx, ry, rz, rx, ry, rz);
-                if (d2 > beta2 * m.r2)
+    if (__ballot(q.live) != 0ull) // wave-uniform
+        bvh_walk<false>(
+            ws, nlevels, nodes,
+            [&](int level, uint32_t k, uint32_t at, const Box &) {
+                const Moment m = mom[at];
+                ask = q.live && !(level < acc_level && (k >> (FAN_SHIFT * (acc_level - level))) == acc_k);
+                if (ask && m.s > 0.0)
                 {
-                    sum += llrint(((dot3(m.nx, m.ny, m.nz, rx, ry, rz) / (d2 * sqrt(d2))) / (4.0 * PI)) * UNITS_TURN);
-                    nnodes++;
-                    acc_level = level; acc_k = k;
-                    ask = false;
+                    const double rx = m.px - qx, ry = m.py - qy, rz = m.pz - qz;
+                    const double d2 = dot3(rx, ry, rz, rx, ry, rz);
+                    if (d2 > beta2 * m.r2)
+                    {
+                        sum += llrint(((dot3(m.nx, m.ny, m.nz, rx, ry, rz) / (d2 * sqrt(d2))) / (4.0 * PI)) * UNITS_TURN);
+                        nnodes++;
+                        acc_level = level; acc_k = k;
+                        ask = false;
+                    }
                 }
-            }
-            if (__ballot(ask) == 0ull) continue;
-            if (level == 0)
-            {
-                const Leaf &lf = leaves[k];
-#pragma unroll 1
-                for (int j = 0; j < LEAF; j++)
-                {
-                    if (lf.id[j] < 0) continue; // wave-uniform: an ineligible or padding slot
-                    const float ax = lf.v[j][0], ay = lf.v[j][1], az = lf.v[j][2], bx = lf.v[j][3], by = lf.v[j][4], bz = lf.v[j][5],
-                                cx = lf.v[j][6], cy = lf.v[j][7], cz = lf.v[j][8];
-                    if (!ask) continue;
+                return __ballot(ask) != 0ull;
+            },
+            [&](int leaf) {
+                for_each_face(leaves[leaf], [&](int32_t, float ax, float ay, float az, float bx, float by, float bz, float cx, float cy, float cz) {
+                    if (!ask) return;
                     sum += face_term(qx, qy, qz, ax, ay, az, bx, by, bz, cx, cy, cz);
                     nfaces++;
-                }
-                continue;
-            }
-            const uint32_t c0 = k * FAN, below = __builtin_amdgcn_readfirstlane(lvl_cnt[level - 1]);
-            const int nchild = (int)min(below - c0, (uint32_t)FAN); // c0 < below: k < ceil(below / FAN)
-            for (int c = nchild - 1; c >= 0; c--) // the last first: pops come in index order, the order of the leaves in memory
-                if (sp < STACK) st[sp++] = ((uint32_t)(level - 1) << 28) | (c0 + (uint32_t)c); // sp < STACK always (ts_bvh_layout.h); the test costs nothing
-        }
-    }
+                });
+            },
+            NoChildKey());
 
-    if (inside)
+    if (q.inside)
     {
-        wq[pid] = live ? sum : BAD_QUERY;
+        wq[q.pid] = q.live ? sum : BAD_QUERY;
         if (terms)
         {
-            terms[2 * (size_t)pid] = live ? nfaces : -1;
-            terms[2 * (size_t)pid + 1] = live ? nnodes : -1;
+            terms[2 * (size_t)q.pid] = q.live ? nfaces : -1;
+            terms[2 * (size_t)q.pid + 1] = q.live ? nnodes : -1;
         }
     }
 }
@@ -270,7 +221,7 @@ size_t ts_winding_moments_bytes(int F)
 
 size_t ts_winding_leaf_faces_bytes(int F) { return (size_t)bvh_view(nullptr, F).nleaves * LEAF * sizeof(int32_t); }
 
-size_t ts_winding_workspace_bytes(int Q) { return winding_carve_bytes(Q) + TS_ALIGN; }
+size_t ts_winding_workspace_bytes(int Q) { return query_carve_bytes(Q) + TS_ALIGN; }
 
 hipError_t ts_winding_moments(int F, const void *bvh, double *moments, int32_t *leaf_faces, hipStream_t s)
 {

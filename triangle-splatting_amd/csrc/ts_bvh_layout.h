@@ -1,6 +1,7 @@
-// ts_bvh_layout.h -- the layout of the triangle index that the build of mesh_bvh.hip writes (include/ts_bvh.h), as the queries read it: the
-// closest-point query of mesh_bvh.hip, the ray query of mesh_ray.hip (include/ts_ray.h, a library of its own) and the crossing counts of
-// mesh_inside.hip (include/ts_inside.h, another).  Every translation unit
+// ts_bvh_layout.h -- the layout of the triangle index that the build of mesh_bvh.hip writes (include/ts_bvh.h), as its readers see it: the
+// closest-point query of mesh_bvh.hip, the ray query of mesh_ray.hip (include/ts_ray.h), the crossing counts of mesh_inside.hip
+// (include/ts_inside.h), the winding number of mesh_winding.hip (include/ts_winding.h), each a library of its own, and the moments pass of
+// mesh_winding.hip, which writes one record per node beside it.  Three of the queries walk it with csrc/ts_bvh_walk.h, cast_kernel with a walk of its own.  Every translation unit
 // that includes it gets its own internal copy.
 //
 // Leaves of LEAF consecutive Morton-sorted faces with their nine fp32 coordinates gathered (slot id -1: ineligible or padding, never
@@ -8,9 +9,8 @@
 // leaves' own boxes.  A node without an eligible face has the empty box (+inf, -inf).  The layout is made of offsets from `bvh` alone and
 // follows from F; a query takes every index it follows from F, never from memory.
 //
-// Stack bound.  F <= 2^31 - 1 gives at most 2^28 leaves, so at most MAX_LEVELS = 11 levels (2^28, 2^25, ..., 2, 1 nodes).  A pop removes one
-// entry and pushes at most FAN children of the level below; leaves push nothing.  By induction the stack holds at most 1 + (FAN - 1) entries
-// per inner level on the current path: STACK = 1 + (FAN - 1) (MAX_LEVELS - 1) = 71, whatever the data.
+// F <= 2^31 - 1 gives at most 2^28 leaves, so at most MAX_LEVELS = 11 levels (2^28, 2^25, ..., 2, 1 nodes).  STACK is what a depth-first
+// walk of that tree holds at most, whatever the data: the argument stands beside the push, in ts_bvh_walk.h.
 #pragma once
 #include "ts_knn_front.h"
 

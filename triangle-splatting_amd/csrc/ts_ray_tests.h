@@ -1,6 +1,7 @@
 // ts_ray_tests.h -- the two tests of a ray that include/ts_ray.h defines, as device functions: the padded slab interval of a box and the
 // watertight triangle test (Woop, Benthin and Wald), float64 on the fp32 coordinates.  Shared by mesh_ray.hip (the first hit) and
 // mesh_inside.hip (all hits, include/ts_inside.h): one text, so that a face is hit in the one unit exactly when it is hit in the other.
+// With them, for the same reason, the rule for which rays are cast at all (ray_direction_valid, ray_valid).
 // Every translation unit that includes it gets its own internal copy and must be built with -ffp-contract=off: every operation below rounds.
 #pragma once
 #include "ts2d_common.h"
@@ -73,6 +74,17 @@ __device__ __forceinline__ RayShear ray_shear(double ox, double oy, double oz, d
     r.Sx = sel3(kx, dx, dy, dz) / dkz; r.Sy = sel3(ky, dx, dy, dz) / dkz; r.Sz = 1.0 / dkz;
     r.okx = sel3(kx, ox, oy, oz); r.oky = sel3(ky, ox, oy, oz); r.okz = sel3(kz, ox, oy, oz);
     return r;
+}
+
+// the rays that are cast at all (include/ts_ray.h): a finite origin, a finite non-zero direction, a limit that is not NaN
+__device__ __forceinline__ bool ray_direction_valid(float dx, float dy, float dz)
+{
+    return finite_f(dx) && finite_f(dy) && finite_f(dz) && !(dx == 0.0f && dy == 0.0f && dz == 0.0f);
+}
+
+__device__ __forceinline__ bool ray_valid(bool origin_finite, float dx, float dy, float dz, const float *__restrict__ t_limit, size_t i)
+{
+    return origin_finite && ray_direction_valid(dx, dy, dz) && !(t_limit && t_limit[i] != t_limit[i]);
 }
 
 // U, V, W, det of the face (a, b, c) and the three sheared depths' sources A[kz] - o[kz], ...: what face_t needs besides

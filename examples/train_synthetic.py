@@ -49,6 +49,10 @@ A "ground truth" is rendered from a hidden set of triangles from several cameras
                                                         something on a closed mesh: an open sheet shadows what lies behind it.  With
                                                         --remesh-method winding the generalised winding number decides the sign instead
                                                         (diff_recon_hip.remesh_winding), which holds for a mesh with holes too
+    python examples/train_synthetic.py --eval-mesh [--weld-mesh EPS] [--extract-mesh RES [...] [--remesh RES2]] --check-intersections
+                                                        print, for every indexed mesh produced (welded, the finished fused one, remeshed), how many
+                                                        face pairs cross, lie in one plane or are duplicates and how many faces take part in a
+                                                        crossing (diff_recon_hip.self_intersection_report: the overlap query of the mesh's own index)
     python examples/train_synthetic.py --eval-mesh --extract-mesh RES --fill-holes N
                                                         close the boundary loops of the fused mesh of at most N edges with centroid fans before anything
                                                         smooths or simplifies it (diff_recon_hip.fill_fused); prints the loops, the filled ones, the open
@@ -247,7 +251,7 @@ def train(rasterizer="2D", iters=200, triangles=20000, width=256, height=192, se
 
 def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, height=192, seed=0, views=2, refine=False, weld=None, geometry=None, surface=None,
                 visible=False, extract=None, extract_color=False, simplify=None, min_piece=0, smooth=None, fill=None, split=False, orient=None, texture=None,
-                out=None, remesh=None, remesh_method="rays"):
+                out=None, remesh=None, remesh_method="rays", check_intersections=False):
     """PSNR / SSIM of the model's opaque mesh -- mesh_from_triangles: one colour per face from the DC coefficients, back faces as reversed
     twins, the soup saveGLB writes -- against the hidden targets of train() called with the same arguments (diff_recon_hip.evaluate_mesh).
     refine: the result also holds "refined", the same scores (plus "kept" and "triangles") of the mesh after a census over these views
@@ -293,7 +297,10 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
     "remeshed": the grid's "dims", "voxel_size", "samples", "undecided" and "inside", the "topology" of the new mesh and "to_fused" =
     mesh_surface_distance to the mesh it came from (None for a fused mesh without faces).  remesh_method = "winding": the generalised
     winding number decides the sign instead (diff_recon_hip.remesh_winding), which also holds for a fused mesh with holes; "remeshed" then
-    also holds "method"."""
+    also holds "method".
+    check_intersections: every indexed mesh above -- "welded", "fused" (the finished fused mesh, behind every step asked for) and
+    "fused"["remeshed"] -- also holds "intersections": diff_recon_hip.self_intersection_report of it, whether the surface passes through
+    itself.  No other entry changes."""
     _, _, cams, gts, kw, _, _ = _setup(rasterizer, iters, triangles, width, height, seed, views, 0.0, False, False)
     for cam, gt in zip(cams, gts):
         cam.gt_image = gt
@@ -315,6 +322,8 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
                              soup={k: soup[k] for k in ("mean_psnr", "mean_ssim")})
         if orient is not None:
             res["welded"]["oriented"] = D.orient_fused(w, orient).stats["orient"]
+        if check_intersections:
+            res["welded"]["intersections"] = D.self_intersection_report((w.vertices, w.faces))
     if geometry is not None or surface is not None:
         target = torch.from_numpy(np.ascontiguousarray(synthetic.scene(triangles, width, height, 2, seed=seed, edge_px=10.0)["vertex"])).to(m._vertex.device)
         edges = (target - target.roll(1, dims=1)).norm(dim=2)  # the hidden scene of _setup: every draw comes from the seeded generator
@@ -399,8 +408,10 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
                     small = D.fill_fused(small, int(fill))
                     res["fused"]["filled"] = dict(small.stats["fill"], max_loop_edges=int(fill), before=res["fused"]["manifold"]["topology"],
                                                   topology=topology_of(small))
+        done = small if simplified else fused  # the finished mesh: behind every step asked for above
+        if check_intersections:
+            res["fused"]["intersections"] = D.self_intersection_report((done.vertices, done.faces))
         if remesh is not None:
-            done = small if simplified else fused  # the finished mesh: behind every step asked for above
             if done.faces.shape[0]:
                 if remesh_method not in ("rays", "winding"):
                     raise ValueError(f"remesh_method must be 'rays' or 'winding', not {remesh_method!r}")
@@ -411,6 +422,8 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
                 res["fused"]["remeshed"] = dict(grid, resolution=int(remesh), topology=topology_of(again),
                                                 to_fused=D.mesh_surface_distance((again.vertices, again.faces), (done.vertices, done.faces), samples, seed=seed)
                                                 if again.faces.shape[0] else None)
+                if check_intersections:
+                    res["fused"]["remeshed"]["intersections"] = D.self_intersection_report((again.vertices, again.faces))
             else:
                 res["fused"]["remeshed"] = None
     return res
@@ -427,6 +440,12 @@ def remeshed_report(r):
     return [f"remeshed mesh{how}, resolution {r['resolution']} ({r['dims'][0]} x {r['dims'][1]} x {r['dims'][2]} samples, {r['inside']} inside, "
             f"{r['undecided']} undecided): {t['faces']} faces, {t['pieces']} pieces, {t['boundary']} boundary edges, Euler characteristic {t['euler']}",
             f"remeshed mesh against the mesh it came from: {dist}"]
+
+
+def intersections_report(r, which):
+    """The line --check-intersections prints for an "intersections" entry of mesh_scores(...): of "welded", of "fused", of "remeshed"."""
+    return [f"{which} mesh, self-intersections: {r['crossing_pairs']} crossing face pairs on {r['crossing_faces']} of {r['faces']} faces, "
+            f"{r['coplanar_pairs']} coplanar candidate pairs, {r['duplicate_pairs']} duplicate pairs, {r['degenerate_faces']} degenerate faces"]
 
 
 def smoothed_report(f):
@@ -716,8 +735,13 @@ if __name__ == "__main__":
     ap.add_argument("--remesh-method", choices=("rays", "winding"), default="rays", help="with --remesh: what decides the sign of the distance volume: crossing counts of rays "
                                                                                           "(closed meshes) or the generalised winding number (diff_recon_hip.remesh_winding: "
                                                                                           "open meshes too)")
+    ap.add_argument("--check-intersections", action="store_true", help="with --weld-mesh and / or --extract-mesh: print, for every indexed mesh produced (welded, fused, "
+                                                                       "remeshed), how many face pairs cross, lie in one plane or are duplicates "
+                                                                       "(diff_recon_hip.self_intersection_report)")
     ap.add_argument("--out", default=None, metavar="PATH", help="with --bake-texture: write the textured fused mesh as a GLB (diff_recon_hip.save_glb_textured_mesh)")
     a = ap.parse_args()
+    if a.check_intersections and a.extract_mesh is None and a.weld_mesh is None:
+        ap.error("--check-intersections checks the mesh of --weld-mesh or of --extract-mesh")
     if a.remesh is not None and a.extract_mesh is None:
         ap.error("--remesh remeshes the mesh of --extract-mesh")
     if a.remesh is not None and a.remesh < 8:
@@ -781,7 +805,8 @@ if __name__ == "__main__":
         res = mesh_scores(m, a.rasterizer, a.iters, a.triangles, views=a.views, refine=a.refine_mesh, weld=a.weld_mesh, geometry=a.eval_geometry,
                           surface=a.eval_surface, visible=a.eval_visible, extract=a.extract_mesh, extract_color=a.extract_color, simplify=a.simplify_mesh,
                           min_piece=a.min_piece, smooth=a.smooth_mesh, fill=a.fill_holes, split=a.split_nonmanifold, orient=a.orient_faces,
-                          texture=a.bake_texture, out=a.out, remesh=a.remesh, remesh_method=a.remesh_method)
+                          texture=a.bake_texture, out=a.out, remesh=a.remesh, remesh_method=a.remesh_method,
+                          check_intersections=a.check_intersections)
         for v, (p_, s_) in enumerate(zip(res["psnr"], res["ssim"])):
             print(f"  opaque mesh, view {v}: PSNR {p_:.2f} dB  SSIM {s_:.4f}")
         print(f"opaque mesh of {m._vertex.shape[0]} triangles: mean PSNR {res['mean_psnr']:.2f} dB, mean SSIM {res['mean_ssim']:.4f} over {len(res['psnr'])} views")
@@ -794,6 +819,9 @@ if __name__ == "__main__":
                 print(line)
             if "oriented" in res["welded"]:
                 for line in oriented_report(res["welded"]["oriented"], "welded"):
+                    print(line)
+            if a.check_intersections:
+                for line in intersections_report(res["welded"]["intersections"], "welded"):
                     print(line)
         if a.eval_geometry is not None:
             for line in geometry_report(res["geometry"]):
@@ -835,6 +863,12 @@ if __name__ == "__main__":
                 if "filled" in res["fused"]:
                     for line in filled_report(res["fused"]):
                         print(line)
+            if a.check_intersections:
+                for line in intersections_report(res["fused"]["intersections"], "fused"):
+                    print(line)
             if a.remesh is not None:
                 for line in remeshed_report(res["fused"]["remeshed"]):
                     print(line)
+                if a.check_intersections and res["fused"]["remeshed"] is not None:
+                    for line in intersections_report(res["fused"]["remeshed"]["intersections"], "remeshed"):
+                        print(line)

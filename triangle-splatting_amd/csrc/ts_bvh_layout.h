@@ -1,8 +1,9 @@
 // ts_bvh_layout.h -- the layout of the triangle index that the build of mesh_bvh.hip writes (include/ts_bvh.h), as its readers see it: the
 // closest-point query of mesh_bvh.hip, the ray query of mesh_ray.hip (include/ts_ray.h), the crossing counts of mesh_inside.hip
-// (include/ts_inside.h), the winding number of mesh_winding.hip (include/ts_winding.h), each a library of its own, and the moments pass of
-// mesh_winding.hip, which writes one record per node beside it.  Three of the queries walk it with csrc/ts_bvh_walk.h, cast_kernel with a walk of its own.  Every translation unit
-// that includes it gets its own internal copy.
+// (include/ts_inside.h), the winding number of mesh_winding.hip (include/ts_winding.h), the overlap query of mesh_overlap.hip
+// (include/ts_overlap.h), whose queries are the leaves of a second index or of the same one, each a library of its own, and the moments
+// pass of mesh_winding.hip, which writes one record per node beside it.  Four of the queries walk it with csrc/ts_bvh_walk.h, cast_kernel
+// with a walk of its own.  Every translation unit that includes it gets its own internal copy.
 //
 // Leaves of LEAF consecutive Morton-sorted faces with their nine fp32 coordinates gathered (slot id -1: ineligible or padding, never
 // evaluated); above them an IMPLICIT tree of fan-out FAN: node k of level l covers the leaves [k FAN^l, (k+1) FAN^l), level 0 being the

@@ -97,6 +97,11 @@
                           mesh_volume_iou_winding: the inside test of OPEN meshes, where a ray count is wrong behind every sheet; also
                           method="winding" of mesh_inside's contains_points, signed_distance and mesh_volume_iou -- the counterpart of
                           libigl's fast winding number; loaded on first use
+    mesh_overlap.py       MeshBVH.overlap / self_intersections / mesh_intersections (the overlap query of the MeshBVH: which face pairs of
+                          one mesh, or of two, cross, lie in one plane or are duplicates; equal to a float64 brute force bit for bit),
+                          intersecting_face_mask, drop_intersecting_faces and self_intersection_report: whether a surface passes through
+                          itself after clustering, hole filling or smoothing -- the counterpart of a collision query's face-pair list;
+                          loaded on first use
     metrics.py           psnr, ssim (= 1 - SSIMLoss), evaluate_mesh and evaluate_vertex_colors: PSNR / SSIM of a mesh's opaque render (one
                           colour per face, or per vertex) against each view's gt_image
                           (reference: src/diff_recon/trainers/trainer_utils.py:331-336, VanillaTS_trainer.py:156-190)
@@ -104,7 +109,7 @@
                           replayed with one launch -- no counterpart in the reference, whose forward reads num_rendered back every step
 
 Native code: libts2d.so (include/ts_loss.h, include/ts_model.h, include/ts_optim.h, include/ts2d.h, include/ts_mesh.h, include/ts_weld.h) and, for
-mesh_distance.py, libts_geom.so beside this file (include/ts_geom.h), for mesh_surface.py, libts_bvh.so (include/ts_bvh.h), for mesh_ray.py, libts_ray.so (include/ts_ray.h), for volume.py, libts_volume.so (include/ts_volume.h), for color_volume.py, libts_color.so (include/ts_color.h), for mesh_simplify.py, libts_simplify.so (include/ts_simplify.h), for mesh_smooth.py, libts_smooth.so (include/ts_smooth.h), for mesh_holes.py, libts_holes.so (include/ts_holes.h), for mesh_manifold.py, libts_manifold.so (include/ts_manifold.h), for mesh_orient.py, libts_orient.so (include/ts_orient.h), for mesh_texture.py, libts_atlas.so (include/ts_atlas.h), for mesh_inside.py, libts_inside.so (include/ts_inside.h), for mesh_winding.py, libts_winding.so (include/ts_winding.h).  No CPU / eager fallback anywhere.
+mesh_distance.py, libts_geom.so beside this file (include/ts_geom.h), for mesh_surface.py, libts_bvh.so (include/ts_bvh.h), for mesh_ray.py, libts_ray.so (include/ts_ray.h), for volume.py, libts_volume.so (include/ts_volume.h), for color_volume.py, libts_color.so (include/ts_color.h), for mesh_simplify.py, libts_simplify.so (include/ts_simplify.h), for mesh_smooth.py, libts_smooth.so (include/ts_smooth.h), for mesh_holes.py, libts_holes.so (include/ts_holes.h), for mesh_manifold.py, libts_manifold.so (include/ts_manifold.h), for mesh_orient.py, libts_orient.so (include/ts_orient.h), for mesh_texture.py, libts_atlas.so (include/ts_atlas.h), for mesh_inside.py, libts_inside.so (include/ts_inside.h), for mesh_winding.py, libts_winding.so (include/ts_winding.h), for mesh_overlap.py, libts_overlap.so (include/ts_overlap.h).  No CPU / eager fallback anywhere.
 """
 from .losses import L1, SSIMLoss, ssimLoss, PhotometricLoss, photometric_loss, DepthNormalLoss, DoGLoss, SmoothnessLoss, dogLoss, smoothnessLoss, downsample_bilinear, downsample_bilinear_many  # noqa: F401
 from .triangle_renderer import TriangleRenderer  # noqa: F401
@@ -142,6 +147,8 @@ _INSIDE_NAMES = ("INSIDE_DIRECTIONS", "RayCrossings", "ray_crossings", "winding_
                  "remesh", "mesh_volume_iou")
 _WINDING_NAMES = ("UNITS_PER_TURN", "winding_moments", "leaf_faces", "generalized_winding_number", "contains_points_winding",
                   "signed_distance_winding", "mesh_to_sdf_winding", "remesh_winding", "mesh_volume_iou_winding", "threshold_units")
+_OVERLAP_NAMES = ("KIND_CROSSING", "KIND_COPLANAR", "KIND_DUPLICATE", "MeshOverlap", "CleanedMesh", "self_intersections", "mesh_intersections",
+                  "intersecting_face_mask", "drop_intersecting_faces", "self_intersection_report")
 
 
 def __getattr__(name):
@@ -190,4 +197,8 @@ def __getattr__(name):
         import importlib
         module = importlib.import_module(".mesh_winding", __name__)
         return module if name == "mesh_winding" else getattr(module, name)
+    if name in _OVERLAP_NAMES or name == "mesh_overlap":  # mesh_overlap.py and libts_overlap.so likewise
+        import importlib
+        module = importlib.import_module(".mesh_overlap", __name__)
+        return module if name == "mesh_overlap" else getattr(module, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

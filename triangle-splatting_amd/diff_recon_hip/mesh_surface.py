@@ -3,7 +3,8 @@
     MeshBVH(vertices, faces, keep=None)                 the index of a mesh, built once; .closest(queries) -> (face, dist2, point);
                                                         .ray_cast(origins, directions) -> the first hit of every ray (mesh_ray.py);
                                                         .ray_crossings(origins, directions) -> all hits, counted (mesh_inside.py);
-                                                        .winding_number(points) -> the generalised winding number (mesh_winding.py)
+                                                        .winding_number(points) -> the generalised winding number (mesh_winding.py);
+                                                        .overlap(other=None) -> the face pairs that intersect (mesh_overlap.py)
     point_to_mesh_distance(points, (vertices, faces))   the same in one call
     mesh_surface_distance((va, fa), (vb, fb), samples, seed=0, thresholds=(), visible_from=None)
                                                         accuracy / completeness / Chamfer / Hausdorff / precision / recall / F-score, sample to surface;
@@ -136,6 +137,13 @@ class MeshBVH:
         then and kept on this object."""
         from .mesh_winding import generalized_winding_number
         return generalized_winding_number(points, self, **kwargs)
+
+    def overlap(self, other: Optional["MeshBVH"] = None, capacity: Optional[int] = None, leaf_visits: Optional[torch.Tensor] = None):
+        """mesh_overlap.overlap(self, other, capacity): the face pairs of this mesh that cross, lie in one plane or are duplicates of each
+        other (other = None), or the pairs (face of this mesh, face of `other`) that do.  The module and its library (libts_overlap.so) are
+        loaded here, on the first call."""
+        from .mesh_overlap import overlap
+        return overlap(self, other, capacity, leaf_visits)
 
 
 def point_to_mesh_distance(points: torch.Tensor, mesh) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:

@@ -475,3 +475,24 @@ def bind_winding(lib):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     return lib
+
+
+# include/ts_overlap.h: the whole C ABI of diff_recon_hip/libts_overlap.so, the fifteenth library (diff_recon_hip/mesh_overlap.py loads and binds it)
+OVERLAP_SIGNATURES = {
+    "tsx_last_error": (C.c_char_p, []),
+    "tsx_overlap": (C.c_int, [C.c_int32, _vp, C.c_size_t, _vp, C.c_int32, _vp, C.c_size_t, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp]),
+    "tsx_sort_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "tsx_sort_pairs": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_size_t, _vp]),
+}
+
+
+def bind_overlap(lib):
+    """Sets restype and argtypes of every function of include/ts_overlap.h on `lib` (a ctypes.CDLL of libts_overlap.so); a library that
+    lacks one is refused."""
+    missing = [name for name in OVERLAP_SIGNATURES if not hasattr(lib, name)]
+    if missing:
+        raise ImportError(f"{getattr(lib, '_name', lib)} does not export {', '.join(missing)}: rebuild it with `python triangle-splatting_amd/build.py`")
+    for name, (restype, argtypes) in OVERLAP_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return lib

@@ -24,6 +24,10 @@ A "ground truth" is rendered from a hidden set of triangles from several cameras
     python examples/train_synthetic.py --eval-mesh --weld-mesh EPS
                                                         then weld the front faces of that mesh (diff_recon_hip.weld_mesh), print V -> V', the faces
                                                         dropped, the topology and the largest cluster, and score the welded mesh beside the soup
+    python examples/train_synthetic.py --eval-mesh --weld-mesh EPS --split-edges L
+                                                        then split the welded mesh until no edge is longer than L (diff_recon_hip.split_fused), start
+                                                        the pieces from their parents' colours, bake the face colours again (bake_face_colors) and
+                                                        print the face count and PSNR / SSIM before and after
     python examples/train_synthetic.py --eval-mesh --eval-geometry N
                                                         then compare N surface samples of the model's front faces with N of the hidden target
                                                         triangles (diff_recon_hip.mesh_distance): accuracy, completeness, Chamfer, F-score
@@ -251,7 +255,7 @@ def train(rasterizer="2D", iters=200, triangles=20000, width=256, height=192, se
 
 def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, height=192, seed=0, views=2, refine=False, weld=None, geometry=None, surface=None,
                 visible=False, extract=None, extract_color=False, simplify=None, min_piece=0, smooth=None, fill=None, split=False, orient=None, texture=None,
-                out=None, remesh=None, remesh_method="rays", check_intersections=False):
+                out=None, remesh=None, remesh_method="rays", check_intersections=False, split_edges=None):
     """PSNR / SSIM of the model's opaque mesh -- mesh_from_triangles: one colour per face from the DC coefficients, back faces as reversed
     twins, the soup saveGLB writes -- against the hidden targets of train() called with the same arguments (diff_recon_hip.evaluate_mesh).
     refine: the result also holds "refined", the same scores (plus "kept" and "triangles") of the mesh after a census over these views
@@ -300,7 +304,11 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
     also holds "method".
     check_intersections: every indexed mesh above -- "welded", "fused" (the finished fused mesh, behind every step asked for) and
     "fused"["remeshed"] -- also holds "intersections": diff_recon_hip.self_intersection_report of it, whether the surface passes through
-    itself.  No other entry changes."""
+    itself.  No other entry changes.
+    split_edges = L (with weld): "welded" also holds "split": the welded mesh split until no edge exceeds L (diff_recon_hip.split_fused), its
+    face colours started from faces_color[face_parent] and baked again from these views (bake_face_colors) -- its scores, "faces", "vertices",
+    "rounds", "converged" and "before": the scores and "faces" of the welded mesh with ITS face colours baked the same way, so that the two
+    differ in resolution alone.  No other entry changes."""
     _, _, cams, gts, kw, _, _ = _setup(rasterizer, iters, triangles, width, height, seed, views, 0.0, False, False)
     for cam, gt in zip(cams, gts):
         cam.gt_image = gt
@@ -324,6 +332,13 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
             res["welded"]["oriented"] = D.orient_fused(w, orient).stats["orient"]
         if check_intersections:
             res["welded"]["intersections"] = D.self_intersection_report((w.vertices, w.faces))
+        if split_edges is not None:
+            score = lambda mesh: D.evaluate_mesh(cams, mesh.vertices, mesh.faces, D.bake_face_colors(cams, mesh.vertices, mesh.faces, mesh.faces_color),
+                                                 bg_color=kw["bg_color"])
+            fine = D.split_fused(w, split_edges)
+            res["welded"]["split"] = dict(score(fine), max_edge=float(split_edges), faces=int(fine.faces.shape[0]), vertices=int(fine.vertices.shape[0]),
+                                          rounds=fine.stats["split"]["rounds"], converged=fine.stats["split"]["converged"],
+                                          before=dict(score(w), faces=int(w.faces.shape[0])))
     if geometry is not None or surface is not None:
         target = torch.from_numpy(np.ascontiguousarray(synthetic.scene(triangles, width, height, 2, seed=seed, edge_px=10.0)["vertex"])).to(m._vertex.device)
         edges = (target - target.roll(1, dims=1)).norm(dim=2)  # the hidden scene of _setup: every draw comes from the seeded generator
@@ -539,6 +554,15 @@ def geometry_report(g, title="mesh geometry"):
             f"{title}, precision / recall: " + ", ".join(f"{p:.4f} / {r:.4f} at {k:g} edges" for k, p, r in zip((0.5, 1, 2), g["precision"], g["recall"]))] + hidden
 
 
+def split_edges_report(s):
+    """The lines --split-edges prints for mesh_scores(...)["welded"]["split"]."""
+    b = s["before"]
+    return [f"split mesh, no edge above {s['max_edge']:g}: faces {b['faces']} -> {s['faces']} in {s['rounds']} rounds"
+            + ("" if s["converged"] else " (not converged)") + f", {s['vertices']} vertices",
+            f"split mesh, face colours baked again: mean PSNR {b['mean_psnr']:.2f} -> {s['mean_psnr']:.2f} dB, mean SSIM {b['mean_ssim']:.4f} -> "
+            f"{s['mean_ssim']:.4f} (before: the welded mesh baked the same way; a fit to the training views)"]
+
+
 def weld_report(welded):
     """The lines --weld-mesh prints for mesh_scores(...)["welded"]."""
     s, t = welded["stats"], welded["topology"]
@@ -694,6 +718,9 @@ if __name__ == "__main__":
     ap.add_argument("--weld-mesh", type=float, default=None, metavar="EPS", help="with --eval-mesh: weld the front faces of the mesh scored last (diff_recon_hip.weld_mesh: "
                                                                                  "vertices within EPS of each other merge, transitively) and print V -> V', the faces dropped, "
                                                                                  "the topology, the largest cluster and the welded mesh's PSNR / SSIM beside the soup's")
+    ap.add_argument("--split-edges", type=float, default=None, metavar="L", help="with --weld-mesh: split the welded mesh until no edge is longer than L "
+                                                                                 "(diff_recon_hip.split_fused), bake the face colours again and print the face "
+                                                                                 "count and PSNR / SSIM before and after")
     ap.add_argument("--eval-geometry", type=int, default=None, metavar="N", help="with --eval-mesh: compare N surface samples of the model's front faces with N of the hidden "
                                                                                    "target triangles (diff_recon_hip.mesh_distance) and print accuracy, completeness, "
                                                                                    "Chamfer and the F-score at 0.5, 1 and 2 times the target's median edge length")
@@ -740,6 +767,10 @@ if __name__ == "__main__":
                                                                        "(diff_recon_hip.self_intersection_report)")
     ap.add_argument("--out", default=None, metavar="PATH", help="with --bake-texture: write the textured fused mesh as a GLB (diff_recon_hip.save_glb_textured_mesh)")
     a = ap.parse_args()
+    if a.split_edges is not None and a.weld_mesh is None:
+        ap.error("--split-edges splits the welded mesh of --weld-mesh")
+    if a.split_edges is not None and not (a.split_edges > 0 and math.isfinite(a.split_edges)):
+        ap.error("--split-edges needs a positive edge length")
     if a.check_intersections and a.extract_mesh is None and a.weld_mesh is None:
         ap.error("--check-intersections checks the mesh of --weld-mesh or of --extract-mesh")
     if a.remesh is not None and a.extract_mesh is None:
@@ -806,7 +837,7 @@ if __name__ == "__main__":
                           surface=a.eval_surface, visible=a.eval_visible, extract=a.extract_mesh, extract_color=a.extract_color, simplify=a.simplify_mesh,
                           min_piece=a.min_piece, smooth=a.smooth_mesh, fill=a.fill_holes, split=a.split_nonmanifold, orient=a.orient_faces,
                           texture=a.bake_texture, out=a.out, remesh=a.remesh, remesh_method=a.remesh_method,
-                          check_intersections=a.check_intersections)
+                          check_intersections=a.check_intersections, split_edges=a.split_edges)
         for v, (p_, s_) in enumerate(zip(res["psnr"], res["ssim"])):
             print(f"  opaque mesh, view {v}: PSNR {p_:.2f} dB  SSIM {s_:.4f}")
         print(f"opaque mesh of {m._vertex.shape[0]} triangles: mean PSNR {res['mean_psnr']:.2f} dB, mean SSIM {res['mean_ssim']:.4f} over {len(res['psnr'])} views")
@@ -822,6 +853,9 @@ if __name__ == "__main__":
                     print(line)
             if a.check_intersections:
                 for line in intersections_report(res["welded"]["intersections"], "welded"):
+                    print(line)
+            if a.split_edges is not None:
+                for line in split_edges_report(res["welded"]["split"]):
                     print(line)
         if a.eval_geometry is not None:
             for line in geometry_report(res["geometry"]):

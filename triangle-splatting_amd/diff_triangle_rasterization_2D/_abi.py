@@ -496,3 +496,25 @@ def bind_overlap(lib):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     return lib
+
+
+# include/ts_subdivide.h: the whole C ABI of diff_recon_hip/libts_subdivide.so, the sixteenth library (diff_recon_hip/mesh_subdivide.py loads and binds it)
+SUBDIVIDE_SIGNATURES = {
+    "tsd_last_error": (C.c_char_p, []),
+    "tsd_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "tsd_edges": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "tsd_split": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int32, C.c_float, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                            _vp, C.c_size_t, _vp]),
+}
+
+
+def bind_subdivide(lib):
+    """Sets restype and argtypes of every function of include/ts_subdivide.h on `lib` (a ctypes.CDLL of libts_subdivide.so); a library that
+    lacks one is refused."""
+    missing = [name for name in SUBDIVIDE_SIGNATURES if not hasattr(lib, name)]
+    if missing:
+        raise ImportError(f"{getattr(lib, '_name', lib)} does not export {', '.join(missing)}: rebuild it with `python triangle-splatting_amd/build.py`")
+    for name, (restype, argtypes) in SUBDIVIDE_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return lib

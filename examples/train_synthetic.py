@@ -28,6 +28,10 @@ A "ground truth" is rendered from a hidden set of triangles from several cameras
                                                         then split the welded mesh until no edge is longer than L (diff_recon_hip.split_fused), start
                                                         the pieces from their parents' colours, bake the face colours again (bake_face_colors) and
                                                         print the face count and PSNR / SSIM before and after
+    python examples/train_synthetic.py --eval-mesh --weld-mesh EPS --split-edges L --flip-edges
+                                                        then flip the edges of the split mesh toward the Delaunay condition
+                                                        (diff_recon_hip.flip_fused), bake the face colours again and print rounds, flips, the
+                                                        smallest and median triangle quality before and after, and PSNR / SSIM beside the unflipped
     python examples/train_synthetic.py --eval-mesh --eval-geometry N
                                                         then compare N surface samples of the model's front faces with N of the hidden target
                                                         triangles (diff_recon_hip.mesh_distance): accuracy, completeness, Chamfer, F-score
@@ -255,7 +259,7 @@ def train(rasterizer="2D", iters=200, triangles=20000, width=256, height=192, se
 
 def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, height=192, seed=0, views=2, refine=False, weld=None, geometry=None, surface=None,
                 visible=False, extract=None, extract_color=False, simplify=None, min_piece=0, smooth=None, fill=None, split=False, orient=None, texture=None,
-                out=None, remesh=None, remesh_method="rays", check_intersections=False, split_edges=None):
+                out=None, remesh=None, remesh_method="rays", check_intersections=False, split_edges=None, flip_edges=False):
     """PSNR / SSIM of the model's opaque mesh -- mesh_from_triangles: one colour per face from the DC coefficients, back faces as reversed
     twins, the soup saveGLB writes -- against the hidden targets of train() called with the same arguments (diff_recon_hip.evaluate_mesh).
     refine: the result also holds "refined", the same scores (plus "kept" and "triangles") of the mesh after a census over these views
@@ -308,7 +312,10 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
     split_edges = L (with weld): "welded" also holds "split": the welded mesh split until no edge exceeds L (diff_recon_hip.split_fused), its
     face colours started from faces_color[face_parent] and baked again from these views (bake_face_colors) -- its scores, "faces", "vertices",
     "rounds", "converged" and "before": the scores and "faces" of the welded mesh with ITS face colours baked the same way, so that the two
-    differ in resolution alone.  No other entry changes."""
+    differ in resolution alone.  No other entry changes.
+    flip_edges (with split_edges): "split" also holds "flipped": the split mesh after diff_recon_hip.flip_fused, baked the same way -- its
+    scores, "rounds", "flips", "guarded", "converged", "slots" (the face slots rewritten) and "quality" / "quality_before": the smallest and
+    the median diff_recon_hip.triangle_quality.  No other entry changes."""
     _, _, cams, gts, kw, _, _ = _setup(rasterizer, iters, triangles, width, height, seed, views, 0.0, False, False)
     for cam, gt in zip(cams, gts):
         cam.gt_image = gt
@@ -339,6 +346,15 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
             res["welded"]["split"] = dict(score(fine), max_edge=float(split_edges), faces=int(fine.faces.shape[0]), vertices=int(fine.vertices.shape[0]),
                                           rounds=fine.stats["split"]["rounds"], converged=fine.stats["split"]["converged"],
                                           before=dict(score(w), faces=int(w.faces.shape[0])))
+            if flip_edges:
+                def quality(mesh):  # [smallest, median]; a face that takes no part counts as degenerate
+                    q = D.triangle_quality(mesh.vertices, mesh.faces).nan_to_num(0.0)
+                    return [float(q.min()), float(q.median())]
+                flat = D.flip_fused(fine)
+                t = flat.stats["flip"]
+                res["welded"]["split"]["flipped"] = dict(score(flat), rounds=t["rounds"], flips=t["flipped"], guarded=t["guarded"],
+                                                         converged=t["converged"], slots=int(t["face_flipped"].sum()),
+                                                         quality=quality(flat), quality_before=quality(fine))
     if geometry is not None or surface is not None:
         target = torch.from_numpy(np.ascontiguousarray(synthetic.scene(triangles, width, height, 2, seed=seed, edge_px=10.0)["vertex"])).to(m._vertex.device)
         edges = (target - target.roll(1, dims=1)).norm(dim=2)  # the hidden scene of _setup: every draw comes from the seeded generator
@@ -563,6 +579,17 @@ def split_edges_report(s):
             f"{s['mean_ssim']:.4f} (before: the welded mesh baked the same way; a fit to the training views)"]
 
 
+def flip_edges_report(s):
+    """The lines --flip-edges prints for mesh_scores(...)["welded"]["split"]: s["flipped"] beside the unflipped split mesh."""
+    t = s["flipped"]
+    return [f"flipped mesh: {t['flips']} flips in {t['rounds']} rounds" + ("" if t["converged"] else " (not converged)")
+            + f", {t['slots']} of {s['faces']} face slots rewritten, {t['guarded']} non-Delaunay edges left guarded",
+            f"flipped mesh, triangle quality: smallest {t['quality_before'][0]:.4f} -> {t['quality'][0]:.4f}, median {t['quality_before'][1]:.4f} -> "
+            f"{t['quality'][1]:.4f}",
+            f"flipped mesh, face colours baked again: mean PSNR {s['mean_psnr']:.2f} -> {t['mean_psnr']:.2f} dB, mean SSIM {s['mean_ssim']:.4f} -> "
+            f"{t['mean_ssim']:.4f} (before: the split mesh, unflipped)"]
+
+
 def weld_report(welded):
     """The lines --weld-mesh prints for mesh_scores(...)["welded"]."""
     s, t = welded["stats"], welded["topology"]
@@ -721,6 +748,9 @@ if __name__ == "__main__":
     ap.add_argument("--split-edges", type=float, default=None, metavar="L", help="with --weld-mesh: split the welded mesh until no edge is longer than L "
                                                                                  "(diff_recon_hip.split_fused), bake the face colours again and print the face "
                                                                                  "count and PSNR / SSIM before and after")
+    ap.add_argument("--flip-edges", action="store_true", help="with --split-edges: flip the edges of the split mesh toward the Delaunay condition "
+                                                              "(diff_recon_hip.flip_fused), bake the face colours again and print rounds, flips, "
+                                                              "triangle quality and PSNR / SSIM beside the unflipped mesh")
     ap.add_argument("--eval-geometry", type=int, default=None, metavar="N", help="with --eval-mesh: compare N surface samples of the model's front faces with N of the hidden "
                                                                                    "target triangles (diff_recon_hip.mesh_distance) and print accuracy, completeness, "
                                                                                    "Chamfer and the F-score at 0.5, 1 and 2 times the target's median edge length")
@@ -769,6 +799,8 @@ if __name__ == "__main__":
     a = ap.parse_args()
     if a.split_edges is not None and a.weld_mesh is None:
         ap.error("--split-edges splits the welded mesh of --weld-mesh")
+    if a.flip_edges and a.split_edges is None:
+        ap.error("--flip-edges flips the split mesh of --split-edges")
     if a.split_edges is not None and not (a.split_edges > 0 and math.isfinite(a.split_edges)):
         ap.error("--split-edges needs a positive edge length")
     if a.check_intersections and a.extract_mesh is None and a.weld_mesh is None:
@@ -837,7 +869,7 @@ if __name__ == "__main__":
                           surface=a.eval_surface, visible=a.eval_visible, extract=a.extract_mesh, extract_color=a.extract_color, simplify=a.simplify_mesh,
                           min_piece=a.min_piece, smooth=a.smooth_mesh, fill=a.fill_holes, split=a.split_nonmanifold, orient=a.orient_faces,
                           texture=a.bake_texture, out=a.out, remesh=a.remesh, remesh_method=a.remesh_method,
-                          check_intersections=a.check_intersections, split_edges=a.split_edges)
+                          check_intersections=a.check_intersections, split_edges=a.split_edges, flip_edges=a.flip_edges)
         for v, (p_, s_) in enumerate(zip(res["psnr"], res["ssim"])):
             print(f"  opaque mesh, view {v}: PSNR {p_:.2f} dB  SSIM {s_:.4f}")
         print(f"opaque mesh of {m._vertex.shape[0]} triangles: mean PSNR {res['mean_psnr']:.2f} dB, mean SSIM {res['mean_ssim']:.4f} over {len(res['psnr'])} views")
@@ -855,7 +887,7 @@ if __name__ == "__main__":
                 for line in intersections_report(res["welded"]["intersections"], "welded"):
                     print(line)
             if a.split_edges is not None:
-                for line in split_edges_report(res["welded"]["split"]):
+                for line in split_edges_report(res["welded"]["split"]) + (flip_edges_report(res["welded"]["split"]) if a.flip_edges else []):
                     print(line)
         if a.eval_geometry is not None:
             for line in geometry_report(res["geometry"]):

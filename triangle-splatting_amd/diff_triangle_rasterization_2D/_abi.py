@@ -518,3 +518,23 @@ def bind_subdivide(lib):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     return lib
+
+
+# include/ts_flip.h: the whole C ABI of diff_recon_hip/libts_flip.so, the seventeenth library (diff_recon_hip/mesh_flip.py loads and binds it)
+FLIP_SIGNATURES = {
+    "tse_last_error": (C.c_char_p, []),
+    "tse_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "tse_flip": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_float, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+}
+
+
+def bind_flip(lib):
+    """Sets restype and argtypes of every function of include/ts_flip.h on `lib` (a ctypes.CDLL of libts_flip.so); a library that lacks one
+    is refused."""
+    missing = [name for name in FLIP_SIGNATURES if not hasattr(lib, name)]
+    if missing:
+        raise ImportError(f"{getattr(lib, '_name', lib)} does not export {', '.join(missing)}: rebuild it with `python triangle-splatting_amd/build.py`")
+    for name, (restype, argtypes) in FLIP_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return lib

@@ -10,7 +10,7 @@
  * kernel are ts2d_mesh_census_add's (ts_mesh.h), called with `texel_idx` as the key image and F T as the row count.
  *
  * All pointers are device pointers, except `fill` (three host floats); everything is enqueued on `stream` (a hipStream_t); no call allocates
- * or synchronises with the host; no call has a workspace.  Argument checks are decided before any HIP call: a negative V or F, an image
+ * or synchronises with the host, so the calls can be captured in a graph; no call has a workspace.  Argument checks are decided before any HIP call: a negative V or F, an image
  * or atlas size below 1, R outside [1, 64], Cx < 1, Cx Cy < K, min_count < 1, a tangent that is NaN, infinite or not positive, or a null
  * required pointer return TS2D_ERR_INVALID with the text in the last-error call of this header.  F T > 2^31 - 1, Wa Ha > 2^31 - 1 or
  * W H > 2^31 - 1 is TS2D_ERR_CAPACITY.  F == 0 still writes `fill` or -1 everywhere.  The outputs overlap neither each other nor an input.

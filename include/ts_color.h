@@ -8,7 +8,8 @@
  * closed.  libts_color.so links no object of the others and keeps its own error text.  The error codes are ts2d.h's.  Nothing is extracted
  * here: the surface comes from ts_volume.h, and colour is read off the grid at its vertices by a pure function of position.
  *
- * All pointers are device pointers; everything is enqueued on `stream` (a hipStream_t); no call allocates or synchronises with the host.
+ * All pointers are device pointers; everything is enqueued on `stream` (a hipStream_t); no call allocates or synchronises with the host, so the
+ * calls can be captured in a graph.
  * Argument checks are decided before any HIP call: a dimension below 1, a null required pointer, h or trunc (or a tangent) that is NaN,
  * infinite or not positive, an image size below 1, min_weight below 1, C outside [1, 8], a negative N, V or F return TS2D_ERR_INVALID with
  * the text in the last-error call of this header.  A grid of more than 2^27 samples, or an image of more than 2^31 - 1 pixels, is

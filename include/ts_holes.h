@@ -7,7 +7,8 @@
  * libts_smooth.so: the export lists of all eight are closed.  It links no other product object and keeps its own error text.  The error
  * codes are ts2d.h's.
  *
- * All pointers are device pointers; everything is enqueued on `stream` (a hipStream_t); no call allocates or synchronises with the host.
+ * All pointers are device pointers; everything is enqueued on `stream` (a hipStream_t); no call allocates or synchronises with the host, so the
+ * calls can be captured in a graph.
  * Argument checks are decided before any HIP call: a negative count, a negative num_entries, a negative max_loop_edges, num_loops above F or
  * num_members above 3 F, a null required pointer, a workspace below tsh_workspace_bytes(V, F) return TS2D_ERR_INVALID with the text in
  * tsh_last_error(); more than 357913941 faces (3 F half-edges, and ts_smooth.h's table) is TS2D_ERR_CAPACITY.

@@ -9,7 +9,8 @@
  * shares with the build (csrc/ts_bvh_layout.h), evaluates a ray with the very text that libts_ray.so evaluates it with
  * (csrc/ts_ray_tests.h) and keeps its own error text.  The error codes are ts2d.h's.
  *
- * All pointers are device pointers; everything is enqueued on `stream` (a hipStream_t); no call allocates or synchronises with the host.
+ * All pointers are device pointers; everything is enqueued on `stream` (a hipStream_t); no call allocates or synchronises with the host, so the
+ * calls can be captured in a graph.
  * Argument checks are decided before any HIP call: a negative count, a null required pointer, an index buffer below the index size of F (the
  * size query of ts_bvh.h; computed here from the layout header), a workspace below its size query, tmin or tmax NaN, tmin > tmax,
  * shared_direction, rule or only_undecided out of range return TS2D_ERR_INVALID with the text in the last-error call of this header.  Counts

@@ -7,7 +7,7 @@
  * (geometry loss, batch_size 3 = the three vertices of a triangle).  Both are EXACT searches, so results are defined by
  * the mathematics, not by the traversal; the traversal here is MI355X-shaped (Morton-sorted points physically gathered,
  * one workgroup per 1024-point box, candidate boxes staged through LDS and pruned per workgroup and per lane).
- * All pointers are device pointers; calls enqueue on `stream` and never synchronise.
+ * All pointers are device pointers; calls enqueue on `stream`, never allocate and never synchronise, so they can be captured in a graph.
  * Purity (DESIGN.md "Purity of the entry points"): the workspace may hold anything on entry; all P elements of mean_dist2 / nearest are
  * overwritten whatever they held (P == 0 writes nothing); no byte outside tsk_workspace_bytes(P) or the P outputs is written. */
 #ifndef TS_KNN_H

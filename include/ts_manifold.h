@@ -7,7 +7,8 @@
  * libts_smooth.so and libts_holes.so: the export lists of all nine are closed.  It links the product's radix_sort object and no other, and
  * keeps its own error text.  The error codes are ts2d.h's.
  *
- * All pointers are device pointers; everything is enqueued on `stream` (a hipStream_t); no call allocates or synchronises with the host.
+ * All pointers are device pointers; everything is enqueued on `stream` (a hipStream_t); no call allocates or synchronises with the host, so the
+ * calls can be captured in a graph.
  * Argument checks are decided before any HIP call: a negative count, a negative capacity, a null required pointer, a workspace below
  * tsf_workspace_bytes(V, F) return TS2D_ERR_INVALID with the text in tsf_last_error(); more than 715827882 faces (3 F corners in an int32;
  * the sort's layout asks for no less) is TS2D_ERR_CAPACITY, and so is, for tsf_split, V + 3 F above 2147483647 (the index of a new vertex).

@@ -7,7 +7,8 @@
  * libts_smooth.so, libts_holes.so and libts_manifold.so: the export lists of all ten are closed.  It links the product's radix_sort object
  * and no other, and keeps its own error text.  The error codes are ts2d.h's.
  *
- * All pointers are device pointers; everything is enqueued on `stream` (a hipStream_t); no call allocates or synchronises with the host.
+ * All pointers are device pointers; everything is enqueued on `stream` (a hipStream_t); no call allocates or synchronises with the host, so the
+ * calls can be captured in a graph.
  * Argument checks are decided before any HIP call: a negative count, a mode outside 0..2, mode 2 without vertices (with V > 0), a null
  * required pointer, a workspace below tsw_workspace_bytes(V, F) return TS2D_ERR_INVALID with the text in tsw_last_error(); more than
  * 715827882 faces (3 F half-edges in an int32; the sort's layout asks for no less) is TS2D_ERR_CAPACITY.

@@ -9,7 +9,8 @@
  * csrc/ts_bvh_walk.h and keeps its own error text.  The error codes are ts2d.h's.  The prefix is tsx_: tso_ is ts_optim.h's, whose functions
  * libts2d.so exports.
  *
- * All pointers are device pointers; everything is enqueued on `stream` (a hipStream_t); no call allocates or synchronises with the host.
+ * All pointers are device pointers; everything is enqueued on `stream` (a hipStream_t); no call allocates or synchronises with the host, so the
+ * calls can be captured in a graph.
  * Argument checks are decided before any HIP call: a negative count or capacity, a null required pointer, an index buffer below the index
  * size of its F (the size query of ts_bvh.h; computed here from the layout header), a capacity > 0 without both lists, a workspace below
  * its size query, a bit count outside [1, 31] return TS2D_ERR_INVALID with the text in the last-error call of this header.  Counts are

@@ -7,7 +7,8 @@
  * same radix sort (csrc/radix_sort.hip) and the same front half of the box searches (csrc/ts_knn_front.h), reads the index through the
  * layout header it shares with the build (csrc/ts_bvh_layout.h) and keeps its own error text.  The error codes are ts2d.h's.
  *
- * All pointers are device pointers; everything is enqueued on `stream` (a hipStream_t); no call allocates or synchronises with the host.
+ * All pointers are device pointers; everything is enqueued on `stream` (a hipStream_t); no call allocates or synchronises with the host, so the
+ * calls can be captured in a graph.
  * Argument checks are decided before any HIP call: a negative count, a null required pointer, an index buffer below the index size of F (the
  * size query of ts_bvh.h; computed here from the layout header), a workspace below its size query, tmin or tmax NaN, tmin > tmax, cull_back
  * other than 0 or 1 return TS2D_ERR_INVALID with the text in the last-error call of this header.  Counts are int32_t, at most 2^31 - 1025.

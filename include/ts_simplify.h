@@ -7,7 +7,8 @@
  * A library of its own, beside libts2d.so, libts_geom.so, libts_bvh.so, libts_ray.so, libts_volume.so and libts_color.so: the export lists
  * of all six are closed.  It links the product's radix sort object and keeps its own error text.  The error codes are ts2d.h's.
  *
- * All pointers are device pointers; everything is enqueued on `stream` (a hipStream_t); no call allocates or synchronises with the host.
+ * All pointers are device pointers; everything is enqueued on `stream` (a hipStream_t); no call allocates or synchronises with the host, so the
+ * calls can be captured in a graph.
  * Argument checks are decided before any HIP call: a negative count, a cell that is zero, negative, NaN or infinite, an origin that is NaN
  * or infinite, a lambda that is negative, NaN or infinite, a mode other than the two below, attributes with C outside 1 .. 8 (C is ignored
  * when attributes is NULL), a null required pointer, a workspace below tsq_workspace_bytes(V, F) return TS2D_ERR_INVALID with the text

@@ -7,7 +7,8 @@
  * the export lists of all seven are closed.  It links the product's radix sort object and keeps its own error text.  The error codes are
  * ts2d.h's.
  *
- * All pointers are device pointers; everything is enqueued on `stream` (a hipStream_t); no call allocates or synchronises with the host.
+ * All pointers are device pointers; everything is enqueued on `stream` (a hipStream_t); no call allocates or synchronises with the host, so the
+ * calls can be captured in a graph.
  * Argument checks are decided before any HIP call: a negative count, a lambda or mu that is NaN or infinite, a negative iteration count, a
  * max_move that is NaN or negative, a mode other than those below, a null required pointer, a workspace below tss_workspace_bytes(V, F)
  * return TS2D_ERR_INVALID with the text in tss_last_error(); more than 357913941 faces (6 F adjacency slots) is TS2D_ERR_CAPACITY.

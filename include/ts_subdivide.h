@@ -6,7 +6,8 @@
  * A library of its own, the sixteenth: the export lists of the other fifteen are closed.  It links the product's radix_sort object and no
  * other product object, and keeps its own error text.  The error codes are ts2d.h's.
  *
- * All pointers are device pointers; everything is enqueued on `stream` (a hipStream_t); no call allocates or synchronises with the host.
+ * All pointers are device pointers; everything is enqueued on `stream` (a hipStream_t); no call allocates or synchronises with the host, so the
+ * calls can be captured in a graph.
  * Argument checks are decided before any HIP call: a negative count, a negative channels, an unknown mode, a max_edge that is not >= 0 (NaN
  * included) in TSD_MARK_LONGER, a null required pointer, a workspace below tsd_workspace_bytes(V, F) return TS2D_ERR_INVALID with the text
  * in tsd_last_error(); TS2D_ERR_CAPACITY where 3 F, 4 F or V + 3 F does not fit the int32 indices (F above 536870911, or V + 3 F above

@@ -6,7 +6,8 @@
  * A library of its own, beside libts2d.so, libts_geom.so, libts_bvh.so and libts_ray.so: the export lists of all four are closed.
  * libts_volume.so links no object of the others and keeps its own error text.  The error codes are ts2d.h's.
  *
- * All pointers are device pointers; everything is enqueued on `stream` (a hipStream_t); no call allocates or synchronises with the host.
+ * All pointers are device pointers; everything is enqueued on `stream` (a hipStream_t); no call allocates or synchronises with the host, so the
+ * calls can be captured in a graph.
  * Argument checks are decided before any HIP call: a dimension below 1, a null required pointer, h or trunc (or a tangent) that is NaN,
  * infinite or not positive, an image size below 1, flags other than 0 or TSV_CARVE_UNCOVERED, min_weight below 1, iso NaN or infinite, a
  * negative capacity, a workspace below its size query return TS2D_ERR_INVALID with the text in the last-error call of this header.  A grid

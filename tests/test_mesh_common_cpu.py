@@ -1,6 +1,7 @@
-"""CPU tests of what the six indexed-mesh units share (csrc/ts_mesh_common.h, ts_mesh_scan.h, ts_mesh_runs.h, ts_mesh_edges.h; no GPU): every
-shared name is defined once, in a header; the units include what they use; a header edit rebuilds the units; and the six size queries
-answer what they answered before the shared pieces were single-sourced, byte for byte (tests/golden/mesh_workspace_bytes.json)."""
+"""CPU tests of what the indexed-mesh units share (csrc/ts_mesh_common.h, ts_mesh_scan.h, ts_mesh_runs.h, ts_mesh_edges.h; no GPU): every
+shared name is defined once, in a header; the units include what they use; no unit whose calls are captured in graphs clears or copies
+with a memset or memcpy node; a header edit rebuilds the units; and the six size queries answer what they answered before the shared
+pieces were single-sourced, byte for byte (tests/golden/mesh_workspace_bytes.json)."""
 import glob
 import importlib.util
 import json
@@ -11,7 +12,6 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-UNITS = ("mesh_weld.hip", "mesh_simplify.hip", "mesh_smooth.hip", "mesh_holes.hip", "mesh_manifold.hip", "mesh_orient.hip")
 SHARED_HEADERS = ("ts_mesh_common.h", "ts_mesh_scan.h", "ts_mesh_runs.h", "ts_mesh_edges.h")
 # shared name -> the header that defines it.  scan_offsets_kernel: the one-workgroup offsets kernel; edge_run_head: the run classifier
 DEFINED_IN = {
@@ -19,6 +19,8 @@ DEFINED_IN = {
     "count_into": "ts_mesh_common.h", "count4_into": "ts_mesh_common.h", "next_corner": "ts_mesh_common.h",
     "face_in_range": "ts_mesh_common.h", "face_takes_part": "ts_mesh_common.h", "edge_run_head": "ts_mesh_common.h",
     "sort_scratch_bytes": "ts_mesh_common.h", "Carver": "ts_mesh_common.h",
+    "mesh_fill_kernel": "ts_mesh_common.h", "mesh_copy_kernel": "ts_mesh_common.h", "fill_blocks": "ts_mesh_common.h",
+    "mesh_fill": "ts_mesh_common.h", "mesh_copy": "ts_mesh_common.h",
     "block_scan256": "ts_mesh_scan.h", "scan_offsets_kernel": "ts_mesh_scan.h", "scan_count_kernel": "ts_mesh_scan.h",
     "scan_apply_kernel": "ts_mesh_scan.h", "scan_columns": "ts_mesh_scan.h",
     "run_bounds_kernel": "ts_mesh_runs.h",
@@ -29,7 +31,14 @@ DEFINED_IN = {
 INCLUDES = {
     "mesh_weld.hip": {"ts_mesh_scan.h"}, "mesh_simplify.hip": {"ts_mesh_runs.h"}, "mesh_smooth.hip": {"ts_mesh_runs.h", "ts_mesh_scan.h"},
     "mesh_holes.hip": {"ts_mesh_scan.h"}, "mesh_manifold.hip": {"ts_mesh_edges.h", "ts_mesh_scan.h"}, "mesh_orient.hip": {"ts_mesh_edges.h"},
+    "mesh_subdivide.hip": {"ts_mesh_edges.h", "ts_mesh_scan.h"}, "mesh_flip.hip": {"ts_mesh_edges.h", "ts_mesh_scan.h"},
+    # the two that take mesh_fill / mesh_copy alone name the common header itself
+    "mesh_overlap.hip": {"ts_mesh_common.h"}, "mesh_distance.hip": {"ts_mesh_common.h"},
 }
+# every unit that clears or copies: each launches mesh_fill, and the ones that copied launch mesh_copy
+FILLS = ("mesh_holes.hip", "mesh_manifold.hip", "mesh_subdivide.hip", "mesh_smooth.hip", "mesh_orient.hip", "mesh_overlap.hip", "mesh_flip.hip",
+         "mesh_weld.hip", "mesh_simplify.hip", "mesh_distance.hip")
+COPIES = ("mesh_manifold.hip", "mesh_orient.hip", "mesh_overlap.hip")
 PROVIDES = {h: {n for n, where in DEFINED_IN.items() if where == h} for h in SHARED_HEADERS}
 
 
@@ -40,10 +49,13 @@ def _build_module():
     return mod
 
 
-def _code(path):
-    """The file without its comments: a name in a sentence is neither a definition nor a use."""
-    text = open(path).read()
+def _strip(text):
+    """Program text without its comments: a name in a sentence is neither a definition nor a use."""
     return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+
+
+def _code(path):
+    return _strip(open(path).read())
 
 
 def _definitions(name, code):
@@ -91,9 +103,35 @@ def test_the_units_include_what_they_use():
     for header, launcher in (("ts_mesh_runs.h", "run_bounds_kernel"), ("ts_mesh_edges.h", "sort_half_edges")):  # sort_half_edges launches other_end_kernel
         for unit, headers in INCLUDES.items():
             assert (header in headers) == bool(re.search(r"\b%s\b" % launcher, _code(os.path.join(csrc, unit)))), (unit, launcher)
-    assert "__global__" not in _code(os.path.join(csrc, "ts_mesh_common.h"))
+    common = _code(os.path.join(csrc, "ts_mesh_common.h"))  # its only kernels are the fill and the copy, and both are templates
+    assert len(re.findall(r"template <int = 0>\s*__global__", common)) == common.count("__global__") == 2
+    assert len(re.findall(r"__global__ void __launch_bounds__\(256\) mesh_(?:fill|copy)_kernel\b", common)) == 2
     scan = _code(os.path.join(csrc, "ts_mesh_scan.h"))
     assert len(re.findall(r"template <int COLS>\s*__global__", scan)) == scan.count("__global__") == 3  # templates: emitted where launched
+
+
+# Every unit behind a header whose calls "can be captured in a graph" (tests/test_graph_replay_gpu.py), with the launch headers, the shared
+# headers and the C-ABI files of those libraries: a memset or a copy node of a graph does not reliably run where stream order put it
+# (DESIGN.md 13b), so these clear and copy with kernels (mesh_fill, mesh_copy, ts_launch_zero_words).
+CAPTURABLE = ("mesh_*.hip", "api_*.hip", "volume.hip", "color_volume.hip", "knn.hip", "radix_sort.hip", "ts_*.h")
+
+
+def test_no_memset_or_memcpy_is_left_in_the_capturable_units():
+    csrc = _build_module().CSRC
+    files = sorted({p for pattern in CAPTURABLE for p in glob.glob(os.path.join(csrc, pattern))})
+    names = {os.path.basename(p) for p in files}
+    assert len(files) > 50 and {"mesh_holes.hip", "mesh_manifold.hip", "mesh_subdivide.hip", "mesh_smooth.hip", "mesh_orient.hip", "mesh_overlap.hip",
+                                "mesh_flip.hip", "mesh_weld.hip", "mesh_simplify.hip", "mesh_distance.hip", "ts_mesh_common.h"} <= names
+    left = {os.path.basename(p): sorted(set(re.findall(r"\bhipMem(?:set|cpy)\w*", _code(p)))) for p in files}
+    assert {f: calls for f, calls in left.items() if calls} == {}
+    # the scanner sees what it looks for, with the scan's own comment stripping: in a call, not in a comment of either kind
+    sample = "e = hipMemsetAsync(p, 0, n, s); // hipMemcpyAsync\n/* hipMemset(p)\n hipMemcpyDtoD */ hipMemcpy2DAsync(a);"
+    assert re.findall(r"\bhipMem(?:set|cpy)\w*", _strip(sample)) == ["hipMemsetAsync", "hipMemcpy2DAsync"]
+    # and what replaced them is what the units launch
+    for unit in sorted(n for n in names if n.startswith("mesh_") and n.endswith(".hip")):
+        code = _code(os.path.join(csrc, unit))
+        assert bool(re.search(r"\bmesh_fill\(", code)) == (unit in FILLS), unit
+        assert bool(re.search(r"\bmesh_copy\(", code)) == (unit in COPIES), unit
 
 
 def test_a_header_edit_rebuilds_the_units():

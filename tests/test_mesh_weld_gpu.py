@@ -328,8 +328,41 @@ def test_outputs_stay_between_their_guards(grid):
         assert np.array_equal(comp.view[:, 0].cpu().numpy(), topo["label"])
 
 
+def weld_call(inputs, eps=EPS):
+    """The calls of include/ts_weld.h in a row on the current stream, each reading the device outputs of the ones before it; every documented
+    output to its capacity (tests/replay.py; also tests/test_graph_replay_gpu.py at the smallest size)."""
+    from diff_recon_hip import mesh_weld
+    from diff_triangle_rasterization_2D import _C as native
+    lib = mesh_weld._lib
+    v, faces = inputs["v"], inputs["f"]
+    V, F = v.shape[0], faces.shape[0]
+    label, counted, remap = (torch.empty(V, device=DEV, dtype=torch.int32) for _ in range(3))
+    visits = torch.zeros(1, device=DEV, dtype=torch.int64)  # "that the caller cleared"
+    out_v, count = torch.empty((V, 3), device=DEV), torch.empty(1, device=DEV, dtype=torch.int32)
+    mean_remap, mean_v, mean_count = torch.empty(V, device=DEV, dtype=torch.int32), torch.empty((V, 3), device=DEV), torch.empty(1, device=DEV, dtype=torch.int32)
+    out_f, keep = torch.empty((F, 3), device=DEV, dtype=torch.int32), torch.empty(F, device=DEV, dtype=torch.uint8)
+    counts, pieces = torch.empty(4, device=DEV, dtype=torch.int64), torch.empty(V, device=DEV, dtype=torch.int32)
+    nbytes = lib.ts2d_weld_workspace_bytes(V, F)
+    ws = torch.empty(nbytes, device=DEV, dtype=torch.uint8)
+    s = torch.cuda.current_stream().cuda_stream
+    native._check(lib.ts2d_weld_labels(V, v.data_ptr(), eps, label.data_ptr(), ws.data_ptr(), nbytes, s), "labels")
+    native._check(lib.ts2d_weld_labels_counted(V, v.data_ptr(), eps, counted.data_ptr(), visits.data_ptr(), ws.data_ptr(), nbytes, s), "labels_counted")
+    native._check(lib.ts2d_weld_compact(V, label.data_ptr(), v.data_ptr(), 1, mean_remap.data_ptr(), mean_v.data_ptr(), mean_count.data_ptr(),
+                                        ws.data_ptr(), nbytes, s), "compact")
+    native._check(lib.ts2d_weld_compact(V, counted.data_ptr(), v.data_ptr(), 0, remap.data_ptr(), out_v.data_ptr(), count.data_ptr(), ws.data_ptr(),
+                                        nbytes, s), "compact")
+    native._check(lib.ts2d_weld_remap_faces(V, F, faces.data_ptr(), remap.data_ptr(), out_f.data_ptr(), keep.data_ptr(), s), "remap")
+    native._check(lib.ts2d_weld_edge_census(V, F, out_f.data_ptr(), keep.data_ptr(), counts.data_ptr(), ws.data_ptr(), nbytes, s), "census")
+    native._check(lib.ts2d_weld_face_components(V, F, out_f.data_ptr(), keep.data_ptr(), pieces.data_ptr(), ws.data_ptr(), nbytes, s), "components")
+    return {"label": label, "label_counted": counted, "box_visits": visits, "remap": remap, "vertices": out_v, "count": count,
+            "remap_mean": mean_remap, "vertices_mean": mean_v, "count_mean": mean_count, "faces": out_f, "keep": keep, "counts": counts,
+            "pieces": pieces}
+
+
 def test_the_calls_can_be_captured_in_a_graph(grid):
-    """No allocation and no host synchronisation inside: a weld is captured once and replayed on other data of the same size."""
+    """No allocation and no host synchronisation inside: a weld is captured once and replayed on other data of the same size.  Then the
+    same through tests/replay.py: all the calls of the header in one graph, captured on the coincident vertices and replayed on the grid
+    and on them in turn, every output compared with the eager run byte for byte."""
     from diff_recon_hip import mesh_weld
     from diff_triangle_rasterization_2D import _C as native
     lib = mesh_weld._lib
@@ -363,6 +396,17 @@ def test_the_calls_can_be_captured_in_a_graph(grid):
     graph.replay()
     torch.cuda.synchronize()
     assert int(count.item()) == 1 and not bool(keep.any()) and counts.tolist() == [0, 0, 0, 0]
+    del graph
+    import replay
+    case_a = {"v": _t(v_np), "f": _t(f_np, torch.int32)}
+    case_b = {"v": torch.zeros((V, 3), device=DEV), "f": _t(f_np, torch.int32)}
+    base_a, base_b, replays = replay.assert_replays(weld_call, case_a, case_b, differ=("count", "counts", "keep", "box_visits"))
+    assert replays == 8
+    i32, i64 = (lambda b, k: b[k].view(torch.int32).numpy()), (lambda b, k: b[k].view(torch.int64).tolist())
+    assert i32(base_a, "count").tolist() == [400] and np.array_equal(i32(base_a, "remap"), want["remap"]) and bool(base_a["keep"].all())
+    assert i64(base_a, "counts") == [1121, 76, 1045, 0] and np.array_equal(i32(base_a, "label"), i32(base_a, "label_counted"))
+    assert i32(base_b, "count").tolist() == [1] and not bool(base_b["keep"].any()) and i64(base_b, "counts") == [0, 0, 0, 0]
+    assert i32(base_a, "count_mean").tolist() == [400] and not i32(base_a, "pieces")[:400].any()  # the welded grid is one piece
 
 
 # ---- 8. render --------------------------------------------------------------------------------------------------------------------------------

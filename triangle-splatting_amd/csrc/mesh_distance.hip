@@ -22,6 +22,7 @@
 // stratified position in [0, W), a binary search in the prefix sums, barycentrics from 24-bit integers.  No float atomics, no rocPRIM.
 #include "ts_knn_front.h"
 #include "ts_geom_launch.h"
+#include "ts_mesh_common.h"
 
 #include <algorithm>
 
@@ -385,7 +386,7 @@ hipError_t ts_geom_sample_surface(int V, int F, const float *vertices, const int
     const SampleCarve c = sample_carve(ws, F);
     if (F > 0)
     {
-        hipError_t e = hipMemsetAsync(c.amax_bits, 0, 8, s);
+        hipError_t e = mesh_fill(c.amax_bits, 0, 8, s);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(area_max_kernel, dim3(std::min(c.nb, 1024)), dim3(256), 0, s, F, area, c.amax_bits);
         hipLaunchKernelGGL(weight_scan_kernel, dim3(c.nb), dim3(256), 0, s, F, area, c.amax_bits, c.C, c.block_sum);

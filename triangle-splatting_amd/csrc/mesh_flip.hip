@@ -358,7 +358,7 @@ hipError_t ts_flip_round(int V, int F, const float *vertices, const int32_t *fac
                          int32_t *out_faces, uint8_t *face_flipped, int32_t *edge_vertices, uint8_t *edge_state, int32_t *edge_opposite,
                          unsigned long long *totals, void *ws, hipStream_t s)
 {
-    hipError_t e = hipMemsetAsync(totals, 0, 4 * sizeof(unsigned long long), s);
+    hipError_t e = mesh_fill(totals, 0, 4 * sizeof(unsigned long long), s);
     if (e != hipSuccess) return e;
     if (F <= 0) return hipSuccess;
     const size_t f = (size_t)F, N = 3 * f;
@@ -392,10 +392,10 @@ hipError_t ts_flip_round(int V, int F, const float *vertices, const int32_t *fac
     }
     else // nothing takes part
     {
-        if ((e = hipMemsetAsync(edge_vertices, 0xFF, 2 * N * sizeof(int32_t), s)) != hipSuccess) return e;
-        if ((e = hipMemsetAsync(edge_opposite, 0xFF, 2 * N * sizeof(int32_t), s)) != hipSuccess) return e;
-        if ((e = hipMemsetAsync(edge_state, NO_EDGE, N, s)) != hipSuccess) return e;
-        if (out_faces && (e = hipMemsetAsync(c.half_edge_edge, 0xFF, N * sizeof(int32_t), s)) != hipSuccess) return e;
+        if ((e = mesh_fill(edge_vertices, 0xFF, 2 * N * sizeof(int32_t), s)) != hipSuccess) return e;
+        if ((e = mesh_fill(edge_opposite, 0xFF, 2 * N * sizeof(int32_t), s)) != hipSuccess) return e;
+        if ((e = mesh_fill(edge_state, NO_EDGE, N, s)) != hipSuccess) return e;
+        if (out_faces && (e = mesh_fill(c.half_edge_edge, 0xFF, N * sizeof(int32_t), s)) != hipSuccess) return e;
     }
     if (out_faces)
         hipLaunchKernelGGL(apply_kernel, dim3(nf), dim3(256), 0, s, F, faces, (const int32_t *)c.half_edge_edge, (const uint8_t *)edge_state,

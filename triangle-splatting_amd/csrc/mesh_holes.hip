@@ -391,20 +391,20 @@ hipError_t ts_holes_loops(int V, int F, const int32_t *faces, const uint8_t *kee
                           const int32_t *edge_faces, int num_entries, int32_t *half_edge_loop, int32_t *loop_offsets, int32_t *loop_half_edges,
                           unsigned long long *counts, void *ws, hipStream_t s)
 {
-    hipError_t e = hipMemsetAsync(counts, 0, 4 * sizeof(unsigned long long), s);
+    hipError_t e = mesh_fill(counts, 0, 4 * sizeof(unsigned long long), s);
     if (e != hipSuccess) return e;
     const size_t f = (size_t)(F > 0 ? F : 0), N = 3 * f;
-    e = hipMemsetAsync(loop_offsets, 0, (f + 1) * sizeof(int32_t), s);
+    e = mesh_fill(loop_offsets, 0, (f + 1) * sizeof(int32_t), s);
     if (e != hipSuccess || N == 0) return e;
-    e = hipMemsetAsync(loop_half_edges, 0xFF, N * sizeof(int32_t), s); // -1 past the member total
+    e = mesh_fill(loop_half_edges, 0xFF, N * sizeof(int32_t), s); // -1 past the member total
     if (e != hipSuccess) return e;
-    if (V <= 0) return hipMemsetAsync(half_edge_loop, 0xFF, N * sizeof(int32_t), s); // nothing takes part
+    if (V <= 0) return mesh_fill(half_edge_loop, 0xFF, N * sizeof(int32_t), s); // nothing takes part
     const size_t v = (size_t)V;
     const LoopsCarve c = loops_carve(ws, v, f);
     uint32_t *out_count = c.census, *in_count = c.census + v, *out_min = c.census + 2 * v;
-    e = hipMemsetAsync(out_count, 0, 2 * v * sizeof(uint32_t), s);
+    e = mesh_fill(out_count, 0, 2 * v * sizeof(uint32_t), s);
     if (e != hipSuccess) return e;
-    e = hipMemsetAsync(out_min, 0xFF, v * sizeof(uint32_t), s);
+    e = mesh_fill(out_min, 0xFF, v * sizeof(uint32_t), s);
     if (e != hipSuccess) return e;
     const unsigned nf = blocks256(f), nh = blocks256(N);
     hipLaunchKernelGGL(classify_kernel, dim3(nf), dim3(256), 0, s, V, F, faces, keep, offsets, neighbors, edge_faces, num_entries, c.succ, out_count,
@@ -431,24 +431,24 @@ hipError_t ts_holes_fill(int V, int F, const float *vertices, const int32_t *fac
                          int channels, uint8_t *loop_status, float *new_vertices, float *new_attributes, uint8_t *new_attr_valid,
                          int32_t *new_faces, int32_t *new_face_loop, unsigned long long *totals, void *ws, hipStream_t s)
 {
-    hipError_t e = hipMemsetAsync(totals, 0, 3 * sizeof(unsigned long long), s);
+    hipError_t e = mesh_fill(totals, 0, 3 * sizeof(unsigned long long), s);
     if (e != hipSuccess) return e;
     const size_t loops = (size_t)(num_loops > 0 ? num_loops : 0), members = (size_t)(num_members > 0 ? num_members : 0);
     if (members)
     {
-        e = hipMemsetAsync(new_faces, 0xFF, 3 * members * sizeof(int32_t), s);
+        e = mesh_fill(new_faces, 0xFF, 3 * members * sizeof(int32_t), s);
         if (e != hipSuccess) return e;
-        e = hipMemsetAsync(new_face_loop, 0xFF, members * sizeof(int32_t), s);
+        e = mesh_fill(new_face_loop, 0xFF, members * sizeof(int32_t), s);
         if (e != hipSuccess) return e;
     }
     if (loops == 0) return hipSuccess;
-    e = hipMemsetAsync(new_vertices, 0, 3 * loops * sizeof(float), s);
+    e = mesh_fill(new_vertices, 0, 3 * loops * sizeof(float), s);
     if (e != hipSuccess) return e;
     if (channels > 0)
     {
-        e = hipMemsetAsync(new_attributes, 0, loops * (size_t)channels * sizeof(float), s);
+        e = mesh_fill(new_attributes, 0, loops * (size_t)channels * sizeof(float), s);
         if (e != hipSuccess) return e;
-        e = hipMemsetAsync(new_attr_valid, 0, loops, s);
+        e = mesh_fill(new_attr_valid, 0, loops, s);
         if (e != hipSuccess) return e;
     }
     const FillCarve c = fill_carve(ws, loops);

@@ -244,16 +244,16 @@ size_t ts_manifold_workspace_bytes(int V, int F)
 hipError_t ts_manifold_fans(int V, int F, const int32_t *faces, const uint8_t *keep, int32_t *corner_fan, int32_t *vertex_fans,
                             unsigned long long *counts, void *ws, hipStream_t s)
 {
-    hipError_t e = hipMemsetAsync(counts, 0, 6 * sizeof(unsigned long long), s);
+    hipError_t e = mesh_fill(counts, 0, 6 * sizeof(unsigned long long), s);
     if (e != hipSuccess) return e;
     const size_t f = (size_t)(F > 0 ? F : 0), N = 3 * f;
     if (V > 0)
     {
-        e = hipMemsetAsync(vertex_fans, 0, (size_t)V * sizeof(int32_t), s);
+        e = mesh_fill(vertex_fans, 0, (size_t)V * sizeof(int32_t), s);
         if (e != hipSuccess) return e;
     }
     if (N == 0) return hipSuccess;
-    if (V <= 0) return hipMemsetAsync(corner_fan, 0xFF, N * sizeof(int32_t), s); // nothing takes part
+    if (V <= 0) return mesh_fill(corner_fan, 0xFF, N * sizeof(int32_t), s); // nothing takes part
     const FansCarve c = fans_carve(ws, f);
     const unsigned nf = blocks256(f), nh = blocks256(N);
     hipLaunchKernelGGL(records_kernel, dim3(nf), dim3(256), 0, s, V, F, faces, keep, c.sort.k[0], c.sort.v[0], c.parent, counts);
@@ -267,23 +267,23 @@ hipError_t ts_manifold_fans(int V, int F, const int32_t *faces, const uint8_t *k
 hipError_t ts_manifold_split(int V, int F, const int32_t *faces, const uint8_t *keep, const int32_t *corner_fan, int capacity, int32_t *out_faces,
                              int32_t *new_vertex_source, int32_t *new_vertex_fan, unsigned long long *totals, void *ws, hipStream_t s)
 {
-    hipError_t e = hipMemsetAsync(totals, 0, 2 * sizeof(unsigned long long), s);
+    hipError_t e = mesh_fill(totals, 0, 2 * sizeof(unsigned long long), s);
     if (e != hipSuccess) return e;
     if (capacity > 0)
     {
-        e = hipMemsetAsync(new_vertex_source, 0xFF, (size_t)capacity * sizeof(int32_t), s); // -1 past the number of new vertices
+        e = mesh_fill(new_vertex_source, 0xFF, (size_t)capacity * sizeof(int32_t), s); // -1 past the number of new vertices
         if (e != hipSuccess) return e;
-        e = hipMemsetAsync(new_vertex_fan, 0xFF, (size_t)capacity * sizeof(int32_t), s);
+        e = mesh_fill(new_vertex_fan, 0xFF, (size_t)capacity * sizeof(int32_t), s);
         if (e != hipSuccess) return e;
     }
     const size_t f = (size_t)(F > 0 ? F : 0), N = 3 * f;
     if (N == 0) return hipSuccess;
-    if (V <= 0) return hipMemcpyAsync(out_faces, faces, N * sizeof(int32_t), hipMemcpyDeviceToDevice, s); // nothing takes part
+    if (V <= 0) return mesh_copy(out_faces, faces, N * sizeof(int32_t), s); // nothing takes part
     const size_t v = (size_t)V;
     const SplitCarve c = split_carve(ws, v, f);
-    e = hipMemsetAsync(c.keeper, 0xFF, v * sizeof(uint32_t), s);
+    e = mesh_fill(c.keeper, 0xFF, v * sizeof(uint32_t), s);
     if (e != hipSuccess) return e;
-    e = hipMemsetAsync(c.flag, 0, N * sizeof(uint32_t), s);
+    e = mesh_fill(c.flag, 0, N * sizeof(uint32_t), s);
     if (e != hipSuccess) return e;
     const unsigned nf = blocks256(f), nh = blocks256(N);
     hipLaunchKernelGGL(labels_kernel, dim3(nf), dim3(256), 0, s, V, F, faces, keep, corner_fan, c.lab, c.flag, c.keeper);

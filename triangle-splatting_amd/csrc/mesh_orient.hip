@@ -263,7 +263,7 @@ OrientCarve orient_carve(void *ws, size_t F)
     Carver w(ws);
     c.sort = edge_sort_carve(w, 3 * F);
     c.parent = w.words(2 * F);
-    c.sums_bytes = 24 * F; // the per-piece sums in one block, cleared by one memset: the 64-bit columns first
+    c.sums_bytes = 24 * F; // the per-piece sums in one block, cleared by one fill (mesh_fill): the 64-bit columns first
     c.sums = w.bytes(c.sums_bytes);
     c.piece_largest = (unsigned long long *)c.sums;
     c.piece_volume = (long long *)(c.piece_largest + F);
@@ -283,20 +283,20 @@ size_t ts_orient_workspace_bytes(int V, int F)
 hipError_t ts_orient_faces(int V, int F, const float *vertices, const int32_t *faces, const uint8_t *keep, int mode, int32_t *face_piece,
                            uint8_t *face_flip, int32_t *out_faces, unsigned long long *counts, void *ws, hipStream_t s)
 {
-    hipError_t e = hipMemsetAsync(counts, 0, 10 * sizeof(unsigned long long), s);
+    hipError_t e = mesh_fill(counts, 0, 10 * sizeof(unsigned long long), s);
     if (e != hipSuccess) return e;
     const size_t f = (size_t)(F > 0 ? F : 0), N = 3 * f;
     if (N == 0) return hipSuccess;
     if (V <= 0) // nothing takes part
     {
-        e = hipMemsetAsync(face_piece, 0xFF, f * sizeof(int32_t), s);
+        e = mesh_fill(face_piece, 0xFF, f * sizeof(int32_t), s);
         if (e != hipSuccess) return e;
-        e = hipMemsetAsync(face_flip, 0, f, s);
+        e = mesh_fill(face_flip, 0, f, s);
         if (e != hipSuccess) return e;
-        return hipMemcpyAsync(out_faces, faces, N * sizeof(int32_t), hipMemcpyDeviceToDevice, s);
+        return mesh_copy(out_faces, faces, N * sizeof(int32_t), s);
     }
     const OrientCarve c = orient_carve(ws, f);
-    e = hipMemsetAsync(c.sums, 0, c.sums_bytes, s);
+    e = mesh_fill(c.sums, 0, c.sums_bytes, s);
     if (e != hipSuccess) return e;
     const unsigned nf = blocks256(f), nh = blocks256(N);
     hipLaunchKernelGGL(records_kernel, dim3(nf), dim3(256), 0, s, V, F, faces, keep, c.sort.k[0], c.sort.v[0], c.parent, counts);

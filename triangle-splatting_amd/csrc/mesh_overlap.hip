@@ -17,6 +17,7 @@
 // (ts_mesh_edges.h) orders its edges; pairs and kinds are gathered into the workspace and copied back.
 #include "ts_bvh_layout.h"
 #include "ts_bvh_walk.h"
+#include "ts_mesh_common.h"
 #include "ts_overlap_launch.h"
 
 namespace
@@ -302,9 +303,9 @@ hipError_t ts_overlap_query(int FA, const void *bvh_a, const int32_t *faces, int
                             uint64_t *stats, int capacity, int32_t *pairs, uint8_t *kind, unsigned long long *leaf_visits, hipStream_t s)
 {
     const bool self = faces != nullptr;
-    hipError_t e = hipMemsetAsync(stats, 0, 8 * sizeof(uint64_t), s);
-    if (e == hipSuccess && FA > 0) e = hipMemsetAsync(count_a, 0, (size_t)FA * sizeof(int32_t), s);
-    if (e == hipSuccess && !self && count_b && FB > 0) e = hipMemsetAsync(count_b, 0, (size_t)FB * sizeof(int32_t), s);
+    hipError_t e = mesh_fill(stats, 0, 8 * sizeof(uint64_t), s);
+    if (e == hipSuccess && FA > 0) e = mesh_fill(count_a, 0, (size_t)FA * sizeof(int32_t), s);
+    if (e == hipSuccess && !self && count_b && FB > 0) e = mesh_fill(count_b, 0, (size_t)FB * sizeof(int32_t), s);
     if (e != hipSuccess) return e;
     if (FA <= 0 || (!self && FB <= 0)) return hipSuccess;
     const BvhView a = bvh_view(const_cast<void *>(bvh_a), FA);
@@ -334,7 +335,7 @@ hipError_t ts_overlap_sort_pairs(int P, int bits_first, int bits_second, int32_t
     uint32_t *const k2[2] = {c.k[at ^ 1], c.k[at]}, *const v2[2] = {c.v[at], c.v[at ^ 1]};
     const int at2 = ts_radix_sort_pairs(k2, v2, (size_t)P, bits_first, c.scratch, s); // then by the first, stable: (first, second) order
     hipLaunchKernelGGL(gather_pairs_kernel, dim3(nb), dim3(256), 0, s, P, v2[at2], pairs, kind, c.pairs, c.kind);
-    hipError_t e = hipMemcpyAsync(pairs, c.pairs, (size_t)P * 8, hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(kind, c.kind, (size_t)P, hipMemcpyDeviceToDevice, s);
+    hipError_t e = mesh_copy(pairs, c.pairs, (size_t)P * 8, s);
+    if (e == hipSuccess) e = mesh_copy(kind, c.kind, (size_t)P, s);
     return e == hipSuccess ? hipGetLastError() : e;
 }

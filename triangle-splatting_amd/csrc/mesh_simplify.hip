@@ -425,7 +425,7 @@ hipError_t ts_simplify_place(int V, int F, const float *vertices, const int32_t 
     if (V <= 0) return hipSuccess;
     const size_t n = (size_t)V, f = (size_t)(F > 0 ? F : 0);
     const PlaceCarve c = place_carve(ws, n, f);
-    hipError_t e = hipMemsetAsync(c.bounds, 0, 4 * n * sizeof(uint32_t), s); // a rank without a run: start == end == 0
+    hipError_t e = mesh_fill(c.bounds, 0, 4 * n * sizeof(uint32_t), s); // a rank without a run: start == end == 0
     if (e != hipSuccess) return e;
     uint32_t *mstart = c.bounds, *mend = c.bounds + n, *fstart = c.bounds + 2 * n, *fend = c.bounds + 3 * n;
     hipLaunchKernelGGL(member_keys_kernel, dim3(blocks256(n)), dim3(256), 0, s, V, remap, c.mk[0], c.mv[0]);
@@ -451,7 +451,7 @@ hipError_t ts_simplify_place(int V, int F, const float *vertices, const int32_t 
 hipError_t ts_simplify_unique_faces(int V, int F, const int32_t *faces, const uint8_t *keep_in, uint8_t *keep_out, unsigned long long *counts,
                                     void *ws, hipStream_t s)
 {
-    hipError_t e = hipMemsetAsync(counts, 0, 2 * sizeof(unsigned long long), s);
+    hipError_t e = mesh_fill(counts, 0, 2 * sizeof(unsigned long long), s);
     if (e != hipSuccess) return e;
     if (F <= 0) return hipSuccess;
     const size_t n = (size_t)F;

@@ -379,19 +379,19 @@ size_t ts_smooth_workspace_bytes(int V, int F)
 hipError_t ts_smooth_adjacency(int V, int F, const int32_t *faces, const uint8_t *keep, int32_t *offsets, int32_t *neighbors, int32_t *edge_faces,
                                uint8_t *vertex_class, unsigned long long *counts, void *ws, hipStream_t s)
 {
-    hipError_t e = hipMemsetAsync(counts, 0, 4 * sizeof(unsigned long long), s);
+    hipError_t e = mesh_fill(counts, 0, 4 * sizeof(unsigned long long), s);
     if (e != hipSuccess || V <= 0) return e;
     const size_t f = (size_t)(F > 0 ? F : 0), N = 6 * f;
     if (N == 0) // every row is empty
     {
-        e = hipMemsetAsync(offsets, 0, ((size_t)V + 1) * sizeof(int32_t), s);
+        e = mesh_fill(offsets, 0, ((size_t)V + 1) * sizeof(int32_t), s);
         if (e != hipSuccess) return e;
-        return hipMemsetAsync(vertex_class, 0, (size_t)V, s);
+        return mesh_fill(vertex_class, 0, (size_t)V, s);
     }
     const AdjacencyCarve c = adjacency_carve(ws, f);
-    e = hipMemsetAsync(neighbors, 0xFF, N * sizeof(int32_t), s); // entries from offsets[V] on stay -1 ...
+    e = mesh_fill(neighbors, 0xFF, N * sizeof(int32_t), s); // entries from offsets[V] on stay -1 ...
     if (e != hipSuccess) return e;
-    e = hipMemsetAsync(edge_faces, 0, N * sizeof(int32_t), s); // ... and 0
+    e = mesh_fill(edge_faces, 0, N * sizeof(int32_t), s); // ... and 0
     if (e != hipSuccess) return e;
     const int bits = bit_length((uint32_t)V); // the sentinel V included
     hipLaunchKernelGGL(records_kernel, dim3(blocks256(f)), dim3(256), 0, s, V, F, faces, keep, c.k[0], c.v[0]);
@@ -441,7 +441,7 @@ hipError_t ts_smooth_vertex_normals(int V, int F, const float *vertices, const i
     if (V <= 0) return hipSuccess;
     const size_t n = (size_t)V, f = (size_t)(F > 0 ? F : 0);
     const NormalCarve c = normal_carve(ws, n, f);
-    hipError_t e = hipMemsetAsync(c.bounds, 0, 2 * n * sizeof(uint32_t), s); // a vertex without a run: start == end == 0
+    hipError_t e = mesh_fill(c.bounds, 0, 2 * n * sizeof(uint32_t), s); // a vertex without a run: start == end == 0
     if (e != hipSuccess) return e;
     uint32_t *fstart = c.bounds, *fend = c.bounds + n;
     int fat = 0;

@@ -361,16 +361,16 @@ hipError_t ts_subdivide_edges(int V, int F, const float *vertices, const int32_t
                               int32_t *edge_use, double *edge_length2, int32_t *half_edge_edge, unsigned long long *counts, void *ws,
                               hipStream_t s)
 {
-    hipError_t e = hipMemsetAsync(counts, 0, 4 * sizeof(unsigned long long), s);
+    hipError_t e = mesh_fill(counts, 0, 4 * sizeof(unsigned long long), s);
     if (e != hipSuccess) return e;
     const size_t N = 3 * (size_t)(F > 0 ? F : 0);
     if (N == 0) return hipSuccess;
     if (V <= 0) // nothing takes part
     {
-        if ((e = hipMemsetAsync(edge_vertices, 0xFF, 2 * N * sizeof(int32_t), s)) != hipSuccess) return e;
-        if ((e = hipMemsetAsync(edge_use, 0, N * sizeof(int32_t), s)) != hipSuccess) return e;
-        if (edge_length2 && (e = hipMemsetAsync(edge_length2, 0, N * sizeof(double), s)) != hipSuccess) return e;
-        return hipMemsetAsync(half_edge_edge, 0xFF, N * sizeof(int32_t), s);
+        if ((e = mesh_fill(edge_vertices, 0xFF, 2 * N * sizeof(int32_t), s)) != hipSuccess) return e;
+        if ((e = mesh_fill(edge_use, 0, N * sizeof(int32_t), s)) != hipSuccess) return e;
+        if (edge_length2 && (e = mesh_fill(edge_length2, 0, N * sizeof(double), s)) != hipSuccess) return e;
+        return mesh_fill(half_edge_edge, 0xFF, N * sizeof(int32_t), s);
     }
     const SubdivideCarve c = subdivide_carve(ws, (size_t)F);
     const SortedEdges edges = edge_table(V, F, vertices, faces, keep, c, MarkRule{MARK_ALL, 0.0, nullptr}, edge_vertices, edge_use, edge_length2,
@@ -385,13 +385,13 @@ hipError_t ts_subdivide_split(int V, int F, const float *vertices, const int32_t
                               float *new_attributes, uint8_t *new_attr_valid, int32_t *new_vertex_edge, int32_t *out_faces,
                               int32_t *out_face_parent, unsigned long long *totals, void *ws, hipStream_t s)
 {
-    hipError_t e = hipMemsetAsync(totals, 0, 4 * sizeof(unsigned long long), s);
+    hipError_t e = mesh_fill(totals, 0, 4 * sizeof(unsigned long long), s);
     if (e != hipSuccess) return e;
     if (F <= 0) return hipSuccess;
     const size_t f = (size_t)F, N = 3 * f;
     const SubdivideCarve c = subdivide_carve(ws, f);
     const unsigned nf = blocks256(f), nh = blocks256(N);
-    if ((e = hipMemsetAsync(c.total, 0, 4 * sizeof(uint32_t), s)) != hipSuccess) return e;
+    if ((e = mesh_fill(c.total, 0, 4 * sizeof(uint32_t), s)) != hipSuccess) return e;
     if (V > 0)
     {
         const MarkRule rule{mode, (double)max_edge * (double)max_edge, vertex_limit};
@@ -405,7 +405,7 @@ hipError_t ts_subdivide_split(int V, int F, const float *vertices, const int32_t
         hipLaunchKernelGGL(scatter_kernel, dim3(nh), dim3(256), 0, s, N, edges.sval, (const uint32_t *)c.eid, (const int32_t *)c.edge_mid,
                            (int32_t *)nullptr, c.half_edge_mid);
     }
-    else if ((e = hipMemsetAsync(c.half_edge_mid, 0xFF, N * sizeof(int32_t), s)) != hipSuccess) return e; // nothing takes part
+    else if ((e = mesh_fill(c.half_edge_mid, 0xFF, N * sizeof(int32_t), s)) != hipSuccess) return e; // nothing takes part
     hipLaunchKernelGGL(vertex_tail_kernel, dim3(nh), dim3(256), 0, s, N, (const uint32_t *)(c.total + 1), channels, new_vertices, new_attributes,
                        new_attr_valid, new_vertex_edge);
     hipLaunchKernelGGL(pieces_kernel, dim3(nf), dim3(256), 0, s, F, (const int32_t *)c.half_edge_mid, c.pieces, totals);

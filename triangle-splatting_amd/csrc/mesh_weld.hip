@@ -331,9 +331,9 @@ hipError_t ts_weld_compact(int V, const uint32_t *label, const float *vertices, 
     if (V <= 0) return hipSuccess;
     const CompactCarve c = compact_carve(ws, V);
     const unsigned nv = blocks256((size_t)V);
-    hipError_t e = hipMemsetAsync(out_vertices, 0, (size_t)V * 3 * sizeof(float), s); // rows V' .. V - 1 stay zero
+    hipError_t e = mesh_fill(out_vertices, 0, (size_t)V * 3 * sizeof(float), s); // rows V' .. V - 1 stay zero
     if (e != hipSuccess) return e;
-    e = hipMemsetAsync(c.root_rank, 0, (size_t)V * sizeof(uint32_t), s); // a foreign label that names a non-root then ranks 0: always a row of out_vertices
+    e = mesh_fill(c.root_rank, 0, (size_t)V * sizeof(uint32_t), s); // a foreign label that names a non-root then ranks 0: always a row of out_vertices
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(root_count_kernel, dim3(c.nb), dim3(256), 0, s, V, label, c.block_count);
     hipLaunchKernelGGL(scan_offsets_kernel<1>, dim3(1), dim3(256), 0, s, c.nb, c.block_count, (uint32_t *)count);
@@ -362,7 +362,7 @@ hipError_t ts_weld_edge_census(int V, int F, const int32_t *faces, const uint8_t
     const size_t E = 3 * (size_t)F;
     Carver w(ws);
     const SortCarve c = sort_carve(w, E);
-    hipError_t e = hipMemsetAsync(counts, 0, 4 * sizeof(unsigned long long), s);
+    hipError_t e = mesh_fill(counts, 0, 4 * sizeof(unsigned long long), s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(edge_keys_kernel, dim3(blocks256((size_t)F)), dim3(256), 0, s, V, F, faces, keep, c.a[0], c.b[0]);
     const int bits = bit_length((uint32_t)(V > 0 ? V : 0)); // the sentinel V included

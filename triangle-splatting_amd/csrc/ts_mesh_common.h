@@ -1,7 +1,9 @@
 // ts_mesh_common.h -- what the indexed-mesh units (mesh_weld.hip, mesh_simplify.hip, mesh_smooth.hip, mesh_holes.hip, mesh_manifold.hip,
-// mesh_orient.hip) share besides their scans (ts_mesh_scan.h), their run bounds (ts_mesh_runs.h) and the sort-by-edge front
-// (ts_mesh_edges.h), single-sourced.  Host and device helpers only, every one with internal linkage: the units live in different libraries,
-// so each gets its own copy.  No kernel is defined here: an unreferenced kernel is still emitted, and not every unit launches every kernel.
+// mesh_orient.hip, mesh_subdivide.hip, mesh_flip.hip) share besides their scans (ts_mesh_scan.h), their run bounds (ts_mesh_runs.h) and
+// the sort-by-edge front (ts_mesh_edges.h), single-sourced; mesh_overlap.hip and mesh_distance.hip include it for its fill and its copy
+// alone.  Host and device helpers, every one with internal linkage: the units live in different libraries,
+// so each gets its own copy.  The only kernels defined here are the fill and the copy below, as templates: an unreferenced kernel is still
+// emitted, a template that nobody launches is not, and not every unit launches both.
 #pragma once
 #include "ts2d_common.h"
 
@@ -80,6 +82,62 @@ __device__ __forceinline__ int edge_run_head(int V, size_t N, size_t j, const ui
     const bool two = j + 1 < N && lo[j + 1] == a && hi[j + 1] == b;
     const bool three = two && j + 2 < N && lo[j + 2] == a && hi[j + 2] == b;
     return three ? 3 : two ? 2 : 1;
+}
+
+// ---- fills and copies --------------------------------------------------------------------------------------------------------------------
+// A hipMemsetAsync or a device-to-device hipMemcpyAsync that is captured into a graph does not reliably run where stream order put it on
+// this stack ("Stream order of the mesh entry points"): the mesh units clear and copy with these two kernels instead, after
+// the model of ts_launch_zero_words.  Any address, any length; whole 32-bit words where the addresses allow, the odd bytes one by one.
+template <int = 0>
+__global__ void __launch_bounds__(256) mesh_fill_kernel(uint8_t *__restrict__ p, size_t bytes, uint32_t word)
+{
+    const size_t stride = (size_t)gridDim.x * 256, i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (((size_t)p & 3) == 0)
+    {
+        const size_t words = bytes / 4;
+        for (size_t j = i; j < words; j += stride) ((uint32_t *)p)[j] = word;
+        if (i < (bytes & 3)) p[4 * words + i] = (uint8_t)word;
+    }
+    else
+        for (size_t j = i; j < bytes; j += stride) p[j] = (uint8_t)word;
+}
+
+template <int = 0>
+__global__ void __launch_bounds__(256) mesh_copy_kernel(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, size_t bytes)
+{
+    const size_t stride = (size_t)gridDim.x * 256, i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if ((((size_t)dst | (size_t)src) & 3) == 0)
+    {
+        const size_t words = bytes / 4;
+        for (size_t j = i; j < words; j += stride) ((uint32_t *)dst)[j] = ((const uint32_t *)src)[j];
+        if (i < (bytes & 3)) dst[4 * words + i] = src[4 * words + i];
+    }
+    else
+        for (size_t j = i; j < bytes; j += stride) dst[j] = src[j];
+}
+
+inline unsigned fill_blocks(size_t bytes, bool by_words)
+{
+    const size_t units = by_words ? std::max(bytes / 4, (size_t)1) : bytes; // one block at least: it also writes the odd bytes behind the words
+    return (unsigned)std::min((units + 255) / 256, (size_t)1 << 20);        // the kernels stride: a count beyond 2^28 units is covered too
+}
+
+// p[0 .. bytes) = the low byte of `value`, enqueued on s: hipMemsetAsync's arguments and meaning, as a kernel launch
+inline hipError_t mesh_fill(void *p, int value, size_t bytes, hipStream_t s)
+{
+    if (bytes == 0) return hipSuccess;
+    const bool by_words = ((size_t)p & 3) == 0;
+    hipLaunchKernelGGL(mesh_fill_kernel<0>, dim3(fill_blocks(bytes, by_words)), dim3(256), 0, s, (uint8_t *)p, bytes, (uint32_t)(value & 0xFF) * 0x01010101u);
+    return hipGetLastError();
+}
+
+// dst[0 .. bytes) = src[0 .. bytes), device to device, the ranges disjoint, enqueued on s
+inline hipError_t mesh_copy(void *dst, const void *src, size_t bytes, hipStream_t s)
+{
+    if (bytes == 0) return hipSuccess;
+    const bool by_words = (((size_t)dst | (size_t)src) & 3) == 0;
+    hipLaunchKernelGGL(mesh_copy_kernel<0>, dim3(fill_blocks(bytes, by_words)), dim3(256), 0, s, (uint8_t *)dst, (const uint8_t *)src, bytes);
+    return hipGetLastError();
 }
 
 // ---- workspace ----------------------------------------------------------------------------------------------------------------------------

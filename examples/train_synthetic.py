@@ -28,6 +28,10 @@ A "ground truth" is rendered from a hidden set of triangles from several cameras
                                                         then split the welded mesh until no edge is longer than L (diff_recon_hip.split_fused), start
                                                         the pieces from their parents' colours, bake the face colours again (bake_face_colors) and
                                                         print the face count and PSNR / SSIM before and after
+    python examples/train_synthetic.py --eval-mesh --weld-mesh EPS [--split-edges L] [--flip-edges] --collapse-edges L
+                                                        collapse the edges shorter than L behind the other steps (diff_recon_hip.collapse_fused),
+                                                        bake the face colours again and print rounds, collapses, vertices and faces, triangle
+                                                        quality and PSNR / SSIM beside the mesh before
     python examples/train_synthetic.py --eval-mesh --weld-mesh EPS --split-edges L --flip-edges
                                                         then flip the edges of the split mesh toward the Delaunay condition
                                                         (diff_recon_hip.flip_fused), bake the face colours again and print rounds, flips, the
@@ -259,7 +263,7 @@ def train(rasterizer="2D", iters=200, triangles=20000, width=256, height=192, se
 
 def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, height=192, seed=0, views=2, refine=False, weld=None, geometry=None, surface=None,
                 visible=False, extract=None, extract_color=False, simplify=None, min_piece=0, smooth=None, fill=None, split=False, orient=None, texture=None,
-                out=None, remesh=None, remesh_method="rays", check_intersections=False, split_edges=None, flip_edges=False):
+                out=None, remesh=None, remesh_method="rays", check_intersections=False, split_edges=None, flip_edges=False, collapse_edges=None):
     """PSNR / SSIM of the model's opaque mesh -- mesh_from_triangles: one colour per face from the DC coefficients, back faces as reversed
     twins, the soup saveGLB writes -- against the hidden targets of train() called with the same arguments (diff_recon_hip.evaluate_mesh).
     refine: the result also holds "refined", the same scores (plus "kept" and "triangles") of the mesh after a census over these views
@@ -339,22 +343,31 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
             res["welded"]["oriented"] = D.orient_fused(w, orient).stats["orient"]
         if check_intersections:
             res["welded"]["intersections"] = D.self_intersection_report((w.vertices, w.faces))
+        score = lambda mesh: D.evaluate_mesh(cams, mesh.vertices, mesh.faces, D.bake_face_colors(cams, mesh.vertices, mesh.faces, mesh.faces_color),
+                                             bg_color=kw["bg_color"])
+
+        def quality(mesh):  # [smallest, median]; a face that takes no part counts as degenerate
+            q = D.triangle_quality(mesh.vertices, mesh.faces).nan_to_num(0.0)
+            return [float(q.min()), float(q.median())]
+        last = w  # the mesh behind the steps so far
         if split_edges is not None:
-            score = lambda mesh: D.evaluate_mesh(cams, mesh.vertices, mesh.faces, D.bake_face_colors(cams, mesh.vertices, mesh.faces, mesh.faces_color),
-                                                 bg_color=kw["bg_color"])
-            fine = D.split_fused(w, split_edges)
+            fine = last = D.split_fused(w, split_edges)
             res["welded"]["split"] = dict(score(fine), max_edge=float(split_edges), faces=int(fine.faces.shape[0]), vertices=int(fine.vertices.shape[0]),
                                           rounds=fine.stats["split"]["rounds"], converged=fine.stats["split"]["converged"],
                                           before=dict(score(w), faces=int(w.faces.shape[0])))
             if flip_edges:
-                def quality(mesh):  # [smallest, median]; a face that takes no part counts as degenerate
-                    q = D.triangle_quality(mesh.vertices, mesh.faces).nan_to_num(0.0)
-                    return [float(q.min()), float(q.median())]
-                flat = D.flip_fused(fine)
+                flat = last = D.flip_fused(fine)
                 t = flat.stats["flip"]
                 res["welded"]["split"]["flipped"] = dict(score(flat), rounds=t["rounds"], flips=t["flipped"], guarded=t["guarded"],
                                                          converged=t["converged"], slots=int(t["face_flipped"].sum()),
                                                          quality=quality(flat), quality_before=quality(fine))
+        if collapse_edges is not None:
+            coarse = D.collapse_fused(last, collapse_edges)
+            t = coarse.stats["collapse"]
+            res["welded"]["collapsed"] = dict(score(coarse), min_edge=float(collapse_edges), rounds=t["rounds"], collapses=t["collapsed"],
+                                              guarded=t["guarded"], converged=t["converged"], faces=int(coarse.faces.shape[0]),
+                                              vertices=int(coarse.vertices.shape[0]), quality=quality(coarse), quality_before=quality(last),
+                                              before=dict(score(last), faces=int(last.faces.shape[0]), vertices=int(last.vertices.shape[0])))
     if geometry is not None or surface is not None:
         target = torch.from_numpy(np.ascontiguousarray(synthetic.scene(triangles, width, height, 2, seed=seed, edge_px=10.0)["vertex"])).to(m._vertex.device)
         edges = (target - target.roll(1, dims=1)).norm(dim=2)  # the hidden scene of _setup: every draw comes from the seeded generator
@@ -579,6 +592,17 @@ def split_edges_report(s):
             f"{s['mean_ssim']:.4f} (before: the welded mesh baked the same way; a fit to the training views)"]
 
 
+def collapse_edges_report(t):
+    """The lines --collapse-edges prints for mesh_scores(...)["welded"]["collapsed"]: the collapsed mesh beside the one it was made from."""
+    b = t["before"]
+    return [f"collapsed mesh: {t['collapses']} collapses of edges below {t['min_edge']:g} in {t['rounds']} rounds" + ("" if t["converged"] else " (not converged)")
+            + f", {t['guarded']} short edges guarded; {b['vertices']} -> {t['vertices']} vertices, {b['faces']} -> {t['faces']} faces",
+            f"collapsed mesh, triangle quality: smallest {t['quality_before'][0]:.4f} -> {t['quality'][0]:.4f}, median {t['quality_before'][1]:.4f} -> "
+            f"{t['quality'][1]:.4f}",
+            f"collapsed mesh, face colours baked again: mean PSNR {b['mean_psnr']:.2f} -> {t['mean_psnr']:.2f} dB, mean SSIM {b['mean_ssim']:.4f} -> "
+            f"{t['mean_ssim']:.4f} (before: the mesh behind the other steps)"]
+
+
 def flip_edges_report(s):
     """The lines --flip-edges prints for mesh_scores(...)["welded"]["split"]: s["flipped"] beside the unflipped split mesh."""
     t = s["flipped"]
@@ -748,6 +772,10 @@ if __name__ == "__main__":
     ap.add_argument("--split-edges", type=float, default=None, metavar="L", help="with --weld-mesh: split the welded mesh until no edge is longer than L "
                                                                                  "(diff_recon_hip.split_fused), bake the face colours again and print the face "
                                                                                  "count and PSNR / SSIM before and after")
+    ap.add_argument("--collapse-edges", type=float, default=None, metavar="L",
+                    help="with --weld-mesh: collapse the edges shorter than L of the welded mesh, behind --split-edges and --flip-edges where they "
+                         "are given (diff_recon_hip.collapse_fused), bake the face colours again and print rounds, collapses, triangle quality "
+                         "and PSNR / SSIM beside the mesh before")
     ap.add_argument("--flip-edges", action="store_true", help="with --split-edges: flip the edges of the split mesh toward the Delaunay condition "
                                                               "(diff_recon_hip.flip_fused), bake the face colours again and print rounds, flips, "
                                                               "triangle quality and PSNR / SSIM beside the unflipped mesh")
@@ -799,6 +827,8 @@ if __name__ == "__main__":
     a = ap.parse_args()
     if a.split_edges is not None and a.weld_mesh is None:
         ap.error("--split-edges splits the welded mesh of --weld-mesh")
+    if a.collapse_edges is not None and a.weld_mesh is None:
+        ap.error("--collapse-edges collapses the welded mesh of --weld-mesh")
     if a.flip_edges and a.split_edges is None:
         ap.error("--flip-edges flips the split mesh of --split-edges")
     if a.split_edges is not None and not (a.split_edges > 0 and math.isfinite(a.split_edges)):
@@ -869,7 +899,7 @@ if __name__ == "__main__":
                           surface=a.eval_surface, visible=a.eval_visible, extract=a.extract_mesh, extract_color=a.extract_color, simplify=a.simplify_mesh,
                           min_piece=a.min_piece, smooth=a.smooth_mesh, fill=a.fill_holes, split=a.split_nonmanifold, orient=a.orient_faces,
                           texture=a.bake_texture, out=a.out, remesh=a.remesh, remesh_method=a.remesh_method,
-                          check_intersections=a.check_intersections, split_edges=a.split_edges, flip_edges=a.flip_edges)
+                          check_intersections=a.check_intersections, split_edges=a.split_edges, flip_edges=a.flip_edges, collapse_edges=a.collapse_edges)
         for v, (p_, s_) in enumerate(zip(res["psnr"], res["ssim"])):
             print(f"  opaque mesh, view {v}: PSNR {p_:.2f} dB  SSIM {s_:.4f}")
         print(f"opaque mesh of {m._vertex.shape[0]} triangles: mean PSNR {res['mean_psnr']:.2f} dB, mean SSIM {res['mean_ssim']:.4f} over {len(res['psnr'])} views")
@@ -888,6 +918,9 @@ if __name__ == "__main__":
                     print(line)
             if a.split_edges is not None:
                 for line in split_edges_report(res["welded"]["split"]) + (flip_edges_report(res["welded"]["split"]) if a.flip_edges else []):
+                    print(line)
+            if a.collapse_edges is not None:
+                for line in collapse_edges_report(res["welded"]["collapsed"]):
                     print(line)
         if a.eval_geometry is not None:
             for line in geometry_report(res["geometry"]):

@@ -538,3 +538,24 @@ def bind_flip(lib):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     return lib
+
+
+# include/ts_collapse.h: the whole C ABI of diff_recon_hip/libts_collapse.so, the eighteenth library (diff_recon_hip/mesh_collapse.py loads and binds it)
+COLLAPSE_SIGNATURES = {
+    "tsp_last_error": (C.c_char_p, []),
+    "tsp_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "tsp_collapse": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32, C.c_float, _vp, C.c_float, C.c_float, C.c_uint32, _vp, _vp, _vp,
+                               _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+}
+
+
+def bind_collapse(lib):
+    """Sets restype and argtypes of every function of include/ts_collapse.h on `lib` (a ctypes.CDLL of libts_collapse.so); a library that
+    lacks one is refused."""
+    missing = [name for name in COLLAPSE_SIGNATURES if not hasattr(lib, name)]
+    if missing:
+        raise ImportError(f"{getattr(lib, '_name', lib)} does not export {', '.join(missing)}: rebuild it with `python triangle-splatting_amd/build.py`")
+    for name, (restype, argtypes) in COLLAPSE_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return lib

@@ -28,6 +28,10 @@ A "ground truth" is rendered from a hidden set of triangles from several cameras
                                                         then split the welded mesh until no edge is longer than L (diff_recon_hip.split_fused), start
                                                         the pieces from their parents' colours, bake the face colours again (bake_face_colors) and
                                                         print the face count and PSNR / SSIM before and after
+    python examples/train_synthetic.py --eval-mesh (--weld-mesh EPS | --extract-mesh RES [--remesh RES]) --decimate-faces N
+                                                        decimate the mesh behind the other steps to N faces by quadric-error collapses
+                                                        (diff_recon_hip.decimate_fused / decimate_mesh) and print faces before and after, rounds,
+                                                        whether N was reached and triangle quality; the welded mesh's face colours are baked again
     python examples/train_synthetic.py --eval-mesh --weld-mesh EPS [--split-edges L] [--flip-edges] --collapse-edges L
                                                         collapse the edges shorter than L behind the other steps (diff_recon_hip.collapse_fused),
                                                         bake the face colours again and print rounds, collapses, vertices and faces, triangle
@@ -263,7 +267,7 @@ def train(rasterizer="2D", iters=200, triangles=20000, width=256, height=192, se
 
 def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, height=192, seed=0, views=2, refine=False, weld=None, geometry=None, surface=None,
                 visible=False, extract=None, extract_color=False, simplify=None, min_piece=0, smooth=None, fill=None, split=False, orient=None, texture=None,
-                out=None, remesh=None, remesh_method="rays", check_intersections=False, split_edges=None, flip_edges=False, collapse_edges=None):
+                out=None, remesh=None, remesh_method="rays", check_intersections=False, split_edges=None, flip_edges=False, collapse_edges=None, decimate_faces=None):
     """PSNR / SSIM of the model's opaque mesh -- mesh_from_triangles: one colour per face from the DC coefficients, back faces as reversed
     twins, the soup saveGLB writes -- against the hidden targets of train() called with the same arguments (diff_recon_hip.evaluate_mesh).
     refine: the result also holds "refined", the same scores (plus "kept" and "triangles") of the mesh after a census over these views
@@ -319,7 +323,13 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
     differ in resolution alone.  No other entry changes.
     flip_edges (with split_edges): "split" also holds "flipped": the split mesh after diff_recon_hip.flip_fused, baked the same way -- its
     scores, "rounds", "flips", "guarded", "converged", "slots" (the face slots rewritten) and "quality" / "quality_before": the smallest and
-    the median diff_recon_hip.triangle_quality.  No other entry changes."""
+    the median diff_recon_hip.triangle_quality.  No other entry changes.
+    decimate_faces = N: with weld, "welded" also holds "decimated": the mesh behind the other steps (the collapse included) decimated to N faces
+    by quadric-error collapses (diff_recon_hip.decimate_fused), baked again -- its scores, "faces", "vertices", "rounds", "collapses",
+    "reached", "quality" / "quality_before" and "before".  A welded soup has only boundary edges: nothing collapses there and "reached" is
+    False.  With extract, "fused" also holds "decimated": the same of the finished fused mesh (the remeshed one with remesh; "of" says which)
+    through diff_recon_hip.decimate_mesh, with "to_source" = mesh_surface_distance to the mesh it came from instead of image scores (None for
+    a mesh without faces).  No other entry changes."""
     _, _, cams, gts, kw, _, _ = _setup(rasterizer, iters, triangles, width, height, seed, views, 0.0, False, False)
     for cam, gt in zip(cams, gts):
         cam.gt_image = gt
@@ -367,6 +377,14 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
             res["welded"]["collapsed"] = dict(score(coarse), min_edge=float(collapse_edges), rounds=t["rounds"], collapses=t["collapsed"],
                                               guarded=t["guarded"], converged=t["converged"], faces=int(coarse.faces.shape[0]),
                                               vertices=int(coarse.vertices.shape[0]), quality=quality(coarse), quality_before=quality(last),
+                                              before=dict(score(last), faces=int(last.faces.shape[0]), vertices=int(last.vertices.shape[0])))
+            last = coarse
+        if decimate_faces is not None:
+            small = D.decimate_fused(last, target_faces=int(decimate_faces))
+            t = small.stats["decimate"]
+            res["welded"]["decimated"] = dict(score(small), target_faces=int(decimate_faces), rounds=t["rounds"], collapses=t["collapsed"],
+                                              reached=t["reached"], faces=int(small.faces.shape[0]), vertices=int(small.vertices.shape[0]),
+                                              quality=quality(small), quality_before=quality(last), of="welded",
                                               before=dict(score(last), faces=int(last.faces.shape[0]), vertices=int(last.vertices.shape[0])))
     if geometry is not None or surface is not None:
         target = torch.from_numpy(np.ascontiguousarray(synthetic.scene(triangles, width, height, 2, seed=seed, edge_px=10.0)["vertex"])).to(m._vertex.device)
@@ -470,6 +488,21 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
                     res["fused"]["remeshed"]["intersections"] = D.self_intersection_report((again.vertices, again.faces))
             else:
                 res["fused"]["remeshed"] = None
+        if decimate_faces is not None:
+            source, of = (again, "remeshed") if remesh is not None and done.faces.shape[0] else (done, "fused")
+            if source.faces.shape[0]:
+                small = D.decimate_mesh(source.vertices, source.faces, target_faces=int(decimate_faces))
+                def shape(mesh):  # [smallest, median] triangle quality; a face that takes no part counts as degenerate
+                    q = D.triangle_quality(mesh.vertices, mesh.faces).nan_to_num(0.0)
+                    return [float(q.min()), float(q.median())]
+                res["fused"]["decimated"] = dict(target_faces=int(decimate_faces), rounds=small.stats["rounds"], collapses=small.stats["collapsed"],
+                                                 reached=small.reached, faces=int(small.faces.shape[0]), vertices=int(small.vertices.shape[0]),
+                                                 quality=shape(small), quality_before=shape(source), of=of,
+                                                 before=dict(faces=int(source.faces.shape[0]), vertices=int(source.vertices.shape[0])),
+                                                 to_source=D.mesh_surface_distance((small.vertices, small.faces), (source.vertices, source.faces), samples,
+                                                                                   seed=seed) if small.faces.shape[0] else None)
+            else:
+                res["fused"]["decimated"] = None
     return res
 
 
@@ -601,6 +634,28 @@ def collapse_edges_report(t):
             f"{t['quality'][1]:.4f}",
             f"collapsed mesh, face colours baked again: mean PSNR {b['mean_psnr']:.2f} -> {t['mean_psnr']:.2f} dB, mean SSIM {b['mean_ssim']:.4f} -> "
             f"{t['mean_ssim']:.4f} (before: the mesh behind the other steps)"]
+
+
+def decimate_faces_report(t):
+    """The lines --decimate-faces prints for a "decimated" entry of mesh_scores(...): of "welded" (with image scores) or of "fused"."""
+    if t is None:
+        return ["decimated mesh: no surface was extracted, nothing to decimate"]
+    b = t["before"]
+    how = f"reached {t['target_faces']} faces" if t["reached"] else f"did NOT reach {t['target_faces']} faces"
+    why = " (every edge of a soup is a boundary edge: all vertices are held, nothing collapses)" if t["collapses"] == 0 and not t["reached"] else ""
+    lines = [f"decimated {t['of']} mesh: {t['collapses']} quadric-error collapses in {t['rounds']} rounds, {how}{why}; "
+             f"{b['vertices']} -> {t['vertices']} vertices, {b['faces']} -> {t['faces']} faces",
+             f"decimated {t['of']} mesh, triangle quality: smallest {t['quality_before'][0]:.4f} -> {t['quality'][0]:.4f}, median "
+             f"{t['quality_before'][1]:.4f} -> {t['quality'][1]:.4f}"]
+    if "mean_psnr" in t:
+        lines.append(f"decimated {t['of']} mesh, face colours baked again: mean PSNR {b['mean_psnr']:.2f} -> {t['mean_psnr']:.2f} dB, mean SSIM "
+                     f"{b['mean_ssim']:.4f} -> {t['mean_ssim']:.4f} (before: the mesh behind the other steps)")
+    else:
+        g = t["to_source"]
+        lines.append(f"decimated {t['of']} mesh against the mesh it came from: " +
+                     (f"accuracy {g['accuracy']:.4g}, completeness {g['completeness']:.4g}, Chamfer {g['chamfer']:.4g}, Hausdorff {g['hausdorff']:.4g}"
+                      if g is not None else "no face is left"))
+    return lines
 
 
 def flip_edges_report(s):
@@ -776,6 +831,11 @@ if __name__ == "__main__":
                     help="with --weld-mesh: collapse the edges shorter than L of the welded mesh, behind --split-edges and --flip-edges where they "
                          "are given (diff_recon_hip.collapse_fused), bake the face colours again and print rounds, collapses, triangle quality "
                          "and PSNR / SSIM beside the mesh before")
+    ap.add_argument("--decimate-faces", type=int, default=None, metavar="N",
+                    help="with --weld-mesh: decimate the welded mesh, behind --split-edges, --flip-edges and --collapse-edges where they are given, to "
+                         "N faces by quadric-error collapses (diff_recon_hip.decimate_fused) and bake the face colours again; with --extract-mesh: the "
+                         "same of the finished fused mesh, behind --remesh where it is given (diff_recon_hip.decimate_mesh); print faces before and "
+                         "after, rounds, whether N was reached, triangle quality and PSNR / SSIM or the distance to the mesh before")
     ap.add_argument("--flip-edges", action="store_true", help="with --split-edges: flip the edges of the split mesh toward the Delaunay condition "
                                                               "(diff_recon_hip.flip_fused), bake the face colours again and print rounds, flips, "
                                                               "triangle quality and PSNR / SSIM beside the unflipped mesh")
@@ -829,6 +889,10 @@ if __name__ == "__main__":
         ap.error("--split-edges splits the welded mesh of --weld-mesh")
     if a.collapse_edges is not None and a.weld_mesh is None:
         ap.error("--collapse-edges collapses the welded mesh of --weld-mesh")
+    if a.decimate_faces is not None and a.weld_mesh is None and a.extract_mesh is None:
+        ap.error("--decimate-faces decimates the mesh of --weld-mesh or of --extract-mesh")
+    if a.decimate_faces is not None and a.decimate_faces < 0:
+        ap.error("--decimate-faces needs a face count >= 0")
     if a.flip_edges and a.split_edges is None:
         ap.error("--flip-edges flips the split mesh of --split-edges")
     if a.split_edges is not None and not (a.split_edges > 0 and math.isfinite(a.split_edges)):
@@ -899,7 +963,8 @@ if __name__ == "__main__":
                           surface=a.eval_surface, visible=a.eval_visible, extract=a.extract_mesh, extract_color=a.extract_color, simplify=a.simplify_mesh,
                           min_piece=a.min_piece, smooth=a.smooth_mesh, fill=a.fill_holes, split=a.split_nonmanifold, orient=a.orient_faces,
                           texture=a.bake_texture, out=a.out, remesh=a.remesh, remesh_method=a.remesh_method,
-                          check_intersections=a.check_intersections, split_edges=a.split_edges, flip_edges=a.flip_edges, collapse_edges=a.collapse_edges)
+                          check_intersections=a.check_intersections, split_edges=a.split_edges, flip_edges=a.flip_edges, collapse_edges=a.collapse_edges,
+                          decimate_faces=a.decimate_faces)
         for v, (p_, s_) in enumerate(zip(res["psnr"], res["ssim"])):
             print(f"  opaque mesh, view {v}: PSNR {p_:.2f} dB  SSIM {s_:.4f}")
         print(f"opaque mesh of {m._vertex.shape[0]} triangles: mean PSNR {res['mean_psnr']:.2f} dB, mean SSIM {res['mean_ssim']:.4f} over {len(res['psnr'])} views")
@@ -921,6 +986,9 @@ if __name__ == "__main__":
                     print(line)
             if a.collapse_edges is not None:
                 for line in collapse_edges_report(res["welded"]["collapsed"]):
+                    print(line)
+            if a.decimate_faces is not None:
+                for line in decimate_faces_report(res["welded"]["decimated"]):
                     print(line)
         if a.eval_geometry is not None:
             for line in geometry_report(res["geometry"]):
@@ -971,3 +1039,6 @@ if __name__ == "__main__":
                 if a.check_intersections and res["fused"]["remeshed"] is not None:
                     for line in intersections_report(res["fused"]["remeshed"]["intersections"], "remeshed"):
                         print(line)
+            if a.decimate_faces is not None:
+                for line in decimate_faces_report(res["fused"]["decimated"]):
+                    print(line)

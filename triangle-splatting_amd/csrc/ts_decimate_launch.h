@@ -1,0 +1,11 @@
+// ts_decimate_launch.h -- the launchers of mesh_decimate.hip as api_decimate.hip calls them (include/ts_decimate.h is the C ABI over them).
+#pragma once
+#include "ts2d_common.h"
+size_t ts_decimate_workspace_bytes(int V, int F);
+hipError_t ts_decimate_quadrics(int V, int F, const float *vertices, const int32_t *faces, const uint8_t *keep, double *out_quadrics, void *ws,
+                                hipStream_t s);
+hipError_t ts_decimate_round(int V, int F, const float *vertices, const int32_t *faces, const uint8_t *keep, const uint8_t *pinned,
+                             const double *quadrics, float max_cost, int max_collapses, float max_edge, float min_cos, uint32_t seed,
+                             int32_t *out_faces, uint8_t *out_keep, int32_t *vertex_target, double *out_quadrics, int32_t *edge_vertices,
+                             uint8_t *edge_state, int32_t *edge_removed, uint8_t *edge_guard, double *edge_cost, unsigned long long *totals,
+                             void *ws, hipStream_t s);

@@ -559,3 +559,25 @@ def bind_collapse(lib):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     return lib
+
+
+# include/ts_decimate.h: the whole C ABI of diff_recon_hip/libts_decimate.so, the nineteenth library (diff_recon_hip/mesh_decimate.py loads and binds it)
+DECIMATE_SIGNATURES = {
+    "tsz_last_error": (C.c_char_p, []),
+    "tsz_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "tsz_vertex_quadrics": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "tsz_decimate": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_float, C.c_int32, C.c_float, C.c_float, C.c_uint32, _vp, _vp, _vp,
+                               _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+}
+
+
+def bind_decimate(lib):
+    """Sets restype and argtypes of every function of include/ts_decimate.h on `lib` (a ctypes.CDLL of libts_decimate.so); a library that
+    lacks one is refused."""
+    missing = [name for name in DECIMATE_SIGNATURES if not hasattr(lib, name)]
+    if missing:
+        raise ImportError(f"{getattr(lib, '_name', lib)} does not export {', '.join(missing)}: rebuild it with `python triangle-splatting_amd/build.py`")
+    for name, (restype, argtypes) in DECIMATE_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return lib

@@ -9,7 +9,19 @@
  * one workgroup per 1024-point box, candidate boxes staged through LDS and pruned per workgroup and per lane).
  * All pointers are device pointers; calls enqueue on `stream`, never allocate and never synchronise, so they can be captured in a graph.
  * Purity (DESIGN.md "Purity of the entry points"): the workspace may hold anything on entry; all P elements of mean_dist2 / nearest are
- * overwritten whatever they held (P == 0 writes nothing); no byte outside tsk_workspace_bytes(P) or the P outputs is written. */
+ * overwritten whatever they held (P == 0 writes nothing); no byte outside tsk_workspace_bytes(P) or the P outputs is written.
+ *
+ * Pinned bit for bit by tests/test_knn_gpu.py against tests/ref_knn.py, on inputs whose every distance is exact in fp32:
+ *   - the sorted order is that of the reference: the bounding box always contains the ORIGIN, a zero extent (planar, collinear
+ *     clouds) quantises to cell 0 on that axis, equal codes keep index order;
+ *   - a point with a NaN or infinite coordinate takes no part as a candidate: its distance to anything is NaN or +inf and never
+ *     compares closer than the initial FLT_MAX.  The answers of the other points are those of the cloud without it, with one
+ *     proviso on the ORDER: NaN is ignored by the bounding box, an infinite coordinate enters it;
+ *   - such a point itself gets +inf from tsk_mean_dist3 (three missing neighbours) and its own index from tsk_nearest_other;
+ *   - an infinite coordinate makes the Morton grid degenerate on its axis (every point lands in cell 0 there): the answers stay
+ *     exact, ties fall to index order as far as that axis decided them, and the search runs slowly (boxes overlap, little is pruned).
+ * Outside the contract: coordinates whose squared differences exceed FLT_MAX.  A candidate whose fp32 squared distance overflows
+ * compares as no closer than the initial FLT_MAX, as in the reference, and is not found. */
 #ifndef TS_KNN_H
 #define TS_KNN_H
 

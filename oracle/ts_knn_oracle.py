@@ -6,7 +6,14 @@ the oracle is the definition itself, evaluated with scipy's exact k-d tree in fl
     nearest_other(points, g)[i] = argmin_j |p_i - p_j|^2 over j // g != i // g           (simple_knn.cu:189-235)
 Parity status: the reference ships no expected outputs (main.cu:50-75 only prints); its extension built for gfx950
 (oracle/build_ref.py -> oracle/_ref/_refknn_C.so) is compared with the product on the GPU (tests/test_reference_gpu.py:
-distances to 2e-6, indices exactly), which pins the tie rule that this float64 oracle cannot.
+on random clouds distances to 2e-6 and indices exactly; on inputs made of exact ties -- lattices across and far from the
+origin, zero extents, duplicates, a twinned mesh -- indices equal and distances bit-equal).  The tie rule, which this
+float64 oracle cannot state (a k-d tree returns any of the tied candidates), is restated in numpy by tests/ref_knn.py: the
+front half in float32 (origin-seeded box, Morton codes, stable sort) and a brute-force search that picks the first tied
+candidate in (code, index) order.  tests/test_knn_cpu.py holds that reference to this oracle where no tie exists,
+tests/test_knn_gpu.py holds the product to it bit for bit, and test_reference_gpu.py holds both to the reference build.
+Rows with NaN or infinite coordinates are pinned against tests/ref_knn.py only (include/ts_knn.h says what they do); no parity
+with the reference build is claimed there, its bounding-box reductions over NaN depend on their order.
 Only tests/ may import this module.
 """
 from __future__ import annotations

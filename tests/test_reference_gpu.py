@@ -306,6 +306,29 @@ def test_simple_knn_against_the_reference_build(n, g):
     assert np.array_equal(mine, theirs)  # exact search, same tie rule
 
 
+@pytest.mark.parametrize("name,g", [("lattice-6.5", 1), ("lattice-6.5", 3), ("lattice+1000", 1), ("lattice+1000", 3), ("plane0", 4), ("plane5", 4),
+                                    ("copies", 3), ("doubled", 3), ("twinned", 3)])
+def test_simple_knn_ties_against_the_reference_build(name, g):
+    """The inputs of tests/test_knn_gpu.py that consist of exact ties (tests/ref_knn.py: lattices across and far from the origin, zero extents,
+    duplicates, the twinned mesh) through the reference's own kernels: indices equal and distances bit-equal, three ways.  The numpy reference is
+    held to the reference build first: where they disagree on a finite input, it and the product are wrong.  Inputs with NaN or infinite
+    coordinates are left out: the reference's bounding-box reductions over NaN depend on their order, so no parity is claimed there."""
+    import torch
+    import ref_knn as RK
+    from simple_knn import distCUDA2, nearestNeighbor
+    ref = ref_build.load("_refknn_C")
+    pts, r = RK.solve(name, g)
+    assert np.isfinite(pts).all() and (name == "doubled" or (r["ties"] >= 2).mean() >= 0.5)
+    p = torch.from_numpy(np.ascontiguousarray(pts)).cuda()
+    theirs_d = ref.distCUDA2(p).cpu().numpy()
+    theirs = ref.nearestNeighbor(p, g).view(torch.int32).cpu().numpy().astype(np.int64)
+    assert np.array_equal(r["nearest"], theirs), np.nonzero(r["nearest"] != theirs)[0][:5]
+    assert np.array_equal(r["mean3"].view(np.uint32), theirs_d.view(np.uint32))
+    mine = nearestNeighbor(p, g).view(torch.int32).cpu().numpy().astype(np.int64)
+    assert np.array_equal(mine, theirs), np.nonzero(mine != theirs)[0][:5]
+    assert np.array_equal(distCUDA2(p).cpu().numpy().view(np.uint32), theirs_d.view(np.uint32))
+
+
 @pytest.mark.parametrize("seed", range(24))
 def test_random_configurations_against_the_reference_build(seed):
     """The random-configuration sweep of test_fuzz_gpu.py (tiny / ragged images, P < 64, feature mode with 1-3 channels,

@@ -31,7 +31,9 @@ A "ground truth" is rendered from a hidden set of triangles from several cameras
     python examples/train_synthetic.py --eval-mesh (--weld-mesh EPS | --extract-mesh RES [--remesh RES]) --decimate-faces N
                                                         decimate the mesh behind the other steps to N faces by quadric-error collapses
                                                         (diff_recon_hip.decimate_fused / decimate_mesh) and print faces before and after, rounds,
-                                                        whether N was reached and triangle quality; the welded mesh's face colours are baked again
+                                                        whether N was reached and triangle quality; the welded mesh's face colours are baked again;
+                                                        --decimate-placement optimal contracts edges instead and moves every survivor to the
+                                                        quadric's minimum (diff_recon_hip.contract_fused / contract_mesh)
     python examples/train_synthetic.py --eval-mesh --weld-mesh EPS [--split-edges L] [--flip-edges] --collapse-edges L
                                                         collapse the edges shorter than L behind the other steps (diff_recon_hip.collapse_fused),
                                                         bake the face colours again and print rounds, collapses, vertices and faces, triangle
@@ -267,7 +269,7 @@ def train(rasterizer="2D", iters=200, triangles=20000, width=256, height=192, se
 
 def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, height=192, seed=0, views=2, refine=False, weld=None, geometry=None, surface=None,
                 visible=False, extract=None, extract_color=False, simplify=None, min_piece=0, smooth=None, fill=None, split=False, orient=None, texture=None,
-                out=None, remesh=None, remesh_method="rays", check_intersections=False, split_edges=None, flip_edges=False, collapse_edges=None, decimate_faces=None):
+                out=None, remesh=None, remesh_method="rays", check_intersections=False, split_edges=None, flip_edges=False, collapse_edges=None, decimate_faces=None, decimate_placement="vertex"):
     """PSNR / SSIM of the model's opaque mesh -- mesh_from_triangles: one colour per face from the DC coefficients, back faces as reversed
     twins, the soup saveGLB writes -- against the hidden targets of train() called with the same arguments (diff_recon_hip.evaluate_mesh).
     refine: the result also holds "refined", the same scores (plus "kept" and "triangles") of the mesh after a census over these views
@@ -329,7 +331,8 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
     "reached", "quality" / "quality_before" and "before".  A welded soup has only boundary edges: nothing collapses there and "reached" is
     False.  With extract, "fused" also holds "decimated": the same of the finished fused mesh (the remeshed one with remesh; "of" says which)
     through diff_recon_hip.decimate_mesh, with "to_source" = mesh_surface_distance to the mesh it came from instead of image scores (None for
-    a mesh without faces).  No other entry changes."""
+    a mesh without faces).  decimate_placement = "optimal": the same through diff_recon_hip.contract_fused / contract_mesh, the survivors placed at
+    the quadric's minimum; the entry then also holds "placement": "optimal".  No other entry changes."""
     _, _, cams, gts, kw, _, _ = _setup(rasterizer, iters, triangles, width, height, seed, views, 0.0, False, False)
     for cam, gt in zip(cams, gts):
         cam.gt_image = gt
@@ -380,12 +383,18 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
                                               before=dict(score(last), faces=int(last.faces.shape[0]), vertices=int(last.vertices.shape[0])))
             last = coarse
         if decimate_faces is not None:
-            small = D.decimate_fused(last, target_faces=int(decimate_faces))
-            t = small.stats["decimate"]
+            if decimate_placement == "optimal":  # edge contraction: the survivors move to the quadric's minimum (diff_recon_hip.contract_fused)
+                small = D.contract_fused(last, target_faces=int(decimate_faces))
+                t = small.stats["contract"]
+            else:
+                small = D.decimate_fused(last, target_faces=int(decimate_faces))
+                t = small.stats["decimate"]
             res["welded"]["decimated"] = dict(score(small), target_faces=int(decimate_faces), rounds=t["rounds"], collapses=t["collapsed"],
                                               reached=t["reached"], faces=int(small.faces.shape[0]), vertices=int(small.vertices.shape[0]),
                                               quality=quality(small), quality_before=quality(last), of="welded",
                                               before=dict(score(last), faces=int(last.faces.shape[0]), vertices=int(last.vertices.shape[0])))
+            if decimate_placement == "optimal":
+                res["welded"]["decimated"]["placement"] = "optimal"
     if geometry is not None or surface is not None:
         target = torch.from_numpy(np.ascontiguousarray(synthetic.scene(triangles, width, height, 2, seed=seed, edge_px=10.0)["vertex"])).to(m._vertex.device)
         edges = (target - target.roll(1, dims=1)).norm(dim=2)  # the hidden scene of _setup: every draw comes from the seeded generator
@@ -491,7 +500,8 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
         if decimate_faces is not None:
             source, of = (again, "remeshed") if remesh is not None and done.faces.shape[0] else (done, "fused")
             if source.faces.shape[0]:
-                small = D.decimate_mesh(source.vertices, source.faces, target_faces=int(decimate_faces))
+                small = (D.contract_mesh if decimate_placement == "optimal" else D.decimate_mesh)(source.vertices, source.faces,
+                                                                                                  target_faces=int(decimate_faces))
                 def shape(mesh):  # [smallest, median] triangle quality; a face that takes no part counts as degenerate
                     q = D.triangle_quality(mesh.vertices, mesh.faces).nan_to_num(0.0)
                     return [float(q.min()), float(q.median())]
@@ -501,6 +511,8 @@ def mesh_scores(m, rasterizer="2D", iters=200, triangles=20000, width=256, heigh
                                                  before=dict(faces=int(source.faces.shape[0]), vertices=int(source.vertices.shape[0])),
                                                  to_source=D.mesh_surface_distance((small.vertices, small.faces), (source.vertices, source.faces), samples,
                                                                                    seed=seed) if small.faces.shape[0] else None)
+                if decimate_placement == "optimal":
+                    res["fused"]["decimated"]["placement"] = "optimal"
             else:
                 res["fused"]["decimated"] = None
     return res
@@ -643,7 +655,8 @@ def decimate_faces_report(t):
     b = t["before"]
     how = f"reached {t['target_faces']} faces" if t["reached"] else f"did NOT reach {t['target_faces']} faces"
     why = " (every edge of a soup is a boundary edge: all vertices are held, nothing collapses)" if t["collapses"] == 0 and not t["reached"] else ""
-    lines = [f"decimated {t['of']} mesh: {t['collapses']} quadric-error collapses in {t['rounds']} rounds, {how}{why}; "
+    what = "quadric-error contractions, survivors placed at the quadric's minimum," if t.get("placement") == "optimal" else "quadric-error collapses"
+    lines = [f"decimated {t['of']} mesh: {t['collapses']} {what} in {t['rounds']} rounds, {how}{why}; "
              f"{b['vertices']} -> {t['vertices']} vertices, {b['faces']} -> {t['faces']} faces",
              f"decimated {t['of']} mesh, triangle quality: smallest {t['quality_before'][0]:.4f} -> {t['quality'][0]:.4f}, median "
              f"{t['quality_before'][1]:.4f} -> {t['quality'][1]:.4f}"]
@@ -836,6 +849,10 @@ if __name__ == "__main__":
                          "N faces by quadric-error collapses (diff_recon_hip.decimate_fused) and bake the face colours again; with --extract-mesh: the "
                          "same of the finished fused mesh, behind --remesh where it is given (diff_recon_hip.decimate_mesh); print faces before and "
                          "after, rounds, whether N was reached, triangle quality and PSNR / SSIM or the distance to the mesh before")
+    ap.add_argument("--decimate-placement", choices=("vertex", "optimal"), default="vertex",
+                    help="with --decimate-faces: vertex (the default) keeps the survivor of every collapse where it was (decimate_fused / "
+                         "decimate_mesh); optimal contracts edges and places the survivor at the regularised minimum of the edge's quadric "
+                         "(diff_recon_hip.contract_fused / contract_mesh), blending vertex colours by how far it went")
     ap.add_argument("--flip-edges", action="store_true", help="with --split-edges: flip the edges of the split mesh toward the Delaunay condition "
                                                               "(diff_recon_hip.flip_fused), bake the face colours again and print rounds, flips, "
                                                               "triangle quality and PSNR / SSIM beside the unflipped mesh")
@@ -891,6 +908,8 @@ if __name__ == "__main__":
         ap.error("--collapse-edges collapses the welded mesh of --weld-mesh")
     if a.decimate_faces is not None and a.weld_mesh is None and a.extract_mesh is None:
         ap.error("--decimate-faces decimates the mesh of --weld-mesh or of --extract-mesh")
+    if a.decimate_placement != "vertex" and a.decimate_faces is None:
+        ap.error("--decimate-placement chooses how --decimate-faces places the survivors")
     if a.decimate_faces is not None and a.decimate_faces < 0:
         ap.error("--decimate-faces needs a face count >= 0")
     if a.flip_edges and a.split_edges is None:
@@ -964,7 +983,7 @@ if __name__ == "__main__":
                           min_piece=a.min_piece, smooth=a.smooth_mesh, fill=a.fill_holes, split=a.split_nonmanifold, orient=a.orient_faces,
                           texture=a.bake_texture, out=a.out, remesh=a.remesh, remesh_method=a.remesh_method,
                           check_intersections=a.check_intersections, split_edges=a.split_edges, flip_edges=a.flip_edges, collapse_edges=a.collapse_edges,
-                          decimate_faces=a.decimate_faces)
+                          decimate_faces=a.decimate_faces, decimate_placement=a.decimate_placement)
         for v, (p_, s_) in enumerate(zip(res["psnr"], res["ssim"])):
             print(f"  opaque mesh, view {v}: PSNR {p_:.2f} dB  SSIM {s_:.4f}")
         print(f"opaque mesh of {m._vertex.shape[0]} triangles: mean PSNR {res['mean_psnr']:.2f} dB, mean SSIM {res['mean_ssim']:.4f} over {len(res['psnr'])} views")

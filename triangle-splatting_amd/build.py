@@ -16,12 +16,13 @@ libts_overlap.so (include/ts_overlap.h: the triangle-overlap query, self-interse
 libts_subdivide.so (include/ts_subdivide.h: the edge table and the conforming split at the midpoints of marked edges of diff_recon_hip/mesh_subdivide.py, SUBDIVIDE_SOURCES + the radix_sort object) and
 libts_flip.so (include/ts_flip.h: the round of edge flips toward the Delaunay condition of diff_recon_hip/mesh_flip.py, FLIP_SOURCES + the radix_sort object) and
 libts_collapse.so (include/ts_collapse.h: the round of half-edge collapses of short edges of diff_recon_hip/mesh_collapse.py, COLLAPSE_SOURCES + the radix_sort object) and
-libts_decimate.so (include/ts_decimate.h: the vertex quadrics and the round of quadric-error collapses under a budget of diff_recon_hip/mesh_decimate.py, DECIMATE_SOURCES + the radix_sort object).
+libts_decimate.so (include/ts_decimate.h: the vertex quadrics and the round of quadric-error collapses under a budget of diff_recon_hip/mesh_decimate.py, DECIMATE_SOURCES + the radix_sort object) and
+libts_contract.so (include/ts_contract.h: the round of quadric-error edge contractions that place the survivor, under a budget, of diff_recon_hip/mesh_contract.py, CONTRACT_SOURCES + the radix_sort object).
 
     python triangle-splatting_amd/build.py [--force] [--verbose] [--lab]
     python triangle-splatting_amd/build.py --variant TAG [--lab] [--all "FLAGS"] [--unit NAME="FLAGS" ...]
 
-Output: triangle-splatting_amd/diff_triangle_rasterization_2D/libts2d.so, triangle-splatting_amd/diff_recon_hip/libts_geom.so, libts_bvh.so, libts_ray.so, libts_volume.so, libts_color.so, libts_simplify.so, libts_smooth.so, libts_holes.so, libts_manifold.so, libts_orient.so, libts_atlas.so, libts_inside.so, libts_winding.so, libts_overlap.so, libts_subdivide.so, libts_flip.so, libts_collapse.so and libts_decimate.so, and the torch extension bindings/_ts2d_torch_C.so (bindings/
+Output: triangle-splatting_amd/diff_triangle_rasterization_2D/libts2d.so, triangle-splatting_amd/diff_recon_hip/libts_geom.so, libts_bvh.so, libts_ray.so, libts_volume.so, libts_color.so, libts_simplify.so, libts_smooth.so, libts_holes.so, libts_manifold.so, libts_orient.so, libts_atlas.so, libts_inside.so, libts_winding.so, libts_overlap.so, libts_subdivide.so, libts_flip.so, libts_collapse.so, libts_decimate.so and libts_contract.so, and the torch extension bindings/_ts2d_torch_C.so (bindings/
 ts2d_torch_ext.cpp, linked -lts2d with an $ORIGIN-relative runpath), both git-ignored.  Every library carries the soname libts2d.so, so the
 extension's dependency on libts2d.so is met by whichever of them _C.py loaded first (TS2D_LIBRARY_PATH).
 --lab builds tools/bin/libts2d_lab.so as well: the same objects + the test hooks of tools/lab/lab_hooks.hip and api.hip compiled with
@@ -199,10 +200,16 @@ DECIMATE_SOURCES = {  # libts_decimate.so only (include/ts_decimate.h): a ninete
 }
 DECIMATE_SHARED = ["radix_sort"]  # the sorts of the half-edge and corner records and the three of the ranking
 DECIMATE_LIB = os.path.join(HERE, "diff_recon_hip", "libts_decimate.so")
+CONTRACT_SOURCES = {  # libts_contract.so only (include/ts_contract.h): a twentieth product library, the export lists of the other nineteen are closed
+    "mesh_contract.hip": ["-ffp-contract=off"],  # the edge quadric, the solve, p* and the guards at p*: every fp64 operation rounds
+    "api_contract.hip": [],                      # its C ABI and its own error text
+}
+CONTRACT_SHARED = ["radix_sort"]  # the sorts of the half-edge and corner records and the three of the ranking
+CONTRACT_LIB = os.path.join(HERE, "diff_recon_hip", "libts_contract.so")
 BIN_DIR = os.path.join(os.path.dirname(HERE), "tools", "bin")
 LAB_LIB = os.path.join(BIN_DIR, "libts2d_lab.so")
 LAB_SRC = os.path.join(os.path.dirname(HERE), "tools", "lab")  # lab_hooks.hip: the test hooks, outside the product's csrc/; it includes csrc's headers (-I)
-HEADERS = ["ts2d_common.h", "ts2d_radix.h", "ts2d_api.h", "ts_knn_front.h", "ts_weld_launch.h", "ts_geom_launch.h", "ts_bvh_launch.h", "ts_bvh_layout.h", "ts_bvh_walk.h", "ts_ray_launch.h", "ts_volume_launch.h", "ts_color_launch.h", "ts_simplify_launch.h", "ts_smooth_launch.h", "ts_holes_launch.h", "ts_manifold_launch.h", "ts_orient_launch.h", "ts_atlas_launch.h", "ts_inside_launch.h", "ts_winding_launch.h", "ts_overlap_launch.h", "ts_subdivide_launch.h", "ts_flip_launch.h", "ts_collapse_launch.h", "ts_collapse_round.h", "ts_decimate_launch.h", "ts_ray_tests.h", "ts_mesh_bary.h", "ts_union_find.h", "ts_mesh_common.h", "ts_mesh_scan.h", "ts_mesh_runs.h", "ts_mesh_edges.h", "ts_mesh_edge_ids.h", "ts2d_lab.h", "ts2d_math.h", "ts2d_wave.h", "ts2d_group.h", "ts2d_support.h", "ts2d_sh.h", "ts2d_stage.h", "ts2d_preprocess_launch.h", "ts2d_imgops.h", "ts2d_select.h", "ts2d_tri.h", os.path.join("..", "..", "include", "ts2d.h"),
+HEADERS = ["ts2d_common.h", "ts2d_radix.h", "ts2d_api.h", "ts_knn_front.h", "ts_weld_launch.h", "ts_geom_launch.h", "ts_bvh_launch.h", "ts_bvh_layout.h", "ts_bvh_walk.h", "ts_ray_launch.h", "ts_volume_launch.h", "ts_color_launch.h", "ts_simplify_launch.h", "ts_smooth_launch.h", "ts_holes_launch.h", "ts_manifold_launch.h", "ts_orient_launch.h", "ts_atlas_launch.h", "ts_inside_launch.h", "ts_winding_launch.h", "ts_overlap_launch.h", "ts_subdivide_launch.h", "ts_flip_launch.h", "ts_collapse_launch.h", "ts_collapse_round.h", "ts_decimate_launch.h", "ts_contract_launch.h", "ts_ray_tests.h", "ts_mesh_bary.h", "ts_union_find.h", "ts_mesh_common.h", "ts_mesh_scan.h", "ts_mesh_runs.h", "ts_mesh_edges.h", "ts_mesh_edge_ids.h", "ts2d_lab.h", "ts2d_math.h", "ts2d_wave.h", "ts2d_group.h", "ts2d_support.h", "ts2d_sh.h", "ts2d_stage.h", "ts2d_preprocess_launch.h", "ts2d_imgops.h", "ts2d_select.h", "ts2d_tri.h", os.path.join("..", "..", "include", "ts2d.h"),
            os.path.join("..", "..", "include", "ts_loss.h"),
            os.path.join("..", "..", "include", "ts_knn.h"),
            os.path.join("..", "..", "include", "ts_model.h"),
@@ -226,7 +233,8 @@ HEADERS = ["ts2d_common.h", "ts2d_radix.h", "ts2d_api.h", "ts_knn_front.h", "ts_
            os.path.join("..", "..", "include", "ts_subdivide.h"),
            os.path.join("..", "..", "include", "ts_flip.h"),
            os.path.join("..", "..", "include", "ts_collapse.h"),
-           os.path.join("..", "..", "include", "ts_decimate.h")]
+           os.path.join("..", "..", "include", "ts_decimate.h"),
+           os.path.join("..", "..", "include", "ts_contract.h")]
 
 
 def hipcc() -> str:
@@ -621,6 +629,24 @@ def decimate_objects() -> list:
     return [_object(u) for u in decimate_units()] + [_object(u) for u in DECIMATE_SHARED]
 
 
+def contract_units() -> list:
+    """The translation units of libts_contract.so that are its own (CONTRACT_SOURCES); it links the objects of CONTRACT_SHARED besides."""
+    return [_unit(k) for k in CONTRACT_SOURCES]
+
+
+def contract_command(unit: str, cc: str = "hipcc") -> list:
+    """The compile command of one unit of CONTRACT_SOURCES: COMMON + its flags, like command()."""
+    table = {_unit(k): (k, v) for k, v in CONTRACT_SOURCES.items()}
+    if unit not in table:
+        raise ValueError(f"unknown unit {unit!r}; the units of libts_contract.so are {', '.join(table)}")
+    key, flags = table[unit]
+    return [cc, *COMMON, *flags, "-c", os.path.join(CSRC, key), "-o", _object(unit)]
+
+
+def contract_objects() -> list:
+    return [_object(u) for u in contract_units()] + [_object(u) for u in CONTRACT_SHARED]
+
+
 def ext_command(cc: str = "hipcc") -> list:
     """The build command of the torch extension (the reference's ext.cpp signatures plus the package's *_ex entry points over the C ABI)."""
     import sysconfig
@@ -659,7 +685,7 @@ def build(force: bool = False, verbose: bool = False, lab: bool = False, variant
     hdr_t = max(_newest_header(), os.path.getmtime(me))
     jobs = []
     cmds = [command(u, extra.get(u, ()), variant, cc) for u in known]
-    if variant is None:  # the other eighteen product libraries: include/ts_geom.h, ts_bvh.h, ts_ray.h, ts_volume.h, ts_color.h, ts_simplify.h, ts_smooth.h, ts_holes.h, ts_manifold.h, ts_orient.h, ts_atlas.h, ts_inside.h, ts_winding.h, ts_overlap.h, ts_subdivide.h, ts_flip.h, ts_collapse.h, ts_decimate.h
+    if variant is None:  # the other nineteen product libraries: include/ts_geom.h, ts_bvh.h, ts_ray.h, ts_volume.h, ts_color.h, ts_simplify.h, ts_smooth.h, ts_holes.h, ts_manifold.h, ts_orient.h, ts_atlas.h, ts_inside.h, ts_winding.h, ts_overlap.h, ts_subdivide.h, ts_flip.h, ts_collapse.h, ts_decimate.h, ts_contract.h
         cmds += [geom_command(u, cc) for u in geom_units()] + [bvh_command(u, cc) for u in bvh_units()] + [ray_command(u, cc) for u in ray_units()]
         cmds += [volume_command(u, cc) for u in volume_units()] + [color_command(u, cc) for u in color_units()]
         cmds += [simplify_command(u, cc) for u in simplify_units()] + [smooth_command(u, cc) for u in smooth_units()]
@@ -668,7 +694,7 @@ def build(force: bool = False, verbose: bool = False, lab: bool = False, variant
         cmds += [inside_command(u, cc) for u in inside_units()] + [winding_command(u, cc) for u in winding_units()]
         cmds += [overlap_command(u, cc) for u in overlap_units()] + [subdivide_command(u, cc) for u in subdivide_units()]
         cmds += [flip_command(u, cc) for u in flip_units()] + [collapse_command(u, cc) for u in collapse_units()]
-        cmds += [decimate_command(u, cc) for u in decimate_units()]
+        cmds += [decimate_command(u, cc) for u in decimate_units()] + [contract_command(u, cc) for u in contract_units()]
     for cmd in cmds:
         s, o = cmd[-3], cmd[-1]
         os.makedirs(os.path.dirname(o), exist_ok=True)
@@ -715,7 +741,8 @@ def build(force: bool = False, verbose: bool = False, lab: bool = False, variant
                               (SUBDIVIDE_LIB, "libts_subdivide.so", subdivide_objects()),
                               (FLIP_LIB, "libts_flip.so", flip_objects()),
                               (COLLAPSE_LIB, "libts_collapse.so", collapse_objects()),
-                              (DECIMATE_LIB, "libts_decimate.so", decimate_objects())) if variant is None else ():
+                              (DECIMATE_LIB, "libts_decimate.so", decimate_objects()),
+                              (CONTRACT_LIB, "libts_contract.so", contract_objects())) if variant is None else ():
         cmd = [cc, "-shared", "-fPIC", f"--offload-arch={ARCH}", f"-Wl,-soname,{soname}", "-o", out, *objs]
         key = tool + "\n" + " ".join(cmd)
         if force or compiled.intersection(objs) or not _fresh(out, key, max(os.path.getmtime(o) for o in objs)):

@@ -125,6 +125,11 @@
                           budget of them per round; the quadrics follow the collapses, so the error is measured against the original
                           surface; same classes, guards and independent set as mesh_collapse.py; bit-equal to a numpy reference) -- the
                           pass that answers "this surface in N faces"; no counterpart in the reference; loaded on first use
+    mesh_contract.py      contract_round / placed_edges / contract_mesh / contract_fused (the same decimation by edge CONTRACTION:
+                          where both ends of an edge are free the survivor moves to the regularised minimum of the edge's quadric,
+                          rounded to fp32 first and judged there over the rings of both ends; attributes blend by how far it went;
+                          bit-equal to a numpy reference) -- the pass that answers "this surface in N faces" with vertices where the
+                          planes say the surface is; no counterpart in the reference; loaded on first use
     metrics.py           psnr, ssim (= 1 - SSIMLoss), evaluate_mesh and evaluate_vertex_colors: PSNR / SSIM of a mesh's opaque render (one
                           colour per face, or per vertex) against each view's gt_image
                           (reference: src/diff_recon/trainers/trainer_utils.py:331-336, VanillaTS_trainer.py:156-190)
@@ -132,7 +137,7 @@
                           replayed with one launch -- no counterpart in the reference, whose forward reads num_rendered back every step
 
 Native code: libts2d.so (include/ts_loss.h, include/ts_model.h, include/ts_optim.h, include/ts2d.h, include/ts_mesh.h, include/ts_weld.h) and, for
-mesh_distance.py, libts_geom.so beside this file (include/ts_geom.h), for mesh_surface.py, libts_bvh.so (include/ts_bvh.h), for mesh_ray.py, libts_ray.so (include/ts_ray.h), for volume.py, libts_volume.so (include/ts_volume.h), for color_volume.py, libts_color.so (include/ts_color.h), for mesh_simplify.py, libts_simplify.so (include/ts_simplify.h), for mesh_smooth.py, libts_smooth.so (include/ts_smooth.h), for mesh_holes.py, libts_holes.so (include/ts_holes.h), for mesh_manifold.py, libts_manifold.so (include/ts_manifold.h), for mesh_orient.py, libts_orient.so (include/ts_orient.h), for mesh_texture.py, libts_atlas.so (include/ts_atlas.h), for mesh_inside.py, libts_inside.so (include/ts_inside.h), for mesh_winding.py, libts_winding.so (include/ts_winding.h), for mesh_overlap.py, libts_overlap.so (include/ts_overlap.h), for mesh_subdivide.py, libts_subdivide.so (include/ts_subdivide.h), for mesh_flip.py, libts_flip.so (include/ts_flip.h), for mesh_collapse.py, libts_collapse.so (include/ts_collapse.h), for mesh_decimate.py, libts_decimate.so (include/ts_decimate.h).  No CPU / eager fallback anywhere.
+mesh_distance.py, libts_geom.so beside this file (include/ts_geom.h), for mesh_surface.py, libts_bvh.so (include/ts_bvh.h), for mesh_ray.py, libts_ray.so (include/ts_ray.h), for volume.py, libts_volume.so (include/ts_volume.h), for color_volume.py, libts_color.so (include/ts_color.h), for mesh_simplify.py, libts_simplify.so (include/ts_simplify.h), for mesh_smooth.py, libts_smooth.so (include/ts_smooth.h), for mesh_holes.py, libts_holes.so (include/ts_holes.h), for mesh_manifold.py, libts_manifold.so (include/ts_manifold.h), for mesh_orient.py, libts_orient.so (include/ts_orient.h), for mesh_texture.py, libts_atlas.so (include/ts_atlas.h), for mesh_inside.py, libts_inside.so (include/ts_inside.h), for mesh_winding.py, libts_winding.so (include/ts_winding.h), for mesh_overlap.py, libts_overlap.so (include/ts_overlap.h), for mesh_subdivide.py, libts_subdivide.so (include/ts_subdivide.h), for mesh_flip.py, libts_flip.so (include/ts_flip.h), for mesh_collapse.py, libts_collapse.so (include/ts_collapse.h), for mesh_decimate.py, libts_decimate.so (include/ts_decimate.h), for mesh_contract.py, libts_contract.so (include/ts_contract.h).  No CPU / eager fallback anywhere.
 """
 from .losses import L1, SSIMLoss, ssimLoss, PhotometricLoss, photometric_loss, DepthNormalLoss, DoGLoss, SmoothnessLoss, dogLoss, smoothnessLoss, downsample_bilinear, downsample_bilinear_many  # noqa: F401
 from .triangle_renderer import TriangleRenderer  # noqa: F401
@@ -179,6 +184,8 @@ _COLLAPSE_NAMES = ("COLLAPSE_STATES", "COLLAPSE_GUARDS", "CollapsedMesh", "Coars
                    "collapse_short_edges", "collapse_fused", "isotropic_remesh")
 _DECIMATE_NAMES = ("DECIMATE_STATES", "DecimatedRound", "DecimatedMesh", "vertex_quadrics", "decimate_round", "cheapest_edges", "decimate_mesh",
                    "decimate_fused")
+_CONTRACT_NAMES = ("CONTRACT_STATES", "CONTRACT_GUARDS", "ContractedRound", "ContractedMesh", "contract_round", "placed_edges", "contract_mesh",
+                   "contract_fused")
 
 
 def __getattr__(name):
@@ -247,4 +254,8 @@ def __getattr__(name):
         import importlib
         module = importlib.import_module(".mesh_decimate", __name__)
         return module if name == "mesh_decimate" else getattr(module, name)
+    if name in _CONTRACT_NAMES or name == "mesh_contract":  # mesh_contract.py and libts_contract.so likewise
+        import importlib
+        module = importlib.import_module(".mesh_contract", __name__)
+        return module if name == "mesh_contract" else getattr(module, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

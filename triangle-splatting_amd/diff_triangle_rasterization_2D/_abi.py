@@ -581,3 +581,24 @@ def bind_decimate(lib):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     return lib
+
+
+# include/ts_contract.h: the whole C ABI of diff_recon_hip/libts_contract.so, the twentieth library (diff_recon_hip/mesh_contract.py loads and binds it)
+CONTRACT_SIGNATURES = {
+    "tsu_last_error": (C.c_char_p, []),
+    "tsu_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "tsu_contract": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_float, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float,
+                               C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+}
+
+
+def bind_contract(lib):
+    """Sets restype and argtypes of every function of include/ts_contract.h on `lib` (a ctypes.CDLL of libts_contract.so); a library that
+    lacks one is refused."""
+    missing = [name for name in CONTRACT_SIGNATURES if not hasattr(lib, name)]
+    if missing:
+        raise ImportError(f"{getattr(lib, '_name', lib)} does not export {', '.join(missing)}: rebuild it with `python triangle-splatting_amd/build.py`")
+    for name, (restype, argtypes) in CONTRACT_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return lib
